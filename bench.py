@@ -2,6 +2,15 @@
 """SDS train-steps/sec of Make-It-3D's coarse stage on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2_dense|c2_pruned|c4_views|c5_refine|small]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, settles the loss scale, warms up, times K steps and prints the headline line (`metric`, `value`,
+`unit`, `ms_per_step`, ...).  Everything else the line can carry - the variants, roofline (it needs an untimed census
+step), CPU baseline, reference-shaped baseline, dense-gradient figures, clock log - is measured only with `--full`.
+`--dump-outputs DIR` writes DIR/<name>.npy after the timed steps: for a training workload, what one step of the timed
+path computes from a freshly seeded state (replay_headline_step: its render and orientation loss; the refine workload:
+its loss), for c4_views the last timed render.  Inputs are seeded, so runs with the same arguments - of one build or of
+two - compare output for output.
 
 One step = one pass of the hot path over one novel view (BASELINE config 2): 128x128 rays, max_steps 1024,
 16-level hash grid + 3x64 MLP (fp16 autocast), march -> 13-point field -> composite, SD2-base-shaped U-Net noise
@@ -22,7 +31,7 @@ pair records of round 2 are faster than it was).  `variants_ms_per_step` adds tw
 nerf/utils.py, each timed on its own steps: the hand-merged single backward, and "overlapped" = the reference's two
 backward passes with the U-Net on a second HIP stream under the regulariser pass (mi3d/sds_step.py).
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     : the step's dominant kernel - algorithmic bytes per launch (1024 B per field evaluation
                  gathered, 2048 B read-modify-written by the scatter) over its launch duration measured with HIP events
                  on the launch stream during the timed steps; the other hot kernels under rooflines_other; `traffic` =
@@ -69,6 +78,12 @@ ENCODE_BYTES_PER_EVAL = 1024   # 16 levels x 8 corners x 2 features
 SCATTER_BYTES_PER_EVAL = 2048  # the same bytes read-modify-written by the gradient scatter
 T_FIXED = 500  # SDS branch under the reference's rule (nerf/sd.py:153: t/1000 <= 0.4 takes the CLIP branch instead)
 HEADLINE = ("fp32", "reference")
+# MIOpen's find step for the U-Net / VAE convolutions compiles its naive reference kernels as candidates on a cold kernel
+# cache (~30 s of the first step in a fresh home directory) and never picks them: measured on the step's 58
+# configurations they were 4x to 140x (median) slower than the implicit-GEMM / Winograd / GEMM solver that won.  The
+# benchmark leaves them out of the search.
+MIOPEN_SKIPPED_CANDIDATES = ("MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_FWD", "MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_BWD",
+                             "MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_WRW")
 
 
 def ensure_built():
@@ -493,6 +508,68 @@ def summarise_ranks(records, expected_updates, backend, group_world_size, launch
             "valid": not problems, "problems": problems}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_MAX_ELEMENTS = 1 << 20   # a larger array is written as a fixed seeded sample of this many elements
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every (name, tensor) of `arrays` as out_dir/<name>.npy - float64 stays float64, every other dtype
+    becomes float32.  An array of more than DUMP_MAX_ELEMENTS elements is flattened and sampled at indices drawn from a
+    generator seeded with 0 (the same indices for the same size in every run); arrays past the 64 MB budget are dropped
+    and named in the returned manifest."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    manifest, used = {}, 0
+    for name, t in arrays:
+        if torch.is_tensor(t):
+            a = (t.detach() if t.dtype == torch.float64 else t.detach().float()).cpu().numpy()
+        else:
+            a = np.asarray(t, dtype=np.float64)
+        entry = {"shape": list(a.shape)}
+        if a.size > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            a = a.reshape(-1)[idx]
+            entry["sampled"] = DUMP_MAX_ELEMENTS
+        if used + a.nbytes > DUMP_BUDGET_BYTES:
+            manifest[name] = dict(entry, dropped="over the 64 MB budget")
+            continue
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        used += a.nbytes
+        manifest[name] = entry
+    return manifest
+
+
+def replay_headline_step(opt, wl, dev, guidance, text_z, rays, seed, init_scale):
+    """--dump-outputs of a training workload: ONE headline step (the timed path: sds_train_step, the reference's
+    two-backward schedule, t = T_FIXED) on a freshly built, seeded training state and a re-seeded generator, untimed,
+    after the timed steps.  The timed steps' own last state is not a function of the inputs alone: how many settle
+    steps overflow, and whether a timed step does, varies from run to run (and a re-timed region adds steps).
+    Returned: the step's render (image, depth, weights_sum) and its orientation loss - every sample's terms are fixed
+    by the inputs; the smoothness loss, and with it the total loss, the gradients and the update, are not: its jitter is
+    one torch.randn_like row per sample in the march's row order, which the march's atomics make differ per run."""
+    import torch
+    from mi3d import sds_step
+    model, optimizer, scaler = sds_step.build_training_state(opt, dev, seed=0, bitfield=wl["bitfield"],
+                                                             init_scale=init_scale)
+    captured = {}
+    render = model.render
+
+    def capture(*a, **k):
+        captured["out"] = render(*a, **k)
+        return captured["out"]
+    model.render = capture
+    torch.manual_seed(seed)
+    ro, rd, ds = rays
+    sds_step.sds_train_step(model, guidance, text_z, optimizer, scaler, ro, rd, ds, wl["H"], wl["W"], opt,
+                            sds_backward=HEADLINE[1], t=T_FIXED)
+    torch.cuda.synchronize()
+    out = captured["out"]
+    arrays = [(k, out[k]) for k in ("image", "depth", "weights_sum", "loss_orient") if k in out]
+    del model, optimizer, scaler, captured, out
+    return arrays
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` outside a launcher: become the launcher (one rank per GPU on this node)."""
     port = 29500 + (os.getpid() % 2000)
@@ -532,9 +609,22 @@ def main():
                     help="do not sample the GPU's clocks / power on a background thread during the timed region")
     ap.add_argument("--refresh-every", type=int, default=16,
                     help="update_extra_state interval inside the timed loop (nerf/utils.py:970-972; 0 = never)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: CPU baselines, the reference-shaped leg, the non-headline "
+                         "variants, the scatter census behind the roofline, dense-gradient figures and the clock log.  "
+                         "Without it a run sets up, settles the loss scale, warms up, times --steps steps and prints the "
+                         "headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computes from the seeded inputs (one "
+                         "untimed step on a freshly seeded state; c4_views: the last timed render) as DIR/<name>.npy, "
+                         "float32 / float64, <= 64 MB in all")
     args = ap.parse_args()
-    if args.profile_run:
+    if args.profile_run:   # (its line is read against the trace: census step + roofline as --full, no legs after the steps)
+        args.full = True
         args.variant_steps, args.no_cpu_baseline, args.no_reference_shaped = 0, True, True
+    if not args.full:
+        args.variant_steps, args.no_cpu_baseline, args.no_reference_shaped = 0, True, True
+        args.no_clock_log = True
 
     if args.cpu_baseline_only:   # child process of cpu_baseline(): host cores only, no GPU
         wl = WORKLOADS[args.workload]
@@ -557,6 +647,8 @@ def main():
             print(json.dumps(cpu_baseline_port(wl)))
         return
 
+    for k in MIOPEN_SKIPPED_CANDIDATES:   # (before torch loads MIOpen)
+        os.environ.setdefault(k, "0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args.gpus)
     rank = int(os.environ.get("RANK", 0))
@@ -627,9 +719,9 @@ def main():
         def render_step():
             for ro, rd, ds in view_rays:
                 with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16, enabled=opt.fp16):
-                    the_model.render(ro, rd, depth_scale=ds, bg_color=torch.rand(3, device=dev), staged=False,
-                                     perturb=True, ambient_ratio=1.0, shading="albedo", force_all_rays=True,
-                                     **sds_step.render_kwargs(opt))
+                    last["render"] = the_model.render(ro, rd, depth_scale=ds, bg_color=torch.rand(3, device=dev),
+                                                      staged=False, perturb=True, ambient_ratio=1.0, shading="albedo",
+                                                      force_all_rays=True, **sds_step.render_kwargs(opt))
         if render_only:
             return render_step
 
@@ -679,6 +771,7 @@ def main():
     # collective for the slowest rank: its per-rank spread is the skew the step time hides)
     grad_sync = timed("all_reduce", bucket.all_reduce_mean) if dist.is_initialized() else bucket.all_reduce_mean
     step_extra = {}     # extra arguments of sds_train_step (the denoise + CLIP variant sets them)
+    last = {}           # the most recent render of a render-only workload (--dump-outputs)
 
     def run(records, schedule, steps, warmup):
         step = make_step(model, optimizer, scaler, schedule, grad_sync)
@@ -753,7 +846,7 @@ def main():
     # ---- untimed, BEFORE the timed region (so that a --profile-run trace ends with the timed steps): which gradient pairs
     # one step's scatter actually carries
     census = None
-    if not render_only:
+    if not render_only and args.full:
         grid_ops.CENSUS = []
         make_step(model, optimizer, scaler, HEADLINE[1], grad_sync)()
         torch.cuda.synchronize()
@@ -793,6 +886,12 @@ def main():
         elapsed, prof, info = run(*HEADLINE, args.steps, args.warmup)
         log(f"headline (re-timed): {1e3 * elapsed / args.steps:.1f} ms/step, {info['applied']} of "
             f"{args.steps * views} updates applied, loss scale {info['scale_before']} -> {info['scale_after']}")
+    if args.dump_outputs and rank == 0:
+        if render_only:   # no training: the last timed render is a function of the seeded weights and draws alone
+            arrays = [(k, v) for k, v in last["render"].items() if torch.is_tensor(v)]
+        else:
+            arrays = replay_headline_step(opt, wl, dev, guidance, text_z, view_rays[0], seed, args.init_scale)
+        log(f"wrote {len(dump_outputs(args.dump_outputs, arrays))} arrays to {args.dump_outputs}")
     ranks = None
     if dist.is_initialized() and not render_only:
         ranks = summarise_ranks(
@@ -802,7 +901,7 @@ def main():
                                  "grad_scaler_scale_after": info["scale_after"], "peak_mem_GiB": info["peak_mem_GiB"],
                                  "views": view_ids, "device": torch.cuda.get_device_name(dev)}),
             args.steps * views, dist.get_backend(), dist.get_world_size(), world)
-    steps_run_total = tries + 1 + (1 + retimed) * (args.warmup + args.steps)   # settle + census + warm-up + timed
+    steps_run_total = tries + int(args.full) + (1 + retimed) * (args.warmup + args.steps)   # settle + census + warm-up + timed
     variants = {f"records={HEADLINE[0]},sds_backward={HEADLINE[1]}": 1e3 * elapsed / args.steps}
     dense_step, clip_step = None, None
     if args.variant_steps > 0 and not render_only:
@@ -873,7 +972,7 @@ def main():
 
     # ---- untimed: the 13-point scatter on dense random gradients
     dense = None
-    if not render_only and not args.profile_run and rank == 0 and world == 1:
+    if args.full and not render_only and not args.profile_run and rank == 0 and world == 1:
         dense = scatter_on_dense_gradients(model, view_rays[0], opt, dev)
     m = int(model.step_counter[(model.local_step - 1) % 16, 0].item())
     line = None
@@ -968,8 +1067,6 @@ def main():
                         "parallelism": f"dp{world} (one view per GPU, flat {bucket.nbytes / 1e6:.1f} MB grad "
                                        f"all-reduce)"}),
             "variants_ms_per_step": variants,
-            "roofline": roofs[0],
-            "rooflines_other": roofs[1:],
             "kernels_ms_per_step": {k: sum(v) / args.steps for k, v in ms.items() if not k.startswith("phase:")},
             # exclusive phases of the step (HIP events on the launch stream): their sum is the step
             "phases_ms_per_step": {k[6:]: sum(v) / args.steps for k, v in ms.items() if k.startswith("phase:")},
@@ -981,6 +1078,8 @@ def main():
             "clocks": info.get("clocks"),
         }
         line["phases_ms_per_step"]["unattributed"] = line["ms_per_step"] - sum(line["phases_ms_per_step"].values())
+        if args.full:   # (the scatter's algorithmic bytes come from the census step, which only --full runs)
+            line["roofline"], line["rooflines_other"] = roofs[0], roofs[1:]
         if census is not None:
             line["grad_nonzero_pair_fraction"] = {
                 ("sds_pass_point0" if k == 1 else
@@ -1086,17 +1185,21 @@ def bench_refine(args, wl, dev, rank, world):
     import torch
     import torch.distributed as dist
     from mi3d import rays as R, refine, sd_standin
-    torch.manual_seed(rank)
     P, H, W = wl["points"], wl["H"], wl["W"]
-    d = torch.randn(P, 3, device=dev)
-    points = (d / d.norm(dim=-1, keepdim=True) * 0.35 * (1 + 0.05 * torch.randn(P, 1, device=dev))).contiguous()
-    colour = torch.nn.Parameter(torch.rand(P, 3, device=dev))
-    feat = torch.nn.Parameter(torch.randn(P, 16, device=dev))
-    origin = colour.detach().clone()
-    unet = refine.UNet(num_input_channels=19).to(dev).train()
-    params = {"colour": colour, "feat": feat}
-    optimizer = torch.optim.Adam([{"params": [colour, feat], "lr": 1e-3}, {"params": unet.parameters(), "lr": 1e-3}],
-                                 betas=(0.9, 0.99), eps=1e-15)
+
+    def training_state():
+        torch.manual_seed(rank)
+        d = torch.randn(P, 3, device=dev)
+        points = (d / d.norm(dim=-1, keepdim=True) * 0.35 * (1 + 0.05 * torch.randn(P, 1, device=dev))).contiguous()
+        colour = torch.nn.Parameter(torch.rand(P, 3, device=dev))
+        feat = torch.nn.Parameter(torch.randn(P, 16, device=dev))
+        origin = colour.detach().clone()
+        unet = refine.UNet(num_input_channels=19).to(dev).train()
+        optimizer = torch.optim.Adam([{"params": [colour, feat], "lr": 1e-3}, {"params": unet.parameters(), "lr": 1e-3}],
+                                     betas=(0.9, 0.99), eps=1e-15)
+        return points, {"colour": colour, "feat": feat}, origin, unet, optimizer
+    points, params, origin, unet, optimizer = training_state()
+    colour, feat = params["colour"], params["feat"]
     guidance = sd_standin.StableDiffusionStandIn(dev)
     text_z = guidance.get_text_embeds()
     t_fixed = T_FIXED  # an int: the guidance decides its branch on the host without a device sync
@@ -1123,24 +1226,42 @@ def bench_refine(args, wl, dev, rank, world):
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    # the point renderer alone (4 rasterise + composite passes of one iteration), HIP events on the launch stream
-    feats = torch.cat((colour, feat), -1).detach()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    reps = 5
-    for _ in range(reps):
-        for sc in (1, 2, 4):
-            refine.render_point(points, feats, H // sc, W // sc, refine.intrinsics(focal, H // sc, W // sc, dev), w2c,
-                                (H // sc, W // sc), radius, wl["ppp"])
-        refine.render_point(points, torch.ones_like(points), H, W, refine.intrinsics(focal, H, W, dev), w2c, (H, W),
-                            radius, wl["ppp"])
-    e1.record()
-    torch.cuda.synchronize()
-    render_ms = e0.elapsed_time(e1) / reps
-    px = sum((H // s) * (W // s) for s in (1, 2, 4)) + H * W
-    alg = 4 * P * 12 + px * wl["ppp"] * 16 + (px - H * W) * 19 * 4 + H * W * 3 * 4   # points in, idx+dists out and back in, images out
-    if rank == 0:
+    if args.dump_outputs and rank == 0:
+        # as replay_headline_step: ONE step of the timed path on a freshly seeded state, untimed - its loss (the forward:
+        # the rasteriser's depth tie-break makes it independent of the atomic list order).  The update is not dumped:
+        # the backward adds into each hit point's features with float atomics, in an order that differs per run.
+        r_points, r_params, r_origin, r_unet, r_optimizer = training_state()
+        torch.manual_seed(1234 + rank)
+        loss = refine.refine_train_step(r_unet, r_params, r_optimizer, guidance, text_z, r_points, w2c, focal, H, W, radius,
+                                        wl["ppp"], r_origin, guidance_scale=5.0, t=t_fixed)
+        log(f"wrote {len(dump_outputs(args.dump_outputs, [('loss', loss)]))} arrays to {args.dump_outputs}")
+        del r_points, r_params, r_origin, r_unet, r_optimizer
+    extra = {}
+    if args.full:
+        # the point renderer alone (4 rasterise + composite passes of one iteration), HIP events on the launch stream
+        feats = torch.cat((colour, feat), -1).detach()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        reps = 5
+        for _ in range(reps):
+            for sc in (1, 2, 4):
+                refine.render_point(points, feats, H // sc, W // sc, refine.intrinsics(focal, H // sc, W // sc, dev), w2c,
+                                    (H // sc, W // sc), radius, wl["ppp"])
+            refine.render_point(points, torch.ones_like(points), H, W, refine.intrinsics(focal, H, W, dev), w2c, (H, W),
+                                radius, wl["ppp"])
+        e1.record()
+        torch.cuda.synchronize()
+        render_ms = e0.elapsed_time(e1) / reps
+        px = sum((H // s) * (W // s) for s in (1, 2, 4)) + H * W
+        alg = 4 * P * 12 + px * wl["ppp"] * 16 + (px - H * W) * 19 * 4 + H * W * 3 * 4   # points in, idx+dists out and back in, images out
         a = alg / (render_ms * 1e-3) / 1e9
+        extra = {
+            "roofline": {"kernel": "point renderer: k_raster_count/scan/fill/tiles + k_points_composite_fwd x 4 passes "
+                                   "(csrc/raster.hip)", "bound": "hbm", "achieved": a, "peak": HBM_PEAK_GBPS,
+                         "unit": "GB/s", "frac": a / HBM_PEAK_GBPS, "traffic": None, "avg_launch_ms": render_ms,
+                         "note": "latency / atomics bound at this size (a few MB per pass): reported for completeness"},
+            "render_ms_per_step": render_ms}
+    if rank == 0:
         print(json.dumps({
             "metric": "refine-stage SDS train-steps/sec (point rasterise + U-Net + SD U-Net), BASELINE config 5",
             "value": world * args.steps / elapsed, "unit": "refine-steps/s", "n_gpus": world, "steps": args.steps,
@@ -1150,11 +1271,7 @@ def bench_refine(args, wl, dev, rank, world):
             "config": {"workload": f"{args.workload}: {P} points, {H}x{W} (+ /2, /4, + mask pass), radius {wl['radius_px']} px, "
                                    f"{wl['ppp']} points per pixel, gated U-Net 19->3, SD2-base-shaped U-Net SDS (t={T_FIXED})",
                        "parallelism": f"dp{world} (independent views)"},
-            "roofline": {"kernel": "point renderer: k_raster_count/scan/fill/tiles + k_points_composite_fwd x 4 passes "
-                                   "(csrc/raster.hip)", "bound": "hbm", "achieved": a, "peak": HBM_PEAK_GBPS,
-                         "unit": "GB/s", "frac": a / HBM_PEAK_GBPS, "traffic": None, "avg_launch_ms": render_ms,
-                         "note": "latency / atomics bound at this size (a few MB per pass): reported for completeness"},
-            "render_ms_per_step": render_ms}))
+            **extra}))
     if world > 1:
         dist.destroy_process_group()
 
