@@ -294,10 +294,16 @@ int mi3d_mlp_forward(const void *x, uint32_t x_plane_rows, int planes_half, uint
 /* Backward of the above for upstream gradient dout [n, dim_out]: writes dx and ACCUMULATES the weight and bias
  * gradients (fp32, same layouts as the weights; caller zeroes them).  Activations are recomputed.
  * dx_plane_rows == 0: dx is [n, dim_in] rows; otherwise dx is level-major planes [dim_in/2][dx_plane_rows][2]
- * (feature pair (2l, 2l+1) of row r at dx[(l*dx_plane_rows + r)*2]), the layout mi3d_grid_scatter_binned consumes. */
+ * (feature pair (2l, 2l+1) of row r at dx[(l*dx_plane_rows + r)*2]), the layout mi3d_grid_scatter_binned consumes.
+ * ALIASING: dx may be x itself (dx == x) when both have the same layout - dx_plane_rows == x_plane_rows (0 = rows for both)
+ * - and therefore the same element type (planes_half covers both): the gradient of a row replaces the row.  Any n is
+ * allowed, a partial last tile (n % 32 != 0) and plane rows past n included; those rows keep their contents.  A wave reads
+ * the 32 rows of its tile before it stores their gradients and no other wave reads them (rows past n are read as row n - 1
+ * by the wave that owns row n - 1).  dx == x in different layouts returns hipErrorInvalidValue; buffers that overlap in any
+ * other way, and dout or a weight overlapping an output, are undefined.  In the forward, `out` must not overlap x. */
 /* The same with a DEVICE-side row count (the inference loop's control block, Part 1b): rows are point-major with
  * `n_stride` rows per stencil point, and only samples s < *count carry data; tiles wholly beyond it are skipped and
- * their outputs left untouched.  count == NULL: every row.  (The gather and the head have the same variant.) */
+ * their outputs left untouched, and so is every row s >= *count of a tile that straddles it.  count == NULL: every row.  (The gather and the head have the same variant.) */
 int mi3d_mlp_forward_counted(const void *x, uint32_t x_plane_rows, int planes_half, uint32_t n, const int32_t *count,
                              uint32_t n_stride, const float *W1, const float *b1, const float *W2, const float *b2,
                              const float *W3, const float *b3, uint32_t dim_in, uint32_t dim_hidden, uint32_t dim_out,

@@ -113,14 +113,17 @@ struct F16 {
         return k;
     }
     // accumulator tile -> ReLU'd K-block: packed convert (the layer output is rounded to binary16 first, as autocast
-    // does), packed max.  The K-block itself is the ReLU mask later on (value > 0 <=> bits != 0).
+    // does), packed max.  The K-block itself is the ReLU mask later on (value > 0 <=> bits != 0).  The max is IEEE 754-2019
+    // `maximum` (v_pk_maximum3_f16): a NaN stays a NaN, as torch.relu keeps it (maxnum - v_pk_max_f16 - handed back 0, and an
+    // overflowed input came out as finite numbers), and max(-0, +0) is +0, which masked() below relies on (0x8000 would
+    // count as an open unit).
     __device__ static __forceinline__ KB relu(const f32x16 &acc) {
         KB k;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const f32x2 pr = {acc[2 * j], acc[2 * j + 1]};
             half2v hv = __builtin_convertvector(pr, half2v);
-            hv = __builtin_elementwise_max(hv, half2v{(_Float16)0, (_Float16)0});
+            hv = __builtin_elementwise_maximum(hv, half2v{(_Float16)0, (_Float16)0});
             k.v[j >> 2][2 * (j & 3)] = hv[0];
             k.v[j >> 2][2 * (j & 3) + 1] = hv[1];
         }
@@ -459,9 +462,9 @@ struct Grads {
 // different accumulators - and only then converts them, which gives the in-order wave four independent chains to
 // overlap (the packed converts of one accumulator run under the MFMAs of the next).
 template <class P, int U, int WPS, bool HP>
-__global__ __launch_bounds__(kWave *kWavesPerWG, WPS) void k_mlp_backward(const float *__restrict__ x, uint32_t x_planes,
+__global__ __launch_bounds__(kWave *kWavesPerWG, WPS) void k_mlp_backward(const float *x, uint32_t x_planes,
                                                                            int /*planes_half: HP*/, const float *__restrict__ dout,
-                                                                           uint32_t n, Weights w, float *__restrict__ dx,
+                                                                           uint32_t n, Weights w, float *dx,
                                                                            uint32_t dx_planes, Grads g) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     float *bias = reinterpret_cast<float *>(lds + (size_t)B_ALL_COUNT * block_bytes<P>());
@@ -1009,9 +1012,11 @@ __global__ __launch_bounds__(kWave *kWavesPerWG, 2) void k_mlp_fwd_g(const float
     // carry data - a tile all of whose rows are beyond it is skipped (its outputs are never read)
     const uint32_t c_rows = count ? (uint32_t)max(*count, 0) : 0xFFFFFFFFu;
     for (uint32_t tile = wave; tile < n_tiles; tile += n_waves) {
+        bool live = true;   // (counted: a tile that straddles the count stores its live samples only)
         if (count) {
             const uint32_t s0 = (tile * 32u) % n_stride;
             if (s0 >= c_rows && s0 + 32u <= n_stride) continue;
+            live = (s0 + (uint32_t)p) % n_stride < c_rows;
         }
         const size_t row = (size_t)tile * 32 + p;
         KB X;
@@ -1046,17 +1051,19 @@ __global__ __launch_bounds__(kWave *kWavesPerWG, 2) void k_mlp_fwd_g(const float
         f32x16 acc = bias(2 * NTH);
 #pragma unroll
         for (int tk = 0; tk < NTH; ++tk) P::mma(acc, blk(B::W3 + tk), HL[tk]);
-        if (row < n && h == 0) {
+        if (row < n && h == 0 && live) {
             f32x4 o = {P::round(acc[0]), P::round(acc[1]), P::round(acc[2]), P::round(acc[3])};
             __builtin_nontemporal_store(o, reinterpret_cast<f32x4 *>(out + row * DOUT));
         }
     }
 }
 
+// x and dx carry no __restrict__ in the backward kernels: mi3d.h lets dx BE x (same layout), and the product calls it so.
+// (Register counts and scratch of every instance are the same with and without the qualifier - hipcc 7.2, gfx950.)
 template <class P, int NTH, int LAYERS, bool HP, bool FULL>   // FULL: dim_in = 32 (plane indices and store guards constant)
-__global__ __launch_bounds__(kWave *kWavesPerWG, (MI3D_MLP_BWD_TIMING_CUT & 4) ? 3 : 2) void k_mlp_bwd_g(const float *__restrict__ x, uint32_t x_planes,
+__global__ __launch_bounds__(kWave *kWavesPerWG, (MI3D_MLP_BWD_TIMING_CUT & 4) ? 3 : 2) void k_mlp_bwd_g(const float *x, uint32_t x_planes,
                                                                         const float *__restrict__ dout, uint32_t n,
-                                                                        uint32_t din, Weights w, float *__restrict__ dx,
+                                                                        uint32_t din, Weights w, float *dx,
                                                                         uint32_t dx_planes, Grads g) {
     using B = Blk<NTH, LAYERS>;
     using KB = typename P::KB;
@@ -1618,6 +1625,9 @@ int mi3d_mlp_backward(const void *xv, uint32_t x_plane_rows, int planes_half, co
         W3 == nullptr || b3 == nullptr || dW1 == nullptr || db1 == nullptr || dW3 == nullptr || db3 == nullptr ||
         (layers == 3 && (W2 == nullptr || b2 == nullptr || dW2 == nullptr || db2 == nullptr)))
         return (int)hipErrorInvalidValue;
+    // dx may be x itself, in the same layout only (mi3d.h): a row's gradient then lands where the wave that owns the row
+    // has already read it.  (planes_half covers both, so the element types cannot differ.)
+    if (dxv == xv && dx_plane_rows != x_plane_rows) return (int)hipErrorInvalidValue;
     if (n == 0) return 0;
     const float *x = reinterpret_cast<const float *>(xv);
     float *dx = reinterpret_cast<float *>(dxv);

@@ -232,11 +232,13 @@ def _backward_mlp(dh, feats, ws, dims, x, cfg, half_mode, P_active, in_place=Fal
     first P_active points of the stencil only.  `in_place`: the gradient planes are written OVER the feature planes (the
     caller knows them dead after this pass) - a wave reads a tile's 32 rows of every plane into registers before it stores
     the same rows' gradients and no other wave touches those rows, so the kernel is indifferent; 9.05 GB less at the step's
-    memory peak.  Only for whole passes over whole tiles (rows == plane rows, a multiple of 32: a partial tile's idle lanes
-    re-read the last row, which another wave may have overwritten by then)."""
+    memory peak.  The rule is the C ABI's (include/mi3d.h Part 4: dx == x in the same layout with the same plane rows,
+    anything else is hipErrorInvalidValue), hence rows == plane rows.  Any row count will do: the idle lanes of a partial
+    last tile re-read row n - 1, which belongs to their own wave's tile and is stored after its reads
+    (tests/test_mlp_exact_gpu.py runs every instance in place with n % 32 != 0 against the out-of-place planes, bit for bit)."""
     n = x.shape[0]
     rows, plane_rows = P_active * n, feats.shape[1]
-    if in_place and rows == plane_rows and rows % 32 == 0 and feats.is_contiguous():
+    if in_place and rows == plane_rows and feats.is_contiguous():
         dplanes = feats
     else:
         # binary16 gradient planes under autocast: what the reference's binary16 dgrad GEMM hands the encoder's backward
