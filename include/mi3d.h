@@ -33,7 +33,8 @@ extern "C" {
 #define MI3D_MAX_POINTS 16
 
 /* the ABI version: 5 (4 = 3 + the compact-round inference loop of Part 1b; 5: that loop's ctl block is int32[16] with
- * the dropped-row count in [8], and its plan never passes max_steps; every other entry point is unchanged) */
+ * the dropped-row count in [8], and its plan never passes max_steps; every other entry point is unchanged).  Part 8
+ * (marching cubes) was added under 5: new symbols only, nothing existing changed. */
 int mi3d_abi_version(void);
 const char *mi3d_last_error_string(int err);
 
@@ -377,6 +378,53 @@ int mi3d_points_composite_forward(const int32_t *idx, const float *dists, uint32
 int mi3d_points_composite_backward(const int32_t *idx, const float *dists, uint32_t H, uint32_t W,
                                    uint32_t points_per_pixel, const float *grad_out, uint32_t C, double radius,
                                    float *grad_features, void *stream);
+
+/* ------------------------------------------------------------------ Part 8: marching cubes (mesh export) */
+
+/* A dense scalar volume -> a WELDED, INDEXED triangle mesh in a deterministic order: what `mcubes.marching_cubes` does
+ * for the reference's export_mesh (nerf/renderer.py:182).  PyMCubes is on no machine this project builds on and its
+ * conventions can only be quoted from memory, so the semantics below are this project's own contract - PARITY UNPINNED,
+ * the standing tiny-cuda-nn's (Part 2) and pytorch3d's (Part 7) restatements have.
+ *
+ * vol float[Rx*Ry*Rz], x slowest: grid point (i, j, k) at (i*Ry + j)*Rz + k; each of Rx, Ry, Rz in [2, 1024].
+ *   - A grid point is INSIDE iff vol >= iso (NaN is outside).  iso must not be NaN.
+ *   - Cube corners 0..7 sit at the min corner + (0,0,0) (1,0,0) (1,1,0) (0,1,0) (0,0,1) (1,0,1) (1,1,1) (0,1,1), cube
+ *     edges 0..11 join corners 0-1 1-2 2-3 3-0 4-5 5-6 6-7 7-4 0-4 1-5 2-6 3-7 (the numbering of Bourke's
+ *     "Polygonising a scalar field"); bit c of the case index is set iff corner c is inside.
+ *   - The 256-case table (csrc/mi3d_mc_tables.h, constructed by tools/gen_mc_tables.py, read back through mi3d_mc_case)
+ *     cuts off the INSIDE corners separately on every ambiguous face, so the segments a cube leaves on a face depend on
+ *     that face's four corners alone and the neighbour has the same segments reversed: meshes have no cracks.  At most
+ *     five triangles per cube.  tests/test_mc_tables_cpu.py states and checks the properties.
+ *   - Every grid edge whose ends differ in side owns exactly ONE vertex.  On the edge from point a to b = a + e_axis it
+ *     sits, in index units, at a_axis + t, t = (iso - va) / (vb - va) in binary32, each operation rounded once; t outside
+ *     [0, 1] (NaN included: a non-finite va or vb) becomes 0.5.  Written: origin_host[c] + spacing_host[c] * (a_c + t_c)
+ *     per coordinate c (t_c = t on the edge's axis, 0 elsewhere) as three separately rounded binary32 operations - the add
+ *     in the parentheses, the multiply, the add; no fused multiply-add.
+ *   - Triangles are wound so that normals point from inside to outside (towards decreasing values) for positive
+ *     spacings: the mesh of a density blob has positive signed volume.  Degenerate triangles (a corner value exactly
+ *     iso) are kept.
+ *   - ORDER (part of the contract; two runs give byte-identical buffers): vertices by owning grid point a (linear index),
+ *     then axis x, y, z; triangles by cell (linear index of its min corner), then table order.
+ *
+ *   mi3d_mc_workspace  bytes of device scratch for a volume of this size (0 for sizes out of range); host only
+ *   mi3d_mc_case       host only: copies table row `case_index` (cube edges, three per triangle, -1 terminated) into
+ *                      edges_host[16] and returns its triangle count; -1 for case_index > 255 or a NULL pointer
+ *   mi3d_mc_count      per-workgroup vertex and triangle counts -> workspace
+ *   mi3d_mc_scan       their exclusive scan; counts (device uint64[4], 8-byte aligned) = {vertices, triangles, 0, 0}.
+ *                      The caller reads counts once to size the outputs - the only host read of an extraction.
+ *   mi3d_mc_emit       vertices float[nv_cap][3], triangles int32[nt_cap][3].  Nothing is written past the caps (vertex
+ *                      ids are int32: at most 2^31 - 1 vertices); what could not be placed is COUNTED in counts[2]
+ *                      (vertices + triangles) instead of being dropped silently, the convention ctl[8] of Part 1b set.
+ * count, scan and emit of one extraction go to the same stream, in this order, with the same vol / sizes / iso / ws. */
+size_t mi3d_mc_workspace(uint32_t Rx, uint32_t Ry, uint32_t Rz);
+int mi3d_mc_case(uint32_t case_index, int8_t *edges_host);
+int mi3d_mc_count(const float *vol, uint32_t Rx, uint32_t Ry, uint32_t Rz, float iso, void *ws, size_t ws_bytes,
+                  unsigned long long *counts, void *stream);
+int mi3d_mc_scan(uint32_t Rx, uint32_t Ry, uint32_t Rz, void *ws, size_t ws_bytes, unsigned long long *counts,
+                 void *stream);
+int mi3d_mc_emit(const float *vol, uint32_t Rx, uint32_t Ry, uint32_t Rz, float iso, const float *origin_host,
+                 const float *spacing_host, void *ws, size_t ws_bytes, unsigned long long *counts, float *vertices,
+                 unsigned long long nv_cap, int32_t *triangles, unsigned long long nt_cap, void *stream);
 
 #ifdef __cplusplus
 }

@@ -71,6 +71,16 @@ _SIGNATURES = {
     "mi3d_points_rasterize": [vp, u32, u32, u32, f32, u32, vp, C.c_size_t, vp, vp, vp, vp],
     "mi3d_points_composite_forward": [vp, vp, u32, u32, u32, vp, u32, C.c_double, vp, vp],
     "mi3d_points_composite_backward": [vp, vp, u32, u32, u32, vp, u32, C.c_double, vp, vp],
+    # Part 8 ------------------------------------------------------------------------------------------
+    "mi3d_mc_count": [vp, u32, u32, u32, f32, vp, C.c_size_t, vp, vp],
+    "mi3d_mc_scan": [u32, u32, u32, vp, C.c_size_t, vp, vp],
+    "mi3d_mc_emit": [vp, u32, u32, u32, f32, vp, vp, vp, C.c_size_t, vp, vp, C.c_uint64, vp, C.c_uint64, vp],
+}
+
+# host-only queries whose return value is not a hipError_t: (argtypes, restype), bound in lib() like the block below
+_LATE_SIGNATURES = {
+    "mi3d_mc_workspace": ([u32, u32, u32], C.c_size_t),
+    "mi3d_mc_case": ([u32, C.POINTER(C.c_int8)], C.c_int),
 }
 
 
@@ -98,6 +108,9 @@ def lib():
         _lib.mi3d_grid_scatter_binned_workspace.argtypes = [u32, u32, f32, f32, u32, u32, f32, u32]
         _lib.mi3d_points_rasterize_workspace.restype = C.c_size_t
         _lib.mi3d_points_rasterize_workspace.argtypes = [u32, u32, u32, f32]
+        for name, (args, res) in _LATE_SIGNATURES.items():
+            fn = getattr(_lib, name)
+            fn.argtypes, fn.restype = args, res
     return _lib
 
 

@@ -7,7 +7,6 @@ What differs is how the work is issued, not what is computed:
     (`self.field_stencil`) instead of 13 separate `self(...)` / `self.normal(...)` passes;
   * RNG draws happen in the reference's order (light direction, march noise, smoothness jitter) so a
     seeded run sees the same random numbers.
-`export_mesh` (marching cubes + xatlas + nvdiffrast, renderer.py:142-330) is outside the hot path and not provided.
 """
 import math
 import weakref
@@ -117,12 +116,16 @@ class NeRFRenderer(nn.Module):
         self.mean_count = 0
         self.local_step = 0
 
+    @torch.no_grad()
     def export_mesh(self, path, resolution=None, S=128):
-        """renderer.py:157-330 (marching cubes + xatlas + nvdiffrast texture baking, reached only through main.py's
-        `--save_mesh`): out of this path's scope (mesh export) - said loudly instead of by AttributeError."""
-        raise NotImplementedError("export_mesh (--save_mesh) is outside the SDS training hot path this package covers; load "
-                                  "the checkpoint into the reference's own class (nerf.network_tcnn.NeRFNetwork_reference "
-                                  "under mi3d.autopatch: same state_dict keys) to export a mesh")
+        """renderer.py:157-191 + the file writing of :300-328, reached through main.py's `--save_mesh`: sigma on the
+        `resolution`^3 lattice of [-1, 1]^3 (default grid_size), marching cubes at min(mean_density, density_thresh)
+        (density_thresh without cuda_ray) on the GPU (mi3d.mesh), `<path>/mesh.obj` + `mesh.mtl`.  Where the reference
+        bakes a UV atlas (xatlas + nvdiffrast, :193-299) this writes the albedo field per VERTEX (`v x y z r g b`); no
+        texture image.  Returns (vertices [nv,3] float32, triangles [nt,3] int32, albedo [nv,3] float32) as NumPy arrays
+        (the reference returns nothing).  `S` is accepted and ignored.  A CPU model raises Mi3dError."""
+        from . import mesh
+        return mesh.export(self, path, resolution, S)
 
     # --- pure-PyTorch sampler path (BASELINE config 1) --------------------------------------------
     def run(self, rays_o, rays_d, ref_bg=None, num_steps=128, upsample_steps=128, light_d=None, ambient_ratio=1.0,
