@@ -34,7 +34,7 @@ extern "C" {
 
 /* the ABI version: 5 (4 = 3 + the compact-round inference loop of Part 1b; 5: that loop's ctl block is int32[16] with
  * the dropped-row count in [8], and its plan never passes max_steps; every other entry point is unchanged).  Part 8
- * (marching cubes) was added under 5: new symbols only, nothing existing changed. */
+ * (marching cubes) and Part 9 (texture baking) were added under 5: new symbols only, nothing existing changed. */
 int mi3d_abi_version(void);
 const char *mi3d_last_error_string(int err);
 
@@ -425,6 +425,62 @@ int mi3d_mc_scan(uint32_t Rx, uint32_t Ry, uint32_t Rz, void *ws, size_t ws_byte
 int mi3d_mc_emit(const float *vol, uint32_t Rx, uint32_t Ry, uint32_t Rz, float iso, const float *origin_host,
                  const float *spacing_host, void *ws, size_t ws_bytes, unsigned long long *counts, float *vertices,
                  unsigned long long nv_cap, int32_t *triangles, unsigned long long nt_cap, void *stream);
+
+/* ------------------------------------------------------------------ Part 9: texture baking (mesh export) */
+
+/* An indexed triangle mesh (Part 8's output) -> a UV atlas, the surface point of every texel, and the 8-bit RGB image of
+ * the albedo evaluated there: what xatlas (unwrap), nvdiffrast (UV-space rasterisation) and the kd-tree inpainting do for
+ * the reference's export_mesh (nerf/renderer.py:193-299).  None of them exists for this hardware; the layout below is this
+ * project's own contract - PARITY UNPINNED, the standing of Part 8.  Added under ABI version 5: new symbols only.
+ *
+ * Marching-cubes triangles are all at most one grid cell large, so every triangle gets the SAME right-triangle patch of
+ * texels and two patches share a rectangular cell (the trivial per-triangle parametrisation): O(1) per triangle,
+ * deterministic, and it needs no inpainting - the gutter texels are evaluated at the affinely extrapolated surface point.
+ *
+ *   - TEXTURE: T x T texels, T in [64, 16384]; image row 0 is the TOP row; texel (X, Y) = column X of row Y.
+ *   - CELL: c + 1 texels wide, c high, c >= 4.  Cells tile the image from the top-left, row by row: cols = T / (c + 1),
+ *     rows = T / c (integer divisions).  Triangle i lies in cell q = i / 2, at cell column q % cols and cell row q / cols,
+ *     as half i & 1.  c is the LARGEST value with 2 * cols * rows >= nt (the product is non-increasing in c);
+ *     mi3d_atlas_cell returns it, 0 if T is out of range or even c = 4 does not hold nt triangles.
+ *   - OWNERSHIP: local texel (x, y) of a cell, 0 <= x <= c, 0 <= y <= c - 1.  Half 0 owns x <= c - 1 and x + y <= c - 1,
+ *     half 1 the rest: c (c + 1) / 2 texels each; half 1 is half 0 under the point reflection (x, y) -> (c - x, c - 1 - y),
+ *     which keeps the winding.  Texels outside every cell (right and bottom margins), in cells past the last triangle and
+ *     in the missing second half of an odd last triangle are owned by no one: owner -1, colour 0.
+ *   - UV CORNERS: vertices 0, 1, 2 of half 0 sit at the CENTRES of local texels (0, 0), (c - 2, 0), (0, c - 2); half 1 at
+ *     their reflections.  Global texel (X, Y) -> vt = ((X + 0.5) / T, 1 - (Y + 0.5) / T) in binary32, each operation
+ *     rounded once (the reference's `1 - v` flip).  Three vt per triangle, unshared: vt index 3 i + k.  Every texel that
+ *     bilinear filtering touches with non-zero weight at a point of the UV triangle lies in the triangle's own half.
+ *   - TEXEL -> SURFACE POINT: (u, v) = the local coordinates, reflected for half 1; s = u / (c - 2), t = v / (c - 2);
+ *     p = (A + s * (B - A)) + t * (C - A) per coordinate with A, B, C the triangle's vertices 0, 1, 2 - every operation a
+ *     separately rounded binary32 one in this order, no fused multiply-add - then clamped to [-1, 1] (the extraction's
+ *     box).  s, t and s + t pass 1 by up to one texel in the gutter: the intended extrapolation.
+ *   - SUPERSAMPLING: ssaa in {1, 2, 4}.  Sub-sample (i, j) of a texel uses u + ((i + 0.5) / ssaa - 0.5) and likewise v with
+ *     j (exact in binary32) in place of u and v; the texel's ssaa^2 samples are stored consecutively, index j * ssaa + i.
+ *     The texel's colour is the binary32 sum of its samples' albedos in that order, times 1 / ssaa^2.
+ *   - QUANTISATION: min(255, floor(a * 255)) in binary32 (the reference's `(feats * 255).astype(np.uint8)`); a negative
+ *     or NaN value gives 0.
+ *
+ *   mi3d_atlas_cell       host only: c for nt triangles in a T x T texture, or 0
+ *   mi3d_atlas_uv         vt float[3 nt][2]
+ *   mi3d_atlas_positions  the band of image rows [row0, row0 + rows), rows >= 1, row0 + rows <= T:
+ *                         xyz float[rows * T * ssaa^2][3] (zeros for a texel no one owns) and, unless NULL,
+ *                         owner int32[rows * T] (triangle index or -1).  vertices float[nv][3], triangles int32[nt][3].
+ *                         A triangle with an index outside [0, nv) is never dereferenced: it owns nothing and is COUNTED
+ *                         in *bad (device uint64, 8-byte aligned, zeroed by the caller, added to by the band that holds
+ *                         the texel of its vertex 0) - the convention counts[2] of Part 8 set.
+ *   mi3d_texture_pack     albedo float[rows * T * ssaa^2][3] in the sample order above, owner int32[rows * T] ->
+ *                         image uint8[rows][T][3] (RGB, 4-byte aligned): the mean, the quantisation, 0 where owner < 0.
+ *                         Written as whole 32-bit words, four texels to three words; only the last one to three texels
+ *                         of a band whose texel count is no multiple of four are written as bytes.
+ * nt in [1, 2^31 - 1] and a (nt, T) pair with c = 0 are refused (hipErrorInvalidValue), as is every NULL pointer other
+ * than `owner` of mi3d_atlas_positions. */
+uint32_t mi3d_atlas_cell(unsigned long long nt, uint32_t T);
+int mi3d_atlas_uv(unsigned long long nt, uint32_t T, float *vt, void *stream);
+int mi3d_atlas_positions(const float *vertices, unsigned long long nv, const int32_t *triangles, unsigned long long nt,
+                         uint32_t T, uint32_t ssaa, uint32_t row0, uint32_t rows, float *xyz, int32_t *owner,
+                         unsigned long long *bad, void *stream);
+int mi3d_texture_pack(const float *albedo, const int32_t *owner, uint32_t T, uint32_t ssaa, uint32_t rows, uint8_t *image,
+                      void *stream);
 
 #ifdef __cplusplus
 }

@@ -75,12 +75,17 @@ _SIGNATURES = {
     "mi3d_mc_count": [vp, u32, u32, u32, f32, vp, C.c_size_t, vp, vp],
     "mi3d_mc_scan": [u32, u32, u32, vp, C.c_size_t, vp, vp],
     "mi3d_mc_emit": [vp, u32, u32, u32, f32, vp, vp, vp, C.c_size_t, vp, vp, C.c_uint64, vp, C.c_uint64, vp],
+    # Part 9 ------------------------------------------------------------------------------------------
+    "mi3d_atlas_uv": [C.c_uint64, u32, vp, vp],
+    "mi3d_atlas_positions": [vp, C.c_uint64, vp, C.c_uint64, u32, u32, u32, u32, vp, vp, vp, vp],
+    "mi3d_texture_pack": [vp, vp, u32, u32, u32, vp, vp],
 }
 
 # host-only queries whose return value is not a hipError_t: (argtypes, restype), bound in lib() like the block below
 _LATE_SIGNATURES = {
     "mi3d_mc_workspace": ([u32, u32, u32], C.c_size_t),
     "mi3d_mc_case": ([u32, C.POINTER(C.c_int8)], C.c_int),
+    "mi3d_atlas_cell": ([C.c_uint64, u32], u32),
 }
 
 

@@ -1,19 +1,25 @@
-"""Mesh export: the trained field -> `mesh.obj` / `mesh.mtl` (the reference's `NeRFRenderer.export_mesh`,
-nerf/renderer.py:157-330 of the reference tree, without its UV atlas).
+"""Mesh export: the trained field -> `mesh.obj` / `mesh.mtl` and, on request, `albedo.png` (the reference's
+`NeRFRenderer.export_mesh`, nerf/renderer.py:157-330 of the reference tree).
 
   extract_volume   sigma on the reference's R^3 lattice of [-1, 1]^3, evaluated by the field kernels in chunks, kept on
                    the device
   marching_cubes   the kernels of csrc/mesh.hip (include/mi3d.h Part 8 states the conventions): device volume in,
                    welded indexed mesh out; the host reads the two counts once to size the outputs (and
                    the overflow counter once after emit)
-  export           volume -> surface -> per-vertex albedo -> files; what `NeRFRenderer.export_mesh` calls
-  write_obj        vertex-coloured OBJ (`v x y z r g b`) + the reference's `mat0` material, no texture
+  bake_texture     the kernels of csrc/texture.hip (include/mi3d.h Part 9): a texel patch per triangle, the field's albedo
+                   at every texel's surface point, packed to 8-bit RGB on the device
+  export           volume -> surface -> per-vertex albedo (-> texture) -> files; what `NeRFRenderer.export_mesh` calls
+  write_obj        vertex-coloured OBJ (`v x y z r g b`) + the reference's `mat0` material; with UVs `v` / `vt` /
+                   `f v/vt` and `map_Kd`
+  write_png        8-bit RGB PNG with the standard library alone
 
-`mcubes` (the reference's extractor) is on no machine this project builds on: vertex positions, ordering and the case
-table are this project's contract, not a pinned copy of PyMCubes.
+`mcubes`, `xatlas` and `nvdiffrast` (the reference's extractor, unwrapper and rasteriser) are on no machine this project
+builds on: vertex positions, ordering, the case table and the atlas are this project's contract, not pinned copies.
 """
 import ctypes as C
 import os
+import struct
+import zlib
 
 import numpy as np
 import torch
@@ -97,6 +103,80 @@ def vertex_albedo(model, vertices):
     return out
 
 
+MIN_TEXTURE, MAX_TEXTURE = 64, 16384
+SSAA = (1, 2, 4)
+
+
+def atlas_cell(nt, texture_size):
+    """The cell size c of include/mi3d.h Part 9 for `nt` triangles in a texture_size^2 atlas; 0 if they do not fit."""
+    nt, T = int(nt), int(texture_size)
+    if nt < 0 or not 0 <= T < 2 ** 32:
+        return 0
+    return int(_lib.lib().mi3d_atlas_cell(nt, T))
+
+
+def _check_texture(texture_size, ssaa):
+    if isinstance(texture_size, bool) or int(texture_size) != texture_size:
+        raise Mi3dError(f"texture_size must be an integer (got {texture_size!r})")
+    if not MIN_TEXTURE <= int(texture_size) <= MAX_TEXTURE:
+        raise Mi3dError(f"texture_size must lie in [{MIN_TEXTURE}, {MAX_TEXTURE}] (got {texture_size})")
+    if ssaa not in SSAA:
+        raise Mi3dError(f"ssaa must be one of {SSAA} (got {ssaa!r})")
+    return int(texture_size), int(ssaa)
+
+
+def _fitting_cell(nt, T):
+    c = atlas_cell(nt, T)
+    if c == 0:
+        fit = next((t for t in (1 << k for k in range(6, 15)) if atlas_cell(nt, t) > 0), None)
+        hint = f"the smallest power of two that fits is {fit}" if fit else f"no size up to {MAX_TEXTURE} fits"
+        raise Mi3dError(f"{nt} triangles do not fit a {T} x {T} texture atlas: {hint}")
+    return c
+
+
+def bake_texture(model, vertices, triangles, texture_size, ssaa=1):
+    """The albedo of `model` baked into the per-triangle atlas of include/mi3d.h Part 9.  vertices float32 [nv, 3] and
+    triangles int32 [nt, 3] on the GPU (what marching_cubes returns).  Returns (image uint8 [T, T, 3], vt float32
+    [3 nt, 2], owner int32 [T, T]) on the same device; image row 0 is the top row, vt of triangle i are rows 3 i .. 3 i + 2.
+    The texels are evaluated in bands of image rows of at most CHUNK points; bands below the last owned texel are not."""
+    T, ssaa = _check_texture(texture_size, ssaa)
+    vertices = _lib.dev_f32(vertices, "vertices", 3)
+    if not isinstance(triangles, torch.Tensor):
+        raise TypeError("triangles must be a torch.Tensor")
+    triangles = _lib.dev_typed(triangles, "triangles", torch.int32)
+    if vertices.dim() != 2 or triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.device != vertices.device:
+        raise Mi3dError(f"vertices {tuple(vertices.shape)} and triangles {tuple(triangles.shape)} must be [nv, 3] and "
+                        f"[nt, 3] on one device")
+    nv, nt = int(vertices.shape[0]), int(triangles.shape[0])
+    if nv == 0 or nt == 0:
+        raise Mi3dError("bake_texture needs a mesh (got no vertices or no triangles)")
+    c = _fitting_cell(nt, T)
+    dev, ss2 = vertices.device, ssaa * ssaa
+    vt = torch.empty(3 * nt, 2, dtype=torch.float32, device=dev)
+    image = torch.zeros(T, T, 3, dtype=torch.uint8, device=dev)
+    owner = torch.full((T, T), -1, dtype=torch.int32, device=dev)
+    bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    _lib.launch("mi3d_atlas_uv", vt, nt, T, _lib.ptr(vt))
+    cols = T // (c + 1)
+    used = -(-((nt + 1) // 2) // cols) * c              # image rows down to the last cell row that holds a triangle
+    band = max(4, CHUNK // (T * ss2) // 4 * 4)          # a multiple of 4 rows: every band starts on a 32-bit word
+    with torch.no_grad():
+        for row0 in range(0, used, band):
+            rows = min(band, used - row0)
+            xyz = torch.empty(rows * T * ss2, 3, dtype=torch.float32, device=dev)
+            _lib.launch("mi3d_atlas_positions", xyz, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, T, ssaa, row0, rows,
+                        _lib.ptr(xyz), _lib.ptr(owner[row0]), _lib.ptr(bad))
+            albedo = model.density(xyz)["albedo"].float().contiguous()
+            if albedo.shape != xyz.shape:
+                raise Mi3dError(f"model.density returned albedo {tuple(albedo.shape)} for points {tuple(xyz.shape)}")
+            _lib.launch("mi3d_texture_pack", albedo, _lib.ptr(albedo), _lib.ptr(owner[row0]), T, ssaa, rows,
+                        _lib.ptr(image[row0]))
+    lost = int(bad)                                     # the one host read of a bake
+    if lost != 0:
+        raise Mi3dError(f"{lost} of the {nt} triangles hold a vertex index outside [0, {nv})")
+    return image, vt, owner
+
+
 MTL = ("newmtl mat0 \n"
        "Ka 1.000000 1.000000 1.000000 \n"
        "Kd 1.000000 1.000000 1.000000 \n"
@@ -114,34 +194,79 @@ def _write_rows(fp, fmt, rows, block=1 << 16):
         fp.write((fmt * part.shape[0]) % tuple(part.ravel().tolist()))
 
 
-def write_obj(path, vertices, triangles, colors, name="mesh"):
+def write_png(path, image):
+    """`image` uint8 [H, W, 3] (row 0 = top) as an 8-bit RGB PNG, non-interlaced, filter 0 on every row; zlib, struct and
+    the CRC of the standard library - no imaging package."""
+    image = np.ascontiguousarray(image)
+    if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or 0 in image.shape:
+        raise ValueError(f"image must be uint8 [H, W, 3] (got {image.dtype} {image.shape})")
+    H, W = image.shape[:2]
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data))
+
+    rows_per_block = max(1, (1 << 24) // (3 * W + 1))
+    z = zlib.compressobj(6)
+    with open(path, "wb") as fp:
+        fp.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0)))
+        for s in range(0, H, rows_per_block):
+            part = image[s:s + rows_per_block].reshape(-1, 3 * W)
+            raw = np.concatenate([np.zeros((part.shape[0], 1), np.uint8), part], 1)     # the filter byte of every row
+            data = z.compress(raw.tobytes())
+            if data:
+                fp.write(chunk(b"IDAT", data))
+        fp.write(chunk(b"IDAT", z.flush()) + chunk(b"IEND", b""))
+    return path
+
+
+def write_obj(path, vertices, triangles, colors, name="mesh", uvs=None, uv_faces=None, texture=None):
     """`<path>/<name>.obj` (lines `v x y z r g b`, `f a b c` one-based) and `<path>/<name>.mtl`.  NumPy arrays:
-    vertices [nv, 3], triangles [nt, 3] (zero-based), colors [nv, 3] in [0, 1].  Returns the two file names."""
+    vertices [nv, 3], triangles [nt, 3] (zero-based), colors [nv, 3] in [0, 1].  Returns the two file names.
+    With `uvs` [nuv, 2], `uv_faces` [nt, 3] (zero-based rows of uvs) and `texture` (an image file name, as the MTL is to
+    cite it) - all three or none - the lines are `v x y z`, `vt u v`, `f a/ta b/tb c/tc` instead and the MTL ends with
+    `map_Kd <texture>`; `colors` is not written then."""
     vertices, colors = np.asarray(vertices, np.float32), np.asarray(colors, np.float32)
     triangles = np.asarray(triangles)
     if vertices.ndim != 2 or vertices.shape[1] != 3 or colors.shape != vertices.shape:
         raise ValueError(f"vertices {vertices.shape} and colors {colors.shape} must both be [nv, 3]")
     if triangles.ndim != 2 or triangles.shape[1] != 3:
         raise ValueError(f"triangles must be [nt, 3] (got {triangles.shape})")
+    textured = uvs is not None or uv_faces is not None or texture is not None
+    if textured:
+        if uvs is None or uv_faces is None or texture is None:
+            raise ValueError("uvs, uv_faces and texture go together")
+        uvs, uv_faces = np.asarray(uvs, np.float32), np.asarray(uv_faces)
+        if uvs.ndim != 2 or uvs.shape[1] != 2 or uv_faces.shape != triangles.shape:
+            raise ValueError(f"uvs must be [nuv, 2] and uv_faces [nt, 3] (got {uvs.shape} and {uv_faces.shape})")
     os.makedirs(path, exist_ok=True)
     obj, mtl = os.path.join(path, f"{name}.obj"), os.path.join(path, f"{name}.mtl")
     with open(obj, "w") as fp:
         fp.write(f"mtllib {name}.mtl\n")
         # %.9g round-trips binary32; colours need no more than six decimals
-        _write_rows(fp, "v %.9g %.9g %.9g %.6f %.6f %.6f\n", np.concatenate([vertices, colors], 1).astype(np.float64))
+        if textured:
+            _write_rows(fp, "v %.9g %.9g %.9g\n", vertices.astype(np.float64))
+            _write_rows(fp, "vt %.9g %.9g\n", uvs.astype(np.float64))
+        else:
+            _write_rows(fp, "v %.9g %.9g %.9g %.6f %.6f %.6f\n", np.concatenate([vertices, colors], 1).astype(np.float64))
         fp.write("usemtl mat0\n")
-        _write_rows(fp, "f %d %d %d\n", triangles.astype(np.int64) + 1)
+        if textured:
+            both = np.stack([triangles.astype(np.int64) + 1, uv_faces.astype(np.int64) + 1], -1).reshape(-1, 6)
+            _write_rows(fp, "f %d/%d %d/%d %d/%d\n", both)
+        else:
+            _write_rows(fp, "f %d %d %d\n", triangles.astype(np.int64) + 1)
     with open(mtl, "w") as fp:
-        fp.write(MTL)
+        fp.write(MTL + (f"map_Kd {texture}\n" if textured else ""))
     return obj, mtl
 
 
-def export(model, path, resolution=None, S=128):
+def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1):
     """What NeRFRenderer.export_mesh does (see there).  `S` only sizes the reference's chunks and is ignored."""
     del S
     if model.aabb_train.device.type != "cuda":
         raise Mi3dError(f"export_mesh needs the model on the GPU (it is on {model.aabb_train.device}): the field and "
                         f"the marching-cubes kernels have no CPU path")
+    if texture_size is not None:
+        texture_size, ssaa = _check_texture(texture_size, ssaa)
     R = model.grid_size if resolution is None else int(resolution)
     # renderer.py:159-165
     thresh = float(min(model.mean_density, model.density_thresh) if model.cuda_ray else model.density_thresh)
@@ -153,7 +278,16 @@ def export(model, path, resolution=None, S=128):
             lo, hi = torch.nan_to_num(vol, nan=0.0).min().item(), torch.nan_to_num(vol, nan=0.0).max().item()
             raise Mi3dError(f"export_mesh: no surface at density threshold {thresh:g}: the {R}^3 volume spans "
                             f"[{lo:g}, {hi:g}]")
+        if texture_size is not None:
+            _fitting_cell(triangles.shape[0], texture_size)     # refuse before the field is evaluated anywhere
         albedo = vertex_albedo(model, vertices)
+        if texture_size is not None:
+            image, vt, _ = bake_texture(model, vertices, triangles, texture_size, ssaa)
     v, f, c = vertices.cpu().numpy(), triangles.cpu().numpy(), albedo.cpu().numpy()
-    write_obj(path, v, f, c)
-    return v, f, c
+    if texture_size is None:
+        write_obj(path, v, f, c)
+        return v, f, c
+    vt, image = vt.cpu().numpy(), image.cpu().numpy()
+    write_obj(path, v, f, c, uvs=vt, uv_faces=np.arange(3 * len(f), dtype=np.int64).reshape(-1, 3), texture="albedo.png")
+    write_png(os.path.join(path, "albedo.png"), image)
+    return v, f, c, vt, image

@@ -117,15 +117,20 @@ class NeRFRenderer(nn.Module):
         self.local_step = 0
 
     @torch.no_grad()
-    def export_mesh(self, path, resolution=None, S=128):
+    def export_mesh(self, path, resolution=None, S=128, texture_size=None, ssaa=1):
         """renderer.py:157-191 + the file writing of :300-328, reached through main.py's `--save_mesh`: sigma on the
         `resolution`^3 lattice of [-1, 1]^3 (default grid_size), marching cubes at min(mean_density, density_thresh)
-        (density_thresh without cuda_ray) on the GPU (mi3d.mesh), `<path>/mesh.obj` + `mesh.mtl`.  Where the reference
-        bakes a UV atlas (xatlas + nvdiffrast, :193-299) this writes the albedo field per VERTEX (`v x y z r g b`); no
-        texture image.  Returns (vertices [nv,3] float32, triangles [nt,3] int32, albedo [nv,3] float32) as NumPy arrays
-        (the reference returns nothing).  `S` is accepted and ignored.  A CPU model raises Mi3dError."""
+        (density_thresh without cuda_ray) on the GPU (mi3d.mesh), `<path>/mesh.obj` + `mesh.mtl`.  By default
+        (`texture_size=None`) this writes the albedo field per VERTEX (`v x y z r g b`) and no texture image, and returns
+        (vertices [nv,3] float32, triangles [nt,3] int32, albedo [nv,3] float32) as NumPy arrays (the reference returns
+        nothing).  With an integer `texture_size` T in [64, 16384] it bakes what the reference's xatlas + nvdiffrast pass
+        (:193-299) bakes, in this project's own atlas (include/mi3d.h Part 9; `ssaa` in {1, 2, 4} samples per texel and
+        axis): `mesh.obj` with `v` / `vt` / `f v/vt`, `mesh.mtl` with `map_Kd albedo.png`, and the T x T `albedo.png`;
+        it then returns (vertices, triangles, albedo, vt [3 nt, 2] float32, image [T, T, 3] uint8).  A mesh too large
+        for T raises Mi3dError naming a size that fits, before anything is written.  `S` is accepted and ignored.  A CPU
+        model raises Mi3dError."""
         from . import mesh
-        return mesh.export(self, path, resolution, S)
+        return mesh.export(self, path, resolution, S, texture_size=texture_size, ssaa=ssaa)
 
     # --- pure-PyTorch sampler path (BASELINE config 1) --------------------------------------------
     def run(self, rays_o, rays_d, ref_bg=None, num_steps=128, upsample_steps=128, light_d=None, ambient_ratio=1.0,
