@@ -34,7 +34,8 @@ extern "C" {
 
 /* the ABI version: 5 (4 = 3 + the compact-round inference loop of Part 1b; 5: that loop's ctl block is int32[16] with
  * the dropped-row count in [8], and its plan never passes max_steps; every other entry point is unchanged).  Part 8
- * (marching cubes) and Part 9 (texture baking) were added under 5: new symbols only, nothing existing changed. */
+ * (marching cubes), Part 9 (texture baking) and Part 10 (GroupNorm) were added under 5: new symbols only, nothing existing
+ * changed. */
 int mi3d_abi_version(void);
 const char *mi3d_last_error_string(int err);
 
@@ -481,6 +482,43 @@ int mi3d_atlas_positions(const float *vertices, unsigned long long nv, const int
                          unsigned long long *bad, void *stream);
 int mi3d_texture_pack(const float *albedo, const int32_t *owner, uint32_t T, uint32_t ssaa, uint32_t rows, uint8_t *image,
                       void *stream);
+
+/* ------------------------------------------------------------------ Part 10: GroupNorm (+ SiLU) of the diffusion half */
+
+/* group_norm, optionally followed by SiLU, on binary16 tensors with fp32 arithmetic in registers: what the guidance
+ * networks (mi3d/sd_standin.py) compute around every convolution, where stock PyTorch under autocast runs a chain of
+ * fp32 kernels (cast, statistics, multiply-add, silu, cast back).  Added under ABI version 5: new symbols only.
+ *
+ *   - LAYOUT: x, y, dy, dx are binary16 [B][C][HW], contiguous; G divides C; group g of a sample is its channels
+ *     [g C/G, (g + 1) C/G), a contiguous span of C/G * HW elements, at most 2^24.  weight, bias float[C];
+ *     mean, rstd float[B][G].
+ *   - CHUNKS: every (sample, channel) row of HW elements is cut into Sc = mi3d_groupnorm_chunks(HW) chunks; one workgroup
+ *     owns one (row, chunk), index (b * C + c) * Sc + k.  The caller allocates the per-chunk workspaces:
+ *     ws float[B * C * Sc][3] = (count, mean, M2) and partial float[B * C * Sc][2] = (sum dz, sum dz * x).
+ *   - FORWARD, two launches: mi3d_groupnorm_stats fills ws (Chan's merge throughout, never sum-of-squares minus
+ *     square-of-sum); mi3d_groupnorm_act_forward merges each group's triples itself, stores mean and
+ *     rstd = 1 / sqrt(M2 / n + eps), and writes y = act(x a_c + b_c), a_c = rstd weight_c, b_c = bias_c - mean a_c,
+ *     rounded once to binary16.  act 0 = identity, 1 = silu(z) = z / (1 + exp(-z)).
+ *   - BACKWARD, input gradient only, two launches: with z recomputed and dz = dy act'(z),
+ *     mi3d_groupnorm_act_backward_sums fills partial; mi3d_groupnorm_act_backward merges each group's sums into
+ *     ds = sum_c weight_c sum dz x, db = sum_c weight_c sum dz and writes dx = rstd weight_c dz + c2 x + c3 with
+ *     c2 = (db mean - ds) rstd^3 / n, c3 = -c2 mean - db rstd / n (n = C/G * HW): ATen's formula.
+ *   - No atomics, fixed reduction orders: bit-reproducible.  No entry point synchronises, allocates or queries the device,
+ *     so all of them can be captured into a hipGraph.  16-byte vector access where the pointers are 16-byte aligned, with
+ *     a scalar head and tail per chunk; any alignment of at least 2 bytes is accepted.
+ * A zero dimension, G not dividing C, a group of more than 2^24 elements, act outside {0, 1} and every NULL pointer are
+ * refused (hipErrorInvalidValue). */
+uint32_t mi3d_groupnorm_chunks(uint32_t HW);
+int mi3d_groupnorm_stats(const void *x, uint32_t B, uint32_t C, uint32_t HW, uint32_t G, float *ws, void *stream);
+int mi3d_groupnorm_act_forward(const void *x, const float *ws, const float *weight, const float *bias, uint32_t B,
+                               uint32_t C, uint32_t HW, uint32_t G, float eps, int act, void *y, float *mean, float *rstd,
+                               void *stream);
+int mi3d_groupnorm_act_backward_sums(const void *x, const void *dy, const float *mean, const float *rstd,
+                                     const float *weight, const float *bias, uint32_t B, uint32_t C, uint32_t HW,
+                                     uint32_t G, int act, float *partial, void *stream);
+int mi3d_groupnorm_act_backward(const void *x, const void *dy, const float *mean, const float *rstd, const float *weight,
+                                const float *bias, const float *partial, uint32_t B, uint32_t C, uint32_t HW, uint32_t G,
+                                int act, void *dx, void *stream);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,7 @@ UNITS = [
     ("raster.hip", ["-ffp-contract=off"]),
     ("mesh.hip", ["-ffp-contract=off"]),
     ("texture.hip", ["-ffp-contract=off"]),
+    ("groupnorm.hip", []),
 ]
 HEADERS = ["mi3d_common.h", "mi3d_grid.h", "mi3d_dev.h", "lds_transpose.h", "mi3d_mc_tables.h", os.path.join("..", "..", "include", "mi3d.h")]
 

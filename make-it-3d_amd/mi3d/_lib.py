@@ -79,6 +79,11 @@ _SIGNATURES = {
     "mi3d_atlas_uv": [C.c_uint64, u32, vp, vp],
     "mi3d_atlas_positions": [vp, C.c_uint64, vp, C.c_uint64, u32, u32, u32, u32, vp, vp, vp, vp],
     "mi3d_texture_pack": [vp, vp, u32, u32, u32, vp, vp],
+    # Part 10 -----------------------------------------------------------------------------------------
+    "mi3d_groupnorm_stats": [vp, u32, u32, u32, u32, vp, vp],
+    "mi3d_groupnorm_act_forward": [vp, vp, vp, vp, u32, u32, u32, u32, f32, i32, vp, vp, vp, vp],
+    "mi3d_groupnorm_act_backward_sums": [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, i32, vp, vp],
+    "mi3d_groupnorm_act_backward": [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, i32, vp, vp],
 }
 
 # host-only queries whose return value is not a hipError_t: (argtypes, restype), bound in lib() like the block below
@@ -86,6 +91,7 @@ _LATE_SIGNATURES = {
     "mi3d_mc_workspace": ([u32, u32, u32], C.c_size_t),
     "mi3d_mc_case": ([u32, C.POINTER(C.c_int8)], C.c_int),
     "mi3d_atlas_cell": ([C.c_uint64, u32], u32),
+    "mi3d_groupnorm_chunks": ([u32], u32),
 }
 
 

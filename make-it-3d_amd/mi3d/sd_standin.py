@@ -39,9 +39,22 @@ import torch.nn.functional as F
 #                   ~300 + ~600 launches per step replayed instead of issued.  Fixed shape ([1, 3, 512, 512], what
 #                   sd.py:124 always feeds it), frozen weights, autocast(float16) only; anything else runs eagerly.
 #                   Measured: 32.10 -> 32.05 ms per guidance call (profiles/sd_knobs_r04_vae_graph.json): nothing - OFF.
+#   GN_FUSED        the chain around every GroupNorm whose input is binary16 - x.float(), the statistics, the multiply-add,
+#                   F.silu, autocast's cast back for the conv: 32 B per element forward, about 48 B backward, all in
+#                   stock fp32 kernels - as two HIP kernels per direction (csrc/groupnorm.hip through mi3d/norm_ops.py):
+#                   binary16 in and out, fp32 in registers, 6 B per element forward and 10 B backward, no fp32 activation
+#                   saved.  The output is the binary16 rounding of the fp32 result, which is what autocast feeds the conv
+#                   or Linear behind every GroupNorm of this file.  Takes precedence over GN_SPLIT_STATS where it applies
+#                   (GPU, contiguous binary16 input, frozen affine); everything else runs the routes above, unchanged.
+#                   Measured (tools/sd_knobs.py, profiles/sd_knobs_gn_fused.json; off / on / off / on in one process):
+#                   30.5 / 22.2 / 30.4 / 22.1 ms per guidance call (VAE encode 9.5 -> 5.3, U-Net 13.5 -> 11.7, backward
+#                   7.5 -> 5.2); the whole step 98.8-100.4 -> 90.7-92.3 ms and 1.0 GiB less peak memory
+#                   (profiles/bench_gn_fused_ab.json) - ON.  With VAE_GRAPH on top: 22.0, still nothing.  With GN_FUSED and
+#                   GN_SPLIT_STATS both off the call takes 23.8 ms on the current PyTorch-ROCm.
 GN_SPLIT_STATS = True
 VAE_HALF_CACHE = False
 VAE_GRAPH = False
+GN_FUSED = True
 
 
 class _SplitStatsGroupNorm(torch.autograd.Function):
@@ -78,7 +91,32 @@ class _SplitStatsGroupNorm(torch.autograd.Function):
 
 
 class GroupNorm(nn.GroupNorm):
-    def forward(self, x):
+    def _affine_f32(self):
+        """The frozen affine pair as fp32: the parameters themselves (VAE), or copies made once (the binary16 U-Net)."""
+        w, b = self.weight, self.bias
+        if w.dtype == torch.float32 and b.dtype == torch.float32 and w.is_contiguous() and b.is_contiguous():
+            return w, b
+        key = (w.data_ptr(), w._version, b.data_ptr(), b._version)
+        cached = self.__dict__.get("_affine_f32_cache")
+        if cached is None or cached[0] != key:
+            cached = (key, w.detach().float().contiguous(), b.detach().float().contiguous())
+            self.__dict__["_affine_f32_cache"] = cached
+        return cached[1], cached[2]
+
+    def forward(self, x, act=None):
+        """act(group_norm(x)), act None or "silu".  Contiguous binary16 on the GPU with a frozen affine pair: the fused HIP
+        route (GN_FUSED), binary16 out.  Everything else: the stock routes, with F.silu on top for act == "silu"."""
+        if act not in (None, "silu"):
+            raise ValueError(f"act must be None or 'silu' (got {act!r})")
+        if (GN_FUSED and x.is_cuda and x.dtype == torch.float16 and x.dim() >= 2 and x.is_contiguous()
+                and self.affine and not self.weight.requires_grad and not self.bias.requires_grad):
+            from . import norm_ops
+            w, b = self._affine_f32()
+            return norm_ops.group_norm_act(x, w, b, self.num_groups, self.eps, act)
+        y = self._stock(x)
+        return F.silu(y) if act == "silu" else y
+
+    def _stock(self, x):
         B = x.shape[0]
         if not (GN_SPLIT_STATS and x.is_cuda and B * self.num_groups <= 256 and x[0].numel() // self.num_groups >= 65536):
             return super().forward(x)
@@ -98,10 +136,10 @@ class ResBlock(nn.Module):
         self.skip = nn.Conv2d(cin, cout, 1) if cin != cout else None
 
     def forward(self, x, temb=None):
-        h = self.conv1(F.silu(self.norm1(x)))
+        h = self.conv1(self.norm1(x, act="silu"))
         if self.time is not None:
             h = h + self.time(F.silu(temb))[:, :, None, None]
-        h = self.conv2(F.silu(self.norm2(h)))
+        h = self.conv2(self.norm2(h, act="silu"))
         return (x if self.skip is None else self.skip(x)) + h
 
 
@@ -205,7 +243,7 @@ class UNetSD2(nn.Module):
             h = blk[1](h, encoder_hidden_states) if isinstance(blk[1], SpatialTransformer) else h
             if len(blk) == 3:
                 h = blk[2](F.interpolate(h, scale_factor=2.0, mode="nearest"))
-        return self.conv_out(F.silu(self.norm_out(h)))
+        return self.conv_out(self.norm_out(h, act="silu"))
 
 
 class VAEEncoderSD(nn.Module):
@@ -236,7 +274,7 @@ class VAEEncoderSD(nn.Module):
         B, C, H, W = h.shape
         a = self.mid_attn(self.mid_norm(h).permute(0, 2, 3, 1).reshape(B, H * W, C))
         h = self.mid2(h + a.reshape(B, H, W, C).permute(0, 3, 1, 2))
-        return self.quant_conv(self.conv_out(F.silu(self.norm_out(h))))  # [B, 8, H/8, W/8] = (mean, logvar)
+        return self.quant_conv(self.conv_out(self.norm_out(h, act="silu")))  # [B, 8, H/8, W/8] = (mean, logvar)
 
 
 class VAEDecoderSD(nn.Module):
@@ -267,7 +305,7 @@ class VAEDecoderSD(nn.Module):
         h = self.mid2(h + a.reshape(B, H, W, C).permute(0, 3, 1, 2))
         for b in self.blocks:
             h = b(F.interpolate(h, scale_factor=2.0, mode="nearest")) if isinstance(b, nn.Conv2d) else b(h)
-        return self.conv_out(F.silu(self.norm_out(h)))
+        return self.conv_out(self.norm_out(h, act="silu"))
 
 
 class _ClipBlock(nn.Module):
@@ -397,7 +435,7 @@ class StableDiffusionStandIn(nn.Module):
                 and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.float16
                 and not torch.cuda.is_current_stream_capturing()):
             return enc(x)
-        key = (id(enc), GN_SPLIT_STATS, x.requires_grad)
+        key = (id(enc), GN_SPLIT_STATS, GN_FUSED, x.requires_grad)
         cached = self.__dict__.get("_vae_graphed")
         if cached is None or cached[0] != key:
             if self.__dict__.get("_vae_graph_failed"):
@@ -524,7 +562,7 @@ class StableDiffusionStandIn(nn.Module):
         and the autocast state, eagerly if capture is unavailable."""
         if not (getattr(self, "graph_unet", False) and x.is_cuda):  # (objects assembled without __init__: eager)
             return self.unet(x, t, encoder_hidden_states=ctx)
-        key = (tuple(x.shape), x.dtype, tuple(ctx.shape), tuple(t.shape), torch.is_autocast_enabled("cuda"))
+        key = (tuple(x.shape), x.dtype, tuple(ctx.shape), tuple(t.shape), torch.is_autocast_enabled("cuda"), GN_FUSED)
         if getattr(self, "_graph", None) is None or self._graph[0] != key:
             try:
                 gx, gt, gc = x.clone(), t.clone(), ctx.clone()

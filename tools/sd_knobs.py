@@ -1,7 +1,9 @@
 """The diffusion half of an SDS step alone - 512 x 512 resize, VAE encode (with graph), U-Net on the CFG pair (hipGraph
 replay), SDS gradient, latents.backward down to the rendered image - with each stock-PyTorch knob of mi3d/sd_standin.py
 off and on:   python tools/sd_knobs.py [--out gpurun_out/sd_knobs.json]
-HIP-event time per call under torch.autocast(float16), mean of 10 after 3 warm-ups; every configuration on one box."""
+HIP-event time per call under torch.autocast(float16), mean of 10 after 3 warm-ups; every configuration on one box.
+GN_FUSED (the HIP GroupNorm + SiLU kernels) is timed off, on, off, on, then once more with VAE_GRAPH on top; the U-Net's
+captured graph is keyed on the switch, so every configuration replays its own kernels.  --tunableop adds the TunableOp leg."""
 import argparse
 import itertools
 import json
@@ -17,6 +19,7 @@ import torch  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="gpurun_out/sd_knobs.json")
+    ap.add_argument("--tunableop", action="store_true", help="also time PyTorch's TunableOp GEMM search (minutes)")
     a = ap.parse_args()
     from mi3d import sd_standin as S
     dev = torch.device("cuda:0")
@@ -24,8 +27,9 @@ def main():
     text_z = g.get_text_embeds()
     res = {}
     ref_grad = None
-    for gn, vh, vg in ((False, False, False), (True, False, False), (True, False, False)):
-        S.GN_SPLIT_STATS, S.VAE_HALF_CACHE, S.VAE_GRAPH = gn, vh, vg
+    for gf, gn, vh, vg in ((False, True, False, False), (True, True, False, False), (False, True, False, False),
+                           (True, True, False, False), (True, True, False, True), (False, False, False, False)):
+        S.GN_FUSED, S.GN_SPLIT_STATS, S.VAE_HALF_CACHE, S.VAE_GRAPH = gf, gn, vh, vg
         ts, parts = [], {"encode": [], "unet": [], "backward": []}
         for i in range(13):
             torch.manual_seed(5)
@@ -46,7 +50,7 @@ def main():
                 ts.append(ev[0].elapsed_time(ev[3]))
                 for k, (x, y) in zip(parts, ((0, 1), (1, 2), (2, 3))):
                     parts[k].append(ev[x].elapsed_time(ev[y]))
-        key = f"gn_split={int(gn)},vae_half_cache={int(vh)},vae_graph={int(vg)}"
+        key = f"gn_fused={int(gf)},gn_split={int(gn)},vae_half_cache={int(vh)},vae_graph={int(vg)}"
         while key in res:
             key += "'"
         res[key] = {"ms": sum(ts) / len(ts), **{k: sum(v) / len(v) for k, v in parts.items()}}
@@ -54,7 +58,9 @@ def main():
         if ref_grad is None:
             ref_grad = gr
         res[key]["image_grad_max_rel_diff_vs_first"] = float((gr - ref_grad).abs().max() / ref_grad.abs().max())
-    S.GN_SPLIT_STATS, S.VAE_HALF_CACHE, S.VAE_GRAPH = True, False, False
+    S.GN_FUSED, S.GN_SPLIT_STATS, S.VAE_HALF_CACHE, S.VAE_GRAPH = True, True, False, False
+    if not a.tunableop:
+        return _write(res, a.out)
     # PyTorch's TunableOp: every GEMM shape benchmarked once against rocBLAS / hipBLASLt's candidate solutions (the search is
     # timed: it runs in the first call, eagerly, before the U-Net graph is captured again on a fresh guidance object)
     import time
@@ -88,16 +94,20 @@ def main():
                 ts.append(ev[0].elapsed_time(ev[3]))
                 for k, (x, y) in zip(parts, ((0, 1), (1, 2), (2, 3))):
                     parts[k].append(ev[x].elapsed_time(ev[y]))
-        res["gn_split=1,tunableop=1"] = {"ms": sum(ts) / len(ts), **{k: sum(v) / len(v) for k, v in parts.items()},
+        res["gn_fused=1,gn_split=1,tunableop=1"] = {"ms": sum(ts) / len(ts), **{k: sum(v) / len(v) for k, v in parts.items()},
                                          "first_call_s_incl_tuning": first,
                                          "tuned_gemms": len(torch.cuda.tunable.get_results())}
     except Exception as e:  # noqa: BLE001
-        res["gn_split=1,tunableop=1"] = {"error": repr(e)}
+        res["gn_fused=1,gn_split=1,tunableop=1"] = {"error": repr(e)}
     finally:
         torch.cuda.tunable.enable(False)
+    _write(res, a.out)
+
+
+def _write(res, out):
     print(json.dumps(res, indent=1))
-    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-    json.dump(res, open(a.out, "w"), indent=1)
+    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+    json.dump(res, open(out, "w"), indent=1)
 
 
 if __name__ == "__main__":
