@@ -520,6 +520,71 @@ int mi3d_groupnorm_act_backward(const void *x, const void *dy, const float *mean
                                 const float *bias, const float *partial, uint32_t B, uint32_t C, uint32_t HW, uint32_t G,
                                 int act, void *dx, void *stream);
 
+/* ------------------------------------------------------------------ Part 11: the refine stage's point cloud */
+
+/* Depth / mask / rgb views -> the coloured point cloud the refine stage starts from: what `depth2point`,
+ * `multidepth2point_mask`, `z_buffer` and `project` of the reference's nerf/refine_utils.py (:61-208) compute, there in
+ * NumPy, two Python loops over every point, and cv2.erode.  Added under ABI version 5: new symbols only.
+ *
+ * ARITHMETIC.  The reference computes positions, projections and depths in binary64 (NumPy) and the sampled colours and
+ * the canonical-depth lookup in binary32 (torch.Tensor, F.grid_sample); so do these kernels.
+ *   - Geometry is `double`, every operation rounded separately (no fused multiply-add), three-term sums in index order
+ *     k = 0, 1, 2, a translation added last.
+ *   - CAMERA: rt_host = 12 doubles, the rows of the 3 x 4 world-to-camera matrix [R | t]; k_host = 9 doubles, the 3 x 3
+ *     intrinsics, row-major.  Both are HOST pointers read during the call (inverses are the caller's, in NumPy float64).
+ *   - PROJECTION (`project`): cam = p . R^T + t, q = cam . K^T, xy = q[:2] / q[2], z = q[2].  z <= 0 is not rejected.
+ *   - PIXEL: rint (round half to even, `np.round`) of x and y; in bounds iff 0 <= x <= W - 1 and 0 <= y <= H - 1.  The
+ *     reference is undefined for a coordinate that is non-finite or fits no int32; here such a point is OUT OF BOUNDS.
+ *   - SAMPLING (F.grid_sample's defaults: bilinear, zero padding, align_corners=False), binary32: a pixel coordinate v
+ *     becomes g = v / H * 2 - 1 - BOTH axes divided by H, as the reference has it - then i = ((g + 1) * size - 1) / 2
+ *     with size = W for x and H for y, floor, and the four taps nw, ne, sw, se added in this order to 0, each
+ *     value * (x weight * y weight); a tap outside the image adds nothing.
+ * Points are double[n][3]; images are row-major [H][W], 1 <= H, W <= 16384; n <= (2^31 - 1) * 256.
+ *
+ *   mi3d_pc_unproject_workspace  host only: bytes of device scratch for an H x W view (0 for sizes out of range)
+ *   mi3d_pc_unproject  depth double[H][W], mask uint8[H][W] -> the world points of the pixels with mask != 0, in
+ *                      ROW-MAJOR PIXEL ORDER: v = Kinv . (x, y, 1), v *= depth[y][x], p = v . R^T + t with kinv_host
+ *                      (9 doubles) and c2w_host (12 doubles: rows [R | t] of the camera-to-world matrix).  Compaction is
+ *                      order-preserving and deterministic (wave ballot, workgroup sums, a scan across workgroups - no
+ *                      atomic appends): two runs give identical bytes.  *count (device uint64, 8-byte aligned) = the
+ *                      number of kept pixels; rows at or past `cap` are not written, so count > cap tells the caller.
+ *   mi3d_pc_project    the PROJECTION written out: xy double[n][2], z double[n]
+ *   mi3d_pc_zmin       zkeys uint64[H][W] (8-byte aligned), initialised in-stream, then one 64-bit atomicMin per in-bounds
+ *                      point of an order-preserving key of its depth z (negative depths order correctly).
+ *   mi3d_pc_visible    the reference's `z_buffer`, which depends on the per-pixel minimum alone:
+ *                      visible[i] = in_bounds(i) and z_i - zmin[pixel(i)] <= 1.0 / H, uint8 0 / 1.  A NaN compares false.
+ *                      Same points and camera as the mi3d_pc_zmin call before it on the same stream.
+ *   mi3d_box_morph     erosion (dilate = 0: minimum) or dilation (dilate = 1: maximum) of float[H][W] by a kh x kw box of
+ *                      ones, kh and kw odd and <= 31, anchor at the centre; separable, rows then columns through an LDS
+ *                      tile with its halo, one launch.  src != dst.  BORDER: pixels outside the image are ignored - a
+ *                      window's minimum / maximum is taken over its in-image part (cv2.erode / cv2.dilate with their
+ *                      default border).  cv2 is on no machine this project builds on: the border rule is this project's
+ *                      contract, PARITY UNPINNED.  A NaN pixel is ignored like one outside (all-NaN window: +-inf).
+ *   mi3d_pc_cano_filter  refine_utils.py:100-107 against the canonical camera: xy rounded (rint), converted to float, the
+ *                      SAMPLING rule on cano_depth float[H][W], then in double d = z - sampled and
+ *                      keep[i] = not (d <= 1.0 / H and d >= -0.2), uint8 0 / 1.  A coordinate that is non-finite or fits
+ *                      no int32 samples 0.  The reference's arithmetic assumes H == W; this entry point does not check.
+ *   mi3d_pc_colour     refine_utils.py:111-114: xy NOT rounded, converted to float, the SAMPLING rule on image
+ *                      float[3][H][W] -> colour float[n][3].
+ * No entry point allocates or synchronises.  A NULL pointer, a size out of range and an even or oversized box are refused
+ * (hipErrorInvalidValue); n = 0 is accepted. */
+size_t mi3d_pc_unproject_workspace(uint32_t H, uint32_t W);
+int mi3d_pc_unproject(const double *depth, const uint8_t *mask, uint32_t H, uint32_t W, const double *kinv_host,
+                      const double *c2w_host, void *ws, size_t ws_bytes, double *points, unsigned long long cap,
+                      unsigned long long *count, void *stream);
+int mi3d_pc_project(const double *points, unsigned long long n, const double *rt_host, const double *k_host, double *xy,
+                    double *z, void *stream);
+int mi3d_pc_zmin(const double *points, unsigned long long n, const double *rt_host, const double *k_host, uint32_t H,
+                 uint32_t W, unsigned long long *zkeys, void *stream);
+int mi3d_pc_visible(const double *points, unsigned long long n, const double *rt_host, const double *k_host, uint32_t H,
+                    uint32_t W, const unsigned long long *zkeys, uint8_t *visible, void *stream);
+int mi3d_box_morph(const float *src, float *dst, uint32_t H, uint32_t W, uint32_t kh, uint32_t kw, int dilate,
+                   void *stream);
+int mi3d_pc_cano_filter(const double *points, unsigned long long n, const double *rt_host, const double *k_host,
+                        const float *cano_depth, uint32_t H, uint32_t W, uint8_t *keep, void *stream);
+int mi3d_pc_colour(const double *points, unsigned long long n, const double *rt_host, const double *k_host,
+                   const float *image, uint32_t H, uint32_t W, float *colour, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ UNITS = [
     ("mesh.hip", ["-ffp-contract=off"]),
     ("texture.hip", ["-ffp-contract=off"]),
     ("groupnorm.hip", []),
+    ("pointcloud.hip", ["-ffp-contract=off"]),
 ]
 HEADERS = ["mi3d_common.h", "mi3d_grid.h", "mi3d_dev.h", "lds_transpose.h", "mi3d_mc_tables.h", os.path.join("..", "..", "include", "mi3d.h")]
 

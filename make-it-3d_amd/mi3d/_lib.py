@@ -84,6 +84,14 @@ _SIGNATURES = {
     "mi3d_groupnorm_act_forward": [vp, vp, vp, vp, u32, u32, u32, u32, f32, i32, vp, vp, vp, vp],
     "mi3d_groupnorm_act_backward_sums": [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, i32, vp, vp],
     "mi3d_groupnorm_act_backward": [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, i32, vp, vp],
+    # Part 11 -----------------------------------------------------------------------------------------
+    "mi3d_pc_unproject": [vp, vp, u32, u32, vp, vp, vp, C.c_size_t, vp, C.c_uint64, vp, vp],
+    "mi3d_pc_project": [vp, C.c_uint64, vp, vp, vp, vp, vp],
+    "mi3d_pc_zmin": [vp, C.c_uint64, vp, vp, u32, u32, vp, vp],
+    "mi3d_pc_visible": [vp, C.c_uint64, vp, vp, u32, u32, vp, vp, vp],
+    "mi3d_box_morph": [vp, vp, u32, u32, u32, u32, i32, vp],
+    "mi3d_pc_cano_filter": [vp, C.c_uint64, vp, vp, vp, u32, u32, vp, vp],
+    "mi3d_pc_colour": [vp, C.c_uint64, vp, vp, vp, u32, u32, vp, vp],
 }
 
 # host-only queries whose return value is not a hipError_t: (argtypes, restype), bound in lib() like the block below
@@ -92,6 +100,7 @@ _LATE_SIGNATURES = {
     "mi3d_mc_case": ([u32, C.POINTER(C.c_int8)], C.c_int),
     "mi3d_atlas_cell": ([C.c_uint64, u32], u32),
     "mi3d_groupnorm_chunks": ([u32], u32),
+    "mi3d_pc_unproject_workspace": ([u32, u32], C.c_size_t),
 }
 
 

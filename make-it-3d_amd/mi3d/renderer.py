@@ -132,6 +132,20 @@ class NeRFRenderer(nn.Module):
         from . import mesh
         return mesh.export(self, path, resolution, S, texture_size=texture_size, ssaa=ssaa)
 
+    @torch.no_grad()
+    def export_point_cloud(self, outputdir, poses, ref_rgb, fov, H, W, **kwargs):
+        """The refine stage's starting point, which the reference builds in Trainer.refine (nerf/utils.py:747-788) from
+        the image files of a test run: every pose of `poses` [V, 4, 4] is rendered at H x W with the eval route, the
+        views become the canonical cloud (view (V - 1) // 2, coloured from `ref_rgb` [H, W, 3]; None: from its own
+        render) and the novel views' cloud on the GPU (mi3d.pointcloud), and `vertices_cano.npy`,
+        `vertices_color_cano.npy`, `vertices_novel.npy`, `vertices_color_novel.npy` are written to `outputdir`.  Returns
+        the four arrays as GPU tensors (float64 points, float32 colours): what refine_train_step takes as `points` and
+        `colour` once cast to float32.  `kwargs` go to pointcloud.from_model.  A CPU model raises Mi3dError."""
+        from . import pointcloud
+        out = pointcloud.from_model(self, poses, fov, H, W, ref_rgb=ref_rgb, **kwargs)
+        pointcloud.save(outputdir, *out)
+        return out
+
     # --- pure-PyTorch sampler path (BASELINE config 1) --------------------------------------------
     def run(self, rays_o, rays_d, ref_bg=None, num_steps=128, upsample_steps=128, light_d=None, ambient_ratio=1.0,
             shading="albedo", bg_color=None, perturb=False, **kwargs):
