@@ -34,8 +34,8 @@ extern "C" {
 
 /* the ABI version: 5 (4 = 3 + the compact-round inference loop of Part 1b; 5: that loop's ctl block is int32[16] with
  * the dropped-row count in [8], and its plan never passes max_steps; every other entry point is unchanged).  Part 8
- * (marching cubes), Part 9 (texture baking) and Part 10 (GroupNorm) were added under 5: new symbols only, nothing existing
- * changed. */
+ * (marching cubes), Part 9 (texture baking), Part 10 (GroupNorm) and Part 1's mi3d_composite_rays_train_backward_depth were
+ * added under 5: new symbols only, nothing existing changed. */
 int mi3d_abi_version(void);
 const char *mi3d_last_error_string(int err);
 
@@ -77,6 +77,18 @@ int mi3d_composite_rays_train_backward(const float *grad_weights_sum, const floa
                                        const int32_t *rays, const float *weights_sum, const float *image,
                                        uint32_t M, uint32_t N, float T_thresh, float *grad_sigmas,
                                        float *grad_rgbs, void *stream);
+/* Not in the reference: the density compositor's backward WITH the gradient of `depth` (the reference's op drops
+ * grad_depth, raymarching.py:287, so a depth loss reaches the field only through (1 - weights_sum) * max_depth on that
+ * path).  grad_depth [N] and depth [N] (the forward's output) are indexed by ray id like grad_weights_sum / weights_sum.
+ * grad_sigmas[i] gains, inside its bracket,  grad_depth * (T_incl_i * t_i - (depth - d_i)),  d_i = sum_{j <= i} w_j t_j;
+ * grad_rgbs is what composite_rays_train_backward writes.  Same skips: an empty ray, a slab that overflows M, rows past
+ * the stop sample.  With grad_depth == 0 the result is bit-identical to composite_rays_train_backward's.  There is no
+ * SDF counterpart: that backward stays the reference's formula.  Added under ABI version 5: a new symbol only. */
+int mi3d_composite_rays_train_backward_depth(const float *grad_weights_sum, const float *grad_depth,
+                                             const float *grad_image, const float *sigmas, const float *rgbs,
+                                             const float *deltas, const int32_t *rays, const float *weights_sum,
+                                             const float *depth, const float *image, uint32_t M, uint32_t N,
+                                             float T_thresh, float *grad_sigmas, float *grad_rgbs, void *stream);
 /* raymarching.h:16-17 composite_sdf_rays_train_{forward,backward} (alpha = sigma) */
 int mi3d_composite_sdf_rays_train_forward(const float *sigmas, const float *rgbs, const float *deltas,
                                           const int32_t *rays, uint32_t M, uint32_t N, float T_thresh,

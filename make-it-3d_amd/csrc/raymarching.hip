@@ -13,6 +13,9 @@
 //    is a wave64 multiplicative prefix scan, early termination is a ballot + first-set-lane, sums are
 //    wave reductions.  Same quadrature, same break rule (accumulate the crossing sample, then stop:
 //    raymarching.cu:554-557), results agree with the sequential loop to fp32 rounding.
+//    composite_rays_train_backward_depth is the backward that also back-propagates `depth` (the reference's drops
+//    grad_depth, raymarching.py:287): one more scan per chunk.  Density variant only - the SDF backward is pinned to the
+//    reference's formula and is left as it is.
 //  * utilities (near/far, sph, morton, packbits) and the inference march/composite: one thread per
 //    element, vectorised loads where the layout allows.
 //
@@ -351,12 +354,19 @@ __global__ __launch_bounds__(256) void k_composite_train_fwd(
     }
 }
 
-template <bool SDF>
-__global__ __launch_bounds__(256) void k_composite_train_bwd(
-    const float *__restrict__ grad_ws, const float *__restrict__ grad_image, const float *__restrict__ sigmas,
-    const float *__restrict__ rgbs, const float *__restrict__ deltas, const int32_t *__restrict__ rays,
-    const float *__restrict__ weights_sum, const float *__restrict__ image, uint32_t M, uint32_t N, float T_thresh,
-    float *__restrict__ grad_sigmas, float *__restrict__ grad_rgbs) {
+// One ray of the backward pass.  DEPTH: the instance that also back-propagates `depth` (density variant only; the SDF
+// backward is pinned to the reference's formula, which has no depth term, and Make-It-3D never calls it).  The forward's
+// depth = sum_{i <= last} w_i t_i, so d depth / d sigma_i = delta_i (T_incl_i t_i - (depth - d_i)) with d_i the depth
+// accumulated up to and including sample i: one more scan and one more wave-uniform carry, the shape of the colour terms.
+// With DEPTH false, grad_depth / depth are never read and the code is the reference's backward as it always was.
+template <bool SDF, bool DEPTH>
+__device__ __forceinline__ void composite_train_bwd_ray(
+    const float *__restrict__ grad_ws, const float *__restrict__ grad_depth, const float *__restrict__ grad_image,
+    const float *__restrict__ sigmas, const float *__restrict__ rgbs, const float *__restrict__ deltas,
+    const int32_t *__restrict__ rays, const float *__restrict__ weights_sum, const float *__restrict__ depth,
+    const float *__restrict__ image, uint32_t M, uint32_t N, float T_thresh, float *__restrict__ grad_sigmas,
+    float *__restrict__ grad_rgbs) {
+    static_assert(!(SDF && DEPTH), "the SDF compositor has no depth-aware backward");
     const int lane = lane_id();
     const uint32_t row = blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
     if (row >= N) return;
@@ -369,6 +379,11 @@ __global__ __launch_bounds__(256) void k_composite_train_bwd(
                 gi2 = grad_image[(size_t)index * 3 + 2];
     const float rf = image[(size_t)index * 3], gf = image[(size_t)index * 3 + 1], bf = image[(size_t)index * 3 + 2];
     const float ws_term = gws * (1.0f - ws_final);
+    float gd = 0.f, df = 0.f, d_run = 0.f;  // DEPTH only: d loss / d depth, the forward's depth, depth before the chunk
+    if constexpr (DEPTH) {
+        gd = grad_depth[index];
+        df = depth[index];
+    }
 
     float T_run = 1.0f, t_run = 0.f, r_run = 0.f, g_run = 0.f, b_run = 0.f;  // colour accumulated before chunk
     for (uint32_t base = 0; base < num_steps; base += kWave) {
@@ -384,18 +399,44 @@ __global__ __launch_bounds__(256) void k_composite_train_bwd(
         // colour accumulated up to and including this sample
         const float sr = wave_scan_add(c.w * c0, lane), sg = wave_scan_add(c.w * c1, lane),
                     sb = wave_scan_add(c.w * c2, lane);
+        float sd = 0.f;  // depth accumulated up to and including this sample, within the chunk
+        if constexpr (DEPTH) sd = wave_scan_add(c.w * c.t_incl, lane);
         if (c.active) {
             const float r = r_run + sr, g = g_run + sg, b = b_run + sb;
             float *gc = grad_rgbs + (size_t)i * 3;
             gc[0] = gi0 * c.w; gc[1] = gi1 * c.w; gc[2] = gi2 * c.w;
-            grad_sigmas[i] = d0 * (gi0 * (c.T_incl * c0 - (rf - r)) + gi1 * (c.T_incl * c1 - (gf - g)) +
-                                   gi2 * (c.T_incl * c2 - (bf - b)) + ws_term);
+            float bracket = gi0 * (c.T_incl * c0 - (rf - r)) + gi1 * (c.T_incl * c1 - (gf - g)) +
+                            gi2 * (c.T_incl * c2 - (bf - b)) + ws_term;
+            if constexpr (DEPTH) bracket = bracket + gd * (c.T_incl * c.t_incl - (df - (d_run + sd)));
+            grad_sigmas[i] = d0 * bracket;
         }
         if (c.terminated) break;
         r_run += __shfl(sr, kWave - 1, kWave);
         g_run += __shfl(sg, kWave - 1, kWave);
         b_run += __shfl(sb, kWave - 1, kWave);
+        if constexpr (DEPTH) d_run += __shfl(sd, kWave - 1, kWave);
     }
+}
+
+template <bool SDF>
+__global__ __launch_bounds__(256) void k_composite_train_bwd(
+    const float *__restrict__ grad_ws, const float *__restrict__ grad_image, const float *__restrict__ sigmas,
+    const float *__restrict__ rgbs, const float *__restrict__ deltas, const int32_t *__restrict__ rays,
+    const float *__restrict__ weights_sum, const float *__restrict__ image, uint32_t M, uint32_t N, float T_thresh,
+    float *__restrict__ grad_sigmas, float *__restrict__ grad_rgbs) {
+    composite_train_bwd_ray<SDF, false>(grad_ws, nullptr, grad_image, sigmas, rgbs, deltas, rays, weights_sum, nullptr,
+                                        image, M, N, T_thresh, grad_sigmas, grad_rgbs);
+}
+
+// The depth-aware instance (density variant): reads grad_depth[N] and the forward's depth[N] as well.
+__global__ __launch_bounds__(256) void k_composite_train_bwd_depth(
+    const float *__restrict__ grad_ws, const float *__restrict__ grad_depth, const float *__restrict__ grad_image,
+    const float *__restrict__ sigmas, const float *__restrict__ rgbs, const float *__restrict__ deltas,
+    const int32_t *__restrict__ rays, const float *__restrict__ weights_sum, const float *__restrict__ depth,
+    const float *__restrict__ image, uint32_t M, uint32_t N, float T_thresh, float *__restrict__ grad_sigmas,
+    float *__restrict__ grad_rgbs) {
+    composite_train_bwd_ray<false, true>(grad_ws, grad_depth, grad_image, sigmas, rgbs, deltas, rays, weights_sum, depth,
+                                         image, M, N, T_thresh, grad_sigmas, grad_rgbs);
 }
 
 // ---------------------------------------------------------------- inference (one thread per alive ray)
@@ -855,6 +896,18 @@ MI3D_COMPOSITE_FWD(mi3d_composite_sdf_rays_train_forward, true)
     }
 MI3D_COMPOSITE_BWD(mi3d_composite_rays_train_backward, false)
 MI3D_COMPOSITE_BWD(mi3d_composite_sdf_rays_train_backward, true)
+
+int mi3d_composite_rays_train_backward_depth(const float *grad_weights_sum, const float *grad_depth,
+                                             const float *grad_image, const float *sigmas, const float *rgbs,
+                                             const float *deltas, const int32_t *rays, const float *weights_sum,
+                                             const float *depth, const float *image, uint32_t M, uint32_t N,
+                                             float T_thresh, float *grad_sigmas, float *grad_rgbs, void *stream) {
+    if (N == 0) return 0;
+    hipLaunchKernelGGL(k_composite_train_bwd_depth, dim3(cdiv(N, 4)), dim3(256), 0, as_stream(stream), grad_weights_sum,
+                       grad_depth, grad_image, sigmas, rgbs, deltas, rays, weights_sum, depth, image, M, N, T_thresh,
+                       grad_sigmas, grad_rgbs);
+    return launch_status();
+}
 
 int mi3d_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, const float *rays_t,
                     const float *rays_o, const float *rays_d, float bound, float dt_gamma, uint32_t max_steps,

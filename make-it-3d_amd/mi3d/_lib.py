@@ -27,6 +27,7 @@ _SIGNATURES = {
     "mi3d_march_zero_tail": [vp, u32, u32, vp, vp, vp, vp],
     "mi3d_composite_rays_train_forward": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, vp],
     "mi3d_composite_rays_train_backward": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, vp, vp],
+    "mi3d_composite_rays_train_backward_depth": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, vp, vp],
     "mi3d_composite_sdf_rays_train_forward": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, vp],
     "mi3d_composite_sdf_rays_train_backward": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, vp, vp],
     "mi3d_march_rays": [u32, u32, vp, vp, vp, vp, f32, f32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp],

@@ -224,9 +224,13 @@ class NeRFRenderer(nn.Module):
 
     # --- occupancy-grid path (the hot path) ------------------------------------------------------------
     def run_cuda(self, rays_o, rays_d, depth_scale=None, bg_color=None, dt_gamma=0, light_d=None, ambient_ratio=1.0,
-                 shading="albedo", perturb=False, force_all_rays=False, max_steps=1024, T_thresh=1e-4, **kwargs):
+                 shading="albedo", perturb=False, force_all_rays=False, max_steps=1024, T_thresh=1e-4, depth_grad=None,
+                 **kwargs):
         """renderer.py:481-583.  Training: march -> field (13-point stencil) -> composite + normal regularisers.
-        Eval: the march/composite loop over alive rays, its round state kept on the device."""
+        Eval: the march/composite loop over alive rays, its round state kept on the device.
+        `depth_grad` (not in the reference; None = opt.depth_grad, default False): in training, composite with the op
+        whose backward back-propagates `depth` - without it a loss on out["depth"] reaches the field only through
+        (1 - weights_sum) * max_depth, as in the reference's cuda_ray path."""
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3)
         rays_d = rays_d.contiguous().view(-1, 3)
@@ -250,7 +254,10 @@ class NeRFRenderer(nn.Module):
             step = 2 * math.sqrt(3) / max_steps  # dt_min: only steers the scatter's merge heuristic
             sigmas, albedo, normals, normals_jitter = self.field_stencil(xyzs, x2, step)
             rgbs = self.shade(albedo, normals, light_d, ambient_ratio, shading)
-            weights_sum, depth, image = raymarching.composite_rays_train(sigmas, rgbs, deltas, rays, T_thresh)
+            if depth_grad is None:
+                depth_grad = getattr(self.opt, "depth_grad", False)
+            composite = raymarching.composite_rays_train_depth if depth_grad else raymarching.composite_rays_train
+            weights_sum, depth, image = composite(sigmas, rgbs, deltas, rays, T_thresh)
             if normals is not None:
                 w = 1 - torch.exp(-sigmas)  # "not very exact in cuda ray mode": per-sample opacity proxy
                 out["loss_orient"] = (w.detach() * (normals * dirs).sum(-1).clamp(min=0) ** 2).mean()

@@ -7,6 +7,9 @@ tests, minus the CLIP terms (openai `clip` weights are unavailable offline and o
     -> regularisers (opacity, entropy, orientation, smoothness)
     -> backward -> clip_grad_norm -> GradScaler.step(Adan)
 
+`ref_view_train_step` is the other kind of coarse-stage step: the reference (front) view, trained against the input
+image and its depth prior (utils.py:551-559) - see its docstring.
+
 `sds_backward`:
   "reference": two NeRF backward passes, exactly as the reference does it - `latents.backward(grad,
                retain_graph=True)` inside guidance.train_step (nerf/sd.py:171), then `scaler.scale(loss).backward()`.
@@ -28,7 +31,7 @@ import torch.nn.functional as F
 DEFAULT_OPT = dict(bound=1.0, cuda_ray=True, min_near=0.1, density_thresh=10.0, bg_radius=-1, blob_density=5.0,
                    blob_radius=0.1, max_depth=10.0, dt_gamma=0.0, max_steps=1024, lambda_entropy=1.0,
                    lambda_opacity=1e-3, lambda_orient=1e-2, lambda_smooth=1.0, guidance_scale=10.0, lr=1e-3,
-                   fp16=True)
+                   fp16=True, lambda_img=1e3, lambda_depth=1.0, depth_grad=False)
 
 
 def make_opt(**over):
@@ -111,6 +114,66 @@ def sds_train_step(model, guidance, text_z, optimizer, scaler, rays_o, rays_d, d
         torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=10)  # on still-scaled grads, as utils.py:984
         scaler.step(optimizer)
         scaler.update()
+    return loss.detach()
+
+
+def pearson_corrcoef(x, y):
+    """Pearson correlation of two 1-D tensors: centred covariance over the product of the standard deviations, clamped
+    to [-1, 1] - what `torchmetrics.PearsonCorrCoef()(x, y)` returns for one batch (nerf/utils.py:306, :432), restated
+    from its published functional form - PARITY UNPINNED (torchmetrics is not a dependency and its version is not
+    pinned by the reference)."""
+    if x.dim() != 1 or x.shape != y.shape:
+        raise ValueError("pearson_corrcoef takes two 1-D tensors of one length")
+    if x.dtype in (torch.float16, torch.bfloat16):
+        x, y = x.float(), y.float()
+    y = y.to(x.dtype)
+    xm, ym = x - x.mean(), y - y.mean()
+    cov, var_x, var_y = (xm * ym).sum(), (xm * xm).sum(), (ym * ym).sum()
+    return (cov / (var_x * var_y).sqrt()).clamp(-1.0, 1.0)
+
+
+def ref_view_loss(pred_rgb, pred_depth, gt_rgb, ref_depth, depth_mask, opt):
+    """utils.py:551-559 with `depth_loss` (:423-433): pred_rgb [1,3,h,w] and pred_depth [1,1,h,w] are upsampled to the
+    reference image's size; lambda_img * L1(rgb) + lambda_depth * (1 - Pearson(depth, prior)) over the pixels
+    `depth_mask` (bool, True = no prior there) leaves in."""
+    size = gt_rgb.shape[-2:]
+    pred_rgb = F.interpolate(pred_rgb, size, mode="bilinear", align_corners=True)
+    pred_depth = F.interpolate(pred_depth, size, mode="bilinear", align_corners=True)
+    loss_img = opt.lambda_img * F.l1_loss(pred_rgb, gt_rgb)
+    valid = ~depth_mask.reshape(-1)
+    d = torch.nan_to_num(pred_depth.squeeze()).reshape(-1)
+    co = pearson_corrcoef(d[valid], ref_depth.reshape(-1)[valid])
+    return loss_img + opt.lambda_depth * (1 - co)
+
+
+def ref_view_train_step(model, optimizer, scaler, rays_o, rays_d, depth_scale, H, W, opt, ref_imgs, ref_depth, depth_mask,
+                        past_diff_iters=False, depth_grad=None, grad_sync=None):
+    """One iteration of `train_step` on the reference (front) view (utils.py:461-559 with data['is_front']): no guidance,
+    albedo shading, the regularisers, then the image and depth-prior terms against ref_imgs [1,4,S,S] (RGBA),
+    ref_depth [S,S] and depth_mask [S,S] (bool).  The sibling of `sds_train_step`; returns the (unscaled) loss.
+    `depth_grad`: None = opt.depth_grad; True lets the Pearson term reach the density through `depth` itself."""
+    optimizer.zero_grad(set_to_none=False)
+    B = rays_o.shape[0]
+    if depth_grad is None:
+        depth_grad = getattr(opt, "depth_grad", False)
+    with torch.autocast("cuda", dtype=torch.float16, enabled=opt.fp16):
+        bg_color = torch.rand(3, device=rays_o.device)
+        alpha = ref_imgs[:, 3:, :, :]
+        gt_rgb = ref_imgs[:, :3, :, :] * alpha + bg_color.view(1, 3, 1, 1) * (1 - alpha)
+        outputs = model.render(rays_o, rays_d, depth_scale=depth_scale, bg_color=bg_color, staged=False, perturb=True,
+                               ambient_ratio=1.0, shading="albedo", force_all_rays=True, depth_grad=depth_grad,
+                               **render_kwargs(opt))
+        pred_rgb = outputs["image"].reshape(B, H, W, 3).permute(0, 3, 1, 2).contiguous()
+        pred_depth = outputs["depth"].reshape(B, H, W, 1).permute(0, 3, 1, 2).contiguous()
+        pred_ws = outputs["weights_sum"].reshape(B, 1, H, W)
+        loss = regularisers(opt, outputs, pred_ws, past_diff_iters=past_diff_iters)
+        loss = loss + ref_view_loss(pred_rgb, pred_depth, gt_rgb, ref_depth, depth_mask, opt)
+    scaler.scale(loss).backward()
+    if grad_sync is not None:
+        grad_sync()
+    torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=10)  # on still-scaled grads, as utils.py:984
+    scaler.step(optimizer)
+    scaler.update()
     return loss.detach()
 
 

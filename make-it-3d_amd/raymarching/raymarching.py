@@ -5,7 +5,9 @@ csrc/raymarching.hip through the C ABI of include/mi3d.h.
 Same callables, same argument order/defaults, same return shapes and the same quirks:
   * `march_rays_train` pads the returned sample count UP PAST the next multiple of `align`
     (a full extra `align` when already aligned) - reference raymarching.py:237-238;
-  * `composite_rays_train.backward` ignores grad_depth - reference raymarching.py:287;
+  * `composite_rays_train.backward` ignores grad_depth - reference raymarching.py:287.  `composite_rays_train_depth`
+    (not in the reference) is the same op with a backward that does back-propagate depth, for a loss on the rendered
+    depth (the reference-view step's Pearson term); nothing calls it unless asked to (renderer `depth_grad`);
   * inputs are cast to fp32 under autocast (custom_fwd(cast_inputs=float32)).
 Differences (none observable through the API):
   * no 537 MB zero fill of the [N*max_steps] sample buffers - only the <= `align` padding rows are
@@ -188,28 +190,33 @@ class _march_rays_train(Function):
 march_rays_train = _march_rays_train.apply
 
 
+def _composite_train_forward(ctx, fwd_name, sigmas, rgbs, deltas, rays, T_thresh):
+    """sigmas [M], rgbs [M,3], deltas [M,2], rays int32 [N,3] -> weights_sum [N], depth [N], image [N,3]."""
+    sigmas = L.dev_f32(sigmas.contiguous(), "sigmas")
+    rgbs = L.dev_f32(rgbs.contiguous(), "rgbs", 3)
+    deltas = L.dev_f32(deltas.contiguous(), "deltas", 2)
+    rays = L.dev_typed(rays.contiguous(), "rays", torch.int32)
+    M, N = sigmas.shape[0], rays.shape[0]
+    if rgbs.shape[0] != M or deltas.shape[0] != M:
+        raise L.Mi3dError("sigmas / rgbs / deltas row counts differ")
+    dev = sigmas.device
+    weights_sum = torch.empty(N, dtype=_f32, device=dev)
+    depth = torch.empty(N, dtype=_f32, device=dev)
+    image = torch.empty(N, 3, dtype=_f32, device=dev)
+    L.launch(fwd_name, sigmas, L.ptr(sigmas), L.ptr(rgbs), L.ptr(deltas), L.ptr(rays), M, N, float(T_thresh),
+           L.ptr(weights_sum), L.ptr(depth), L.ptr(image))
+    ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, depth, image)
+    ctx.dims = [M, N, T_thresh]
+    return weights_sum, depth, image
+
+
 def _composite_train_cls(fwd_name, bwd_name):
     class _composite(Function):
         @staticmethod
         @_custom_fwd
         def forward(ctx, sigmas, rgbs, deltas, rays, T_thresh=1e-4):
             """sigmas [M], rgbs [M,3], deltas [M,2], rays int32 [N,3] -> weights_sum [N], depth [N], image [N,3]."""
-            sigmas = L.dev_f32(sigmas.contiguous(), "sigmas")
-            rgbs = L.dev_f32(rgbs.contiguous(), "rgbs", 3)
-            deltas = L.dev_f32(deltas.contiguous(), "deltas", 2)
-            rays = L.dev_typed(rays.contiguous(), "rays", torch.int32)
-            M, N = sigmas.shape[0], rays.shape[0]
-            if rgbs.shape[0] != M or deltas.shape[0] != M:
-                raise L.Mi3dError("sigmas / rgbs / deltas row counts differ")
-            dev = sigmas.device
-            weights_sum = torch.empty(N, dtype=_f32, device=dev)
-            depth = torch.empty(N, dtype=_f32, device=dev)
-            image = torch.empty(N, 3, dtype=_f32, device=dev)
-            L.launch(fwd_name, sigmas, L.ptr(sigmas), L.ptr(rgbs), L.ptr(deltas), L.ptr(rays), M, N, float(T_thresh),
-                   L.ptr(weights_sum), L.ptr(depth), L.ptr(image))
-            ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, depth, image)
-            ctx.dims = [M, N, T_thresh]
-            return weights_sum, depth, image
+            return _composite_train_forward(ctx, fwd_name, sigmas, rgbs, deltas, rays, T_thresh)
 
         @staticmethod
         @_custom_bwd
@@ -234,6 +241,42 @@ composite_rays_train = _composite_rays_train.apply
 _composite_sdf_rays_train = _composite_train_cls("mi3d_composite_sdf_rays_train_forward",
                                                  "mi3d_composite_sdf_rays_train_backward")
 composite_sdf_rays_train = _composite_sdf_rays_train.apply
+
+
+class _composite_rays_train_depth(Function):
+    """composite_rays_train whose backward also back-propagates `depth` (C ABI: ..._backward_depth).  Same forward launch,
+    same outputs.  A loss that never touches depth (grad_depth is None) runs the very backward kernel
+    composite_rays_train runs."""
+
+    @staticmethod
+    @_custom_fwd
+    def forward(ctx, sigmas, rgbs, deltas, rays, T_thresh=1e-4):
+        ctx.set_materialize_grads(False)
+        return _composite_train_forward(ctx, "mi3d_composite_rays_train_forward", sigmas, rgbs, deltas, rays, T_thresh)
+
+    @staticmethod
+    @_custom_bwd
+    def backward(ctx, grad_weights_sum, grad_depth, grad_image):
+        sigmas, rgbs, deltas, rays, weights_sum, depth, image = ctx.saved_tensors
+        M, N, T_thresh = ctx.dims
+        # set_materialize_grads(False): an output the loss never used arrives as None
+        grad_weights_sum = torch.zeros_like(weights_sum) if grad_weights_sum is None else grad_weights_sum.contiguous()
+        grad_image = torch.zeros_like(image) if grad_image is None else grad_image.contiguous()
+        grad_sigmas = torch.zeros_like(sigmas)  # samples past a ray's termination keep zero gradient
+        grad_rgbs = torch.zeros_like(rgbs)
+        if grad_depth is None:
+            L.launch("mi3d_composite_rays_train_backward", sigmas, L.ptr(grad_weights_sum), L.ptr(grad_image),
+                     L.ptr(sigmas), L.ptr(rgbs), L.ptr(deltas), L.ptr(rays), L.ptr(weights_sum), L.ptr(image), M, N,
+                     float(T_thresh), L.ptr(grad_sigmas), L.ptr(grad_rgbs))
+        else:
+            grad_depth = grad_depth.contiguous()
+            L.launch("mi3d_composite_rays_train_backward_depth", sigmas, L.ptr(grad_weights_sum), L.ptr(grad_depth),
+                     L.ptr(grad_image), L.ptr(sigmas), L.ptr(rgbs), L.ptr(deltas), L.ptr(rays), L.ptr(weights_sum),
+                     L.ptr(depth), L.ptr(image), M, N, float(T_thresh), L.ptr(grad_sigmas), L.ptr(grad_rgbs))
+        return grad_sigmas, grad_rgbs, None, None, None
+
+
+composite_rays_train_depth = _composite_rays_train_depth.apply
 
 # ---------------------------------------------------------------------------- inference
 
