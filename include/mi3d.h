@@ -34,8 +34,8 @@ extern "C" {
 
 /* the ABI version: 5 (4 = 3 + the compact-round inference loop of Part 1b; 5: that loop's ctl block is int32[16] with
  * the dropped-row count in [8], and its plan never passes max_steps; every other entry point is unchanged).  Part 8
- * (marching cubes), Part 9 (texture baking), Part 10 (GroupNorm) and Part 1's mi3d_composite_rays_train_backward_depth were
- * added under 5: new symbols only, nothing existing changed. */
+ * (marching cubes), Part 9 (texture baking), Part 10 (GroupNorm), Part 12 (the Canny detector) and Part 1's
+ * mi3d_composite_rays_train_backward_depth were added under 5: new symbols only, nothing existing changed. */
 int mi3d_abi_version(void);
 const char *mi3d_last_error_string(int err);
 
@@ -531,6 +531,52 @@ int mi3d_groupnorm_act_backward_sums(const void *x, const void *dy, const float 
 int mi3d_groupnorm_act_backward(const void *x, const void *dy, const float *mean, const float *rstd, const float *weight,
                                 const float *bias, const float *partial, uint32_t B, uint32_t C, uint32_t HW, uint32_t G,
                                 int act, void *dx, void *stream);
+
+/* ------------------------------------------------------------------ Part 12: the Canny depth-edge detector */
+
+/* The edge detector of the reference's load_views (nerf/refine_utils.py:386-393: `cv2.Canny(uint8 depth, 10, 10)`, dilated
+ * and removed from a novel view's mask, so that the "flying" pixels of a depth discontinuity never become points).  Added
+ * under ABI version 5: new symbols only.  (Declared ahead of the point-cloud part it serves: tests/test_pointcloud_cpu.py
+ * reads that part as the tail of this header.)
+ *
+ * STANDING.  The arithmetic below is OpenCV's `Canny(image, t1, t2)` with apertureSize = 3 and L2gradient = False,
+ * RESTATED FROM MEMORY: cv2 is on no machine this project builds or runs on.  The contract is therefore this project's
+ * own and parity with cv2 is UNPINNED - the standing of mi3d_box_morph's border, of mcubes and of xatlas.
+ *
+ *   - SIZE: H, W >= 1 and H * W < 2^31.  image and cls are uint8[H][W], row-major.
+ *   - THRESHOLDS: low = floor(t1), high = floor(t2) as int32 (the caller's floor); swapped here if low > high.
+ *   - SOBEL, image borders replicated, all in integers:
+ *       gx = (I[y-1][x+1] + 2 I[y][x+1] + I[y+1][x+1]) - (the same at x-1)
+ *       gy = (I[y+1][x-1] + 2 I[y+1][x] + I[y+1][x+1]) - (the same at y-1)
+ *       mag = |gx| + |gy| (at most 2040).  The magnitude of a position outside the image is 0.
+ *   - DIRECTION: a pixel is a candidate iff mag > low.  ax = |gx|, ay = |gy| << 15, t22 = ax * 13573 (tan 22.5 deg in
+ *     15 fractional bits), t67 = t22 + (ax << 16); with ax, |gy| <= 1020 every term is below 2^27: 32-bit arithmetic.
+ *   - NON-MAXIMUM SUPPRESSION by sector:
+ *       ay < t22 (horizontal gradient)  keep iff mag > mag[y][x-1] and mag >= mag[y][x+1]
+ *       ay > t67 (vertical gradient)    keep iff mag > mag[y-1][x] and mag >= mag[y+1][x]
+ *       otherwise (diagonal)            (gx ^ gy) >= 0: keep iff mag > mag[y-1][x-1] and mag > mag[y+1][x+1]
+ *                                       else:           keep iff mag > mag[y-1][x+1] and mag > mag[y+1][x-1]
+ *   - CLASSES: a kept pixel is strong (2) if mag > high, else weak (1); everything else is 0.
+ *   - HYSTERESIS: a weak pixel with a strong 8-neighbour becomes strong, to the fixed point.  Promotion is monotone
+ *     (1 -> 2 only), so the fixed point is unique: the weak pixels 8-connected to a strong one through weak pixels.
+ *   - FINAL EDGE MAP (the caller's): 255 where cls == 2 after hysteresis, else 0.
+ *
+ *   mi3d_canny_classify    one launch: Sobel, magnitude, non-maximum suppression and the double threshold, from a
+ *                          32 x 32 image tile with its 2-pixel halo in LDS (a decision needs the magnitudes of the 8
+ *                          neighbours).  counts (device uint64[2], 8-byte aligned) is zeroed in-stream and receives
+ *                          {weak, strong}.  image != cls.
+ *   mi3d_canny_hysteresis  `sweeps` >= 1 sweeps over cls, in place, in-stream.  In a sweep every workgroup loads its tile
+ *                          of cls with a 1-pixel halo, promotes until the tile is stable and writes its promoted pixels
+ *                          back.  No workgroup waits on another (no grid barrier, no cooperative launch); a tile reads
+ *                          its neighbours' pixels in whatever state of the ascent they are in, which changes how many
+ *                          sweeps are needed and never the fixed point.  After the call changed[0] (device int32) != 0
+ *                          iff the call's FINAL sweep promoted at least one pixel; the host repeats the call until it
+ *                          is 0.  H * W sweeps always suffice.
+ * No entry point allocates or synchronises.  A NULL pointer, a size out of range and sweeps = 0 are refused
+ * (hipErrorInvalidValue). */
+int mi3d_canny_classify(const uint8_t *image, uint32_t H, uint32_t W, int32_t low, int32_t high, uint8_t *cls,
+                        unsigned long long *counts, void *stream);
+int mi3d_canny_hysteresis(uint8_t *cls, uint32_t H, uint32_t W, uint32_t sweeps, int32_t *changed, void *stream);
 
 /* ------------------------------------------------------------------ Part 11: the refine stage's point cloud */
 

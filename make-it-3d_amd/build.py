@@ -25,6 +25,7 @@ UNITS = [
     ("texture.hip", ["-ffp-contract=off"]),
     ("groupnorm.hip", []),
     ("pointcloud.hip", ["-ffp-contract=off"]),
+    ("canny.hip", []),
 ]
 HEADERS = ["mi3d_common.h", "mi3d_grid.h", "mi3d_dev.h", "lds_transpose.h", "mi3d_mc_tables.h", os.path.join("..", "..", "include", "mi3d.h")]
 

@@ -93,6 +93,9 @@ _SIGNATURES = {
     "mi3d_box_morph": [vp, vp, u32, u32, u32, u32, i32, vp],
     "mi3d_pc_cano_filter": [vp, C.c_uint64, vp, vp, vp, u32, u32, vp, vp],
     "mi3d_pc_colour": [vp, C.c_uint64, vp, vp, vp, u32, u32, vp, vp],
+    # Part 12 -----------------------------------------------------------------------------------------
+    "mi3d_canny_classify": [vp, u32, u32, i32, i32, vp, vp, vp],
+    "mi3d_canny_hysteresis": [vp, u32, u32, u32, vp, vp],
 }
 
 # host-only queries whose return value is not a hipError_t: (argtypes, restype), bound in lib() like the block below

@@ -6,6 +6,9 @@ arithmetic (geometry in binary64, sampling in binary32, as NumPy and torch give 
   project, z_buffer, depth2point   the reference's names, argument order and results (PINNED by fixtures its own functions
                                    generate, tests/golden/pointcloud.npz)
   erode, dilate                    cv2.erode / cv2.dilate by a box of ones; the border rule is this project's contract
+  canny, depth_edge_mask           cv2.Canny (aperture 3, L1 gradient) and the depth-edge mask load_views builds from it
+                                   (:386-393); csrc/canny.hip, include/mi3d.h Part 12 states the arithmetic, which is
+                                   restated from memory: this project's contract, cv2 parity unpinned
   multidepth2point_mask            the novel views' points: coverage of the canonical cloud (refine.render_point), erosion,
                                    unprojection, the canonical-depth filter, z_buffer, colours
   build                            `load_views` for arrays already in memory at H x W
@@ -17,10 +20,11 @@ Inputs may be NumPy arrays or tensors; results are tensors on the GPU (float64 p
 3 x 3 and 4 x 4 inverses are taken on the host in NumPy float64.  There is no CPU path: a CPU device raises Mi3dError.
 
 Not comparable with the reference: the subset draw above `npoint` (torch.randperm under `generator`; the reference
-shuffles with NumPy's global state), the erosion's border (cv2 is on no machine this project builds on), and the Canny
-depth-edge mask, which is not restated (`edge_masks` takes its place if the caller has one).
+shuffles with NumPy's global state), and the erosion's border and the Canny detector's arithmetic (cv2 is on no machine
+this project builds on).  The depth-edge mask is opt-in (`depth_edges=True`); the default leaves it out, as before.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -30,6 +34,7 @@ from . import _lib
 from ._lib import Mi3dError
 
 MAX_SIDE, MAX_BOX = 16384, 31
+HYSTERESIS_SWEEPS = 8                   # sweeps per host read of `changed`: a sweep is a launch, the read is what costs
 FILES = ("vertices_cano.npy", "vertices_color_cano.npy", "vertices_novel.npy", "vertices_color_novel.npy")
 
 
@@ -238,6 +243,93 @@ def dilate(img, k, iterations=1, device=None):
     return _morph(img, k, iterations, True, device)
 
 
+# ----------------------------------------------------------------------------------------------------------- depth edges
+def _threshold(t, name):
+    """floor(t) as an int32; NaN is refused.  (No magnitude exceeds 2040: clamping to the int32 range changes nothing.)"""
+    t = float(t)
+    if math.isnan(t):
+        raise Mi3dError(f"{name} is NaN")
+    return int(min(max(math.floor(t) if math.isfinite(t) else t, -2.0 ** 31), 2.0 ** 31 - 1))
+
+
+def _gray(image, device, name="image"):
+    """uint8 [H, W], torch or NumPy -> a contiguous uint8 tensor on the GPU.  Any other dtype raises TypeError."""
+    if not isinstance(image, torch.Tensor):
+        image = np.asarray(image)
+    if str(image.dtype).replace("torch.", "") != "uint8":
+        raise TypeError(f"{name} must be uint8 (got {image.dtype}): quantise it first, as depth_edge_mask does")
+    if len(image.shape) != 2:
+        raise Mi3dError(f"a single-channel [H, W] image is expected (got {tuple(image.shape)})")
+    H, W = int(image.shape[0]), int(image.shape[1])
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise Mi3dError(f"H, W >= 1 and H * W < 2^31 are needed (got {H} x {W})")
+    dev = _device(device, image)
+    return _upload(image, torch.uint8, dev), H, W
+
+
+def canny_classify(image, threshold1, threshold2, device=None):
+    """mi3d_canny_classify: Sobel, magnitude, non-maximum suppression and the double threshold in one launch.  Returns
+    (cls uint8 [H, W]: 0 not an edge, 1 weak, 2 strong; counts int64 [2] = {weak, strong}), both on the GPU."""
+    low, high = _threshold(threshold1, "threshold1"), _threshold(threshold2, "threshold2")
+    img, H, W = _gray(image, device)
+    cls = torch.empty_like(img)
+    counts = torch.empty(2, dtype=torch.int64, device=img.device)
+    _lib.launch("mi3d_canny_classify", img, _lib.ptr(img), H, W, low, high, _lib.ptr(cls), _lib.ptr(counts))
+    return cls, counts
+
+
+def hysteresis(cls, sweeps=HYSTERESIS_SWEEPS, device=None):
+    """A class map (uint8 [H, W] of 0 / 1 / 2) -> its fixed point under "a weak pixel with a strong 8-neighbour becomes
+    strong", a new tensor.  mi3d_canny_hysteresis runs `sweeps` sweeps per call; the host reads `changed` after each call
+    and stops at 0.  The result depends on neither `sweeps` nor scheduling.  H * W sweeps always suffice: more calls than
+    that raise Mi3dError."""
+    sweeps = int(sweeps)
+    if sweeps < 1:
+        raise Mi3dError(f"sweeps must be at least 1 (got {sweeps})")
+    src, H, W = _gray(cls, device, "cls")
+    out = src.clone()
+    changed = torch.empty(1, dtype=torch.int32, device=out.device)
+    for _ in range(-(-H * W // sweeps) + 1):
+        _lib.launch("mi3d_canny_hysteresis", out, _lib.ptr(out), H, W, sweeps, _lib.ptr(changed))
+        if int(changed) == 0:                            # the one host read of a batch
+            return out
+    raise Mi3dError(f"hysteresis did not settle within {H * W} sweeps of a {H} x {W} map")
+
+
+def canny(image, threshold1, threshold2, device=None):
+    """cv2.Canny(image, threshold1, threshold2) with apertureSize=3, L2gradient=False, for a uint8 [H, W] image (torch or
+    NumPy; any other dtype raises TypeError): uint8 [H, W] of 0 / 255 on the GPU.  The arithmetic is include/mi3d.h Part
+    12's, restated from memory and this project's own contract: thresholds floored and swapped if out of order (NaN
+    raises), replicated borders, L1 magnitude, integer direction sectors.  One host read (the weak / strong counts); the
+    hysteresis is skipped when either count is 0 - with threshold1 == threshold2, the pipeline's case, no pixel is weak."""
+    cls, counts = canny_classify(image, threshold1, threshold2, device)
+    weak, strong = counts.tolist()
+    if weak and strong:
+        cls = hysteresis(cls)
+    return (cls == 2).to(torch.uint8) * 255
+
+
+def depth_edge_mask(depth, mask, threshold=10, k=11, device=None):
+    """refine_utils.py:386-393: bool [H, W] on the GPU, True within a k x k box of a Canny edge of the masked depth.
+    `v = depth * mask * 255.0` in float64, left to right; `np.uint8(v)` as the reference's platforms evaluate it:
+    truncation toward zero, then mod 256 (exact for every finite v; NumPy leaves an out-of-range conversion undefined);
+    a non-finite v gives 0.  Then canny(., threshold, threshold) and dilate(., k) == 255.
+    The quirk this inherits: the quantisation WRAPS above 256 / 255 = 1.004 scene units, so the reference also finds an
+    "edge" along that depth contour (and every further multiple); it is kept, because the default reproduces the
+    reference."""
+    dev = _device(device, depth, mask)
+    shape = tuple(depth.shape) if isinstance(depth, torch.Tensor) else np.shape(depth)
+    if len(shape) != 2:
+        raise Mi3dError(f"a single-channel [H, W] depth is expected (got {tuple(shape)})")
+    depth = _image(depth, shape, torch.float64, dev, "depth")
+    mask = _image(mask, shape, torch.float64, dev, "mask")
+    v = depth * mask * 255.0
+    v = torch.where(torch.isfinite(v), v, torch.zeros_like(v))
+    q = torch.fmod(torch.trunc(v), 256.0)                # exact; the sign of v
+    q = torch.where(q < 0, q + 256.0, q).to(torch.uint8)
+    return dilate(canny(q, threshold, threshold, device=dev), k, device=dev) == 255
+
+
 # ------------------------------------------------------------------------------------------------------- the novel views
 def _subset(n, npoint, generator, device):
     g_dev = generator.device if generator is not None else torch.device("cpu")
@@ -318,13 +410,16 @@ def cano_filter(v, cam, cano_c2w, cano_D, H, W, device=None):
 
 
 def build(ref_rgb, rgbs, depths, masks, c2ws, K, H, W, radius=2, ppp=8, edge_masks=None, device=None, npoint=1000000,
-          generator=None):
+          generator=None, depth_edges=False):
     """`load_views` (refine_utils.py:335-410) for views already in memory at H x W: rgbs [V, H, W, 3] in [0, 1], depths
     [V, H, W], masks [V, H, W] in [0, 1], c2ws [V, 4, 4], ref_rgb [H, W, 3] (the canonical view's colours).  Another size
     raises: cv2.resize is not restated.  The canonical view is (V - 1) // 2; its mask is eroded 11 x 11 twice and compared
-    `== 1`, the novel views' once.  The reference's Canny depth-edge mask is out of scope; `edge_masks` [V, H, W] (bool,
-    the canonical entry unused), if given, is removed from the novel masks where the reference removes its own.  Returns
-    (vertices_cano, vertices_color_cano, vertices_novel, vertices_color_novel)."""
+    `== 1`, the novel views' once.  `depth_edges=True` removes `depth_edge_mask(depth, eroded mask, 10, 11)` from every
+    novel view's mask, as the reference does (:386-395); the canonical view computes none (the reference computes one and
+    discards it, :360 is commented out).  `edge_masks` [V, H, W] (bool, the canonical entry unused), if given, is removed
+    from the novel masks too (with `depth_edges`: the union).  The default, `depth_edges=False`, leaves every output what
+    it was before the detector existed.  Returns (vertices_cano, vertices_color_cano, vertices_novel,
+    vertices_color_novel)."""
     H, W = _size(H, W)
     dev = _device(device, depths, masks, rgbs)
     V = int(depths.shape[0])
@@ -346,6 +441,8 @@ def build(ref_rgb, rgbs, depths, masks, c2ws, K, H, W, radius=2, ppp=8, edge_mas
     all_mask = []
     for i in novel:
         m = erode(masks[i], 11) == 1
+        if depth_edges:
+            m = m & ~depth_edge_mask(depths[i], m, 10, 11, device=dev)
         if edge_masks is not None:
             m = m & ~edge_masks[i]
         all_mask.append(m)
@@ -395,15 +492,17 @@ def render_views(model, poses, fov, H, W, **render_kwargs):
 
 
 def from_model(model, poses, fov, H, W, ref_rgb=None, radius=2, ppp=8, edge_masks=None, npoint=1000000, generator=None,
-               **render_kwargs):
+               depth_edges=False, **render_kwargs):
     """The trained field -> the four arrays: `render_views`, K as Trainer.refine builds it (nerf/utils.py:758-759), then
-    `build`.  `ref_rgb` [H, W, 3] colours the canonical view; without it the canonical render does."""
+    `build`.  `ref_rgb` [H, W, 3] colours the canonical view; without it the canonical render does.  `depth_edges` is
+    `build`'s: True drops the novel views' pixels on a depth discontinuity, as the reference does."""
     rgbs, depths, masks = render_views(model, poses, fov, H, W, **render_kwargs)
     if ref_rgb is None:
         ref_rgb = rgbs[(rgbs.shape[0] - 1) // 2]
     poses = poses.detach().cpu().numpy() if isinstance(poses, torch.Tensor) else np.asarray(poses)
     return build(ref_rgb, rgbs, depths, masks, poses.astype(np.float64), intrinsics(fov, H, W), H, W, radius=radius,
-                 ppp=ppp, edge_masks=edge_masks, device=rgbs.device, npoint=npoint, generator=generator)
+                 ppp=ppp, edge_masks=edge_masks, device=rgbs.device, npoint=npoint, generator=generator,
+                 depth_edges=depth_edges)
 
 
 def save(outputdir, vertices_cano, vertices_color_cano, vertices_novel, vertices_color_novel):

@@ -140,7 +140,9 @@ class NeRFRenderer(nn.Module):
         render) and the novel views' cloud on the GPU (mi3d.pointcloud), and `vertices_cano.npy`,
         `vertices_color_cano.npy`, `vertices_novel.npy`, `vertices_color_novel.npy` are written to `outputdir`.  Returns
         the four arrays as GPU tensors (float64 points, float32 colours): what refine_train_step takes as `points` and
-        `colour` once cast to float32.  `kwargs` go to pointcloud.from_model.  A CPU model raises Mi3dError."""
+        `colour` once cast to float32.  `kwargs` go to pointcloud.from_model: `depth_edges=True` removes the novel views'
+        pixels on a depth discontinuity (the reference's Canny depth-edge mask; off by default).  A CPU model raises
+        Mi3dError."""
         from . import pointcloud
         out = pointcloud.from_model(self, poses, fov, H, W, ref_rgb=ref_rgb, **kwargs)
         pointcloud.save(outputdir, *out)

@@ -8,7 +8,11 @@ read by the host inside it), zmin + visible, one 15 x 15 erosion, canonical filt
 canonical cloud - and `build` end to end by wall clock, median of 3.  `bytes` = what a stage must move at least.
 --reference: wall time of the reference's OWN z_buffer and depth2point (oracle.ref_import) on ONE view of the same size,
 on the CPU of the build container, once each - two Python loops over every point.  The parent commit has no number to
-compare with: it cannot do this at all.  Both runs merge their keys into --out."""
+compare with: it cannot do this at all.  Both runs merge their keys into --out.
+The GPU run also writes `depth_edges` (the Canny depth-edge mask, mi3d.h Part 12), same clock and repeats: classify on the
+novel view's quantised depth, one batch of hysteresis sweeps on the 40 / 120 classes of a noisy image (a copy of the class
+map is part of the timed work: the sweeps are in place), `depth_edge_mask` whole (10 / 10: no weak pixel, so no
+hysteresis; one host read), and `build` with and without `depth_edges` by wall clock."""
 import argparse
 import importlib.util
 import json
@@ -143,6 +147,53 @@ def gpu(a):
            "stages_one_novel_view": st}
     print(json.dumps(res, indent=1))
     merge(a.out, "mi355x", res)
+
+    # ---- the Canny depth-edge mask
+    m = pc.erode(mask_f, 11) == 1
+    q = (D * m * 255.0).trunc().to(torch.int64).remainder(256).to(torch.uint8)
+    cls_q, counts_q = pc.canny_classify(q, 10, 10)
+    y, x = np.mgrid[:H, :W]
+    noisy = np.clip(128 + 100 * np.sin(x / 5) * np.cos(y / 7) + np.random.default_rng(0).integers(-6, 7, (H, W)), 0, 255)
+    noisy = torch.from_numpy(noisy.astype(np.uint8)).to(dev)
+    cls_n, counts_n = pc.canny_classify(noisy, 40, 120)
+    work, flag = torch.empty_like(cls_n), torch.empty(1, dtype=torch.int32, device=dev)
+
+    def batch():
+        work.copy_(cls_n)
+        pc._lib.launch("mi3d_canny_hysteresis", work, pc._lib.ptr(work), H, W, pc.HYSTERESIS_SWEEPS, pc._lib.ptr(flag))
+
+    calls = []
+    orig = pc._lib.launch
+    pc._lib.launch = lambda name, *args: (calls.append(name), orig(name, *args))[1]
+    try:
+        settled = pc.hysteresis(cls_n)
+    finally:
+        pc._lib.launch = orig
+    de = {"quantised_depth": {"weak_strong": counts_q.tolist(), "edge_pixels": int((cls_q == 2).sum())},
+          "noisy_image_40_120": {"weak_strong": counts_n.tolist(), "strong_after_hysteresis": int((settled == 2).sum()),
+                                 "host_batches_to_settle": len(calls), "sweeps_per_batch": pc.HYSTERESIS_SWEEPS}}
+    de["classify"] = dict(timed(lambda: pc.canny_classify(q, 10, 10)), bytes=px * 2,
+                          note="includes the in-stream zeroing of the counts and the allocation of the outputs")
+    de["hysteresis_batch"] = dict(timed(batch), bytes=px * 2 * (pc.HYSTERESIS_SWEEPS + 1),
+                                  note="a copy of the class map, then one call of HYSTERESIS_SWEEPS sweeps; no host read")
+    de["depth_edge_mask"] = dict(timed(lambda: pc.depth_edge_mask(D, m, 10, 11)),
+                                 note="quantisation (torch ops), classify, the host's read of the counts, 11 x 11 dilation")
+    for name in ("classify", "hysteresis_batch"):
+        de[name]["hbm_share"] = de[name]["bytes"] / (de[name]["ms_median"] * 1e-3) / HBM_PEAK
+    for key, flagged in (("build_without_depth_edges", False), ("build_with_depth_edges", True)):
+        ts = []
+        for r in range(4):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = pc.build(rgbs[ind], rgbs, depths, masks, c2ws, K, H, W, device=dev, depth_edges=flagged)
+            torch.cuda.synchronize()
+            if r:
+                ts.append(1e3 * (time.perf_counter() - t0))
+        de[key] = {"ms_median": statistics.median(ts), "ms_min": min(ts), "repeats": len(ts), "clock": "wall",
+                   "views": a.views, "rows": [int(t.shape[0]) for t in out]}
+    de = {"device": torch.cuda.get_device_name(dev), "side": a.side, "views": a.views, **de}
+    print(json.dumps(de, indent=1))
+    merge(a.out, "depth_edges", de)
 
 
 def main():
