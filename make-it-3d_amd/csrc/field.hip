@@ -34,31 +34,6 @@
 #ifndef MI3D_MLP_LDS_TRANSPOSE
 #define MI3D_MLP_LDS_TRANSPOSE 1
 #endif
-// development switches of the backward (variant builds, tools/build_dev.py): an instance of its own for the full input
-// width; the next tile's rows requested late in the tile (after the last use of this tile's) instead of at its top
-#ifndef MI3D_MLP_BWD_FULL
-#define MI3D_MLP_BWD_FULL 1
-#endif
-#ifndef MI3D_MLP_BWD_LATE_PREFETCH
-#define MI3D_MLP_BWD_LATE_PREFETCH 1
-#endif
-// TIMING ONLY (variant builds for tools/mlp_ab.py --timing-only; the gradients are wrong with either bit): what a group of
-// the backward's vector instructions costs - 1 = no bias-gradient sums (40 dot products per tile), 2 = no ReLU masks on
-// the gradients (64 packed operations per tile); 4 (round 6) = recompute + input gradient ONLY, in the
-// "lane = sample" orientation throughout (14 matrix products per tile, no transposes, no weight-gradient registers) at
-// THREE waves per SIMD: what a producer wave of a producer / consumer pair could at best cost (the input-gradient planes
-// of this build are correct, every weight gradient is zero)
-#ifndef MI3D_MLP_DO_LDS
-// the 4-wide output gradient's tile turned round through the wave's LDS like every other binary16 tile, instead of on the
-// matrix core (VERDICT r04 item 3 / DESIGN.md 7.3a): 42 MFMAs and 72 packed converts per tile instead of 43 / 80.  Both
-// builds in one process (tools/mlp_ab.py, profiles/mlp_ab_r05_do_lds.json): every template instance's input-gradient
-// planes bit-identical, weight gradients to 1.5e-6 (the order of their float atomics); 13 points 8.37 -> 8.34 ms, point-0
-// pass 0.71 -> 0.71: the last matrix-core transpose of the binary16 kernels is gone, the time it took was already hidden.
-#define MI3D_MLP_DO_LDS 1
-#endif
-#ifndef MI3D_MLP_BWD_TIMING_CUT
-#define MI3D_MLP_BWD_TIMING_CUT 0
-#endif
 
 namespace {
 
@@ -259,7 +234,6 @@ enum : int {
     B_W1T = B_W2T + NTH * NTH, // [tk]  N = input feature, K = hidden-1 feature (D)      W1[K][N]
     B_ID = B_W1T + NTH,    //           N = index j, K = index k (X): (j == k) - as the B operand of a tile held
                            //           "lane = sample" it hands back the tile "lane = index" (a transpose on the matrix core)
-    B_FWD_COUNT = B_W3T,
     B_ALL_COUNT = B_ID + 1,
 };
 
@@ -367,13 +341,6 @@ template <class P> __device__ __forceinline__ typename P::KB rows_kb_half(const 
     for (int j = 0; j < 8; ++j) P::set_pair_bits(k, j, u[j]);
     return k;
 }
-template <class P>
-__device__ __forceinline__ typename P::KB load_rows_kb(const float *__restrict__ x, size_t row, size_t n, int h,
-                                                       size_t plane_rows, int planes_half) {
-    float raw[16];
-    load_rows_raw(x, row, n, h, plane_rows, raw, planes_half);
-    return rows_kb<P>(raw);
-}
 
 // [rows,4] output-side gradient as a K-block (kind X over the 4 outputs): only lane-half 0, q < 4 are non-zero
 // (the zeroing of rows past n and of lane-half 1 happens at the use, one iteration after the load was issued)
@@ -400,53 +367,6 @@ __device__ __forceinline__ f32x16 bias_rows(const float *bias, int h) {
     for (int q = 0; q < 16; ++q) a[q] = bias[rowmap(q, h)];
     return a;
 }
-// ---------------------------------------------------------------- forward
-template <class P>
-__global__ __launch_bounds__(kWave *kWavesPerWG, 2) void k_mlp_forward(const float *__restrict__ x, uint32_t x_planes, int x_half,
-                                                                     uint32_t n, Weights w, float *__restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    float *bias = reinterpret_cast<float *>(lds + (size_t)B_FWD_COUNT * block_bytes<P>());
-    build_blocks<P>(lds, bias, w, B_FWD_COUNT);
-    __syncthreads();
-    const int lane = threadIdx.x & (kWave - 1), p = lane & 31, h = lane >> 5;
-    const uint32_t wave = blockIdx.x * kWavesPerWG + threadIdx.x / kWave, n_waves = gridDim.x * kWavesPerWG;
-    const uint32_t n_tiles = (n + 31) / 32;
-    // the lane offset is laundered through an empty asm so every use is a fresh LDS read: hipcc would otherwise
-    // hoist all (loop-invariant) operand blocks into registers and spill the accumulators
-    auto blk = [&](int b) {
-        int l = lane;
-        asm volatile("" : "+v"(l));
-        return P::load_block(lds + (size_t)b * block_bytes<P>(), l);
-    };
-
-    for (uint32_t tile = wave; tile < n_tiles; tile += n_waves) {
-        const size_t row = (size_t)tile * 32 + p;
-        const bool valid = row < n;
-        const typename P::KB X = load_rows_kb<P>(x, row, n, h, x_planes, x_half);
-        typename P::KB H1[NTH], H2[NTH];
-#pragma unroll
-        for (int t = 0; t < NTH; ++t) {
-            f32x16 acc = bias_rows(bias + 32 * t, h);
-            P::mma(acc, blk(B_W1 + t), X);
-            H1[t] = P::relu(acc);
-        }
-#pragma unroll
-        for (int t = 0; t < NTH; ++t) {
-            f32x16 acc = bias_rows(bias + HID + 32 * t, h);
-#pragma unroll
-            for (int tk = 0; tk < NTH; ++tk) P::mma(acc, blk(B_W2 + t * NTH + tk), H1[tk]);
-            H2[t] = P::relu(acc);
-        }
-        f32x16 acc = bias_rows(bias + 2 * HID, h);
-#pragma unroll
-        for (int tk = 0; tk < NTH; ++tk) P::mma(acc, blk(B_W3 + tk), H2[tk]);
-        if (valid && h == 0) {  // rows 0..3 of the tile = the four outputs, held by lane-half 0 in registers 0..3
-            f32x4 o = {P::round(acc[0]), P::round(acc[1]), P::round(acc[2]), P::round(acc[3])};
-            __builtin_nontemporal_store(o, reinterpret_cast<f32x4 *>(out + row * DOUT));
-        }
-    }
-}
-
 // ---------------------------------------------------------------- backward
 struct Grads {
     float *dW1, *db1, *dW2, *db2, *dW3, *db3;
@@ -997,7 +917,7 @@ __global__ __launch_bounds__(kWave *kWavesPerWG, 2) void k_mlp_fwd_g(const float
     const int lane = threadIdx.x & (kWave - 1), p = lane & 31, h = lane >> 5;
     const uint32_t wave = blockIdx.x * kWavesPerWG + threadIdx.x / kWave, n_waves = gridDim.x * kWavesPerWG;
     const uint32_t n_tiles = (n + 31) / 32;
-    auto blk = [&](int b) {  // fresh LDS read at every use (see k_mlp_forward)
+    auto blk = [&](int b) {  // fresh LDS read at every use (see k_mlp_backward)
         int l = lane;
         asm volatile("" : "+v"(l));
         return P::load_block(lds + (size_t)b * block_bytes<P>(), l);
@@ -1061,7 +981,7 @@ __global__ __launch_bounds__(kWave *kWavesPerWG, 2) void k_mlp_fwd_g(const float
 // x and dx carry no __restrict__ in the backward kernels: mi3d.h lets dx BE x (same layout), and the product calls it so.
 // (Register counts and scratch of every instance are the same with and without the qualifier - hipcc 7.2, gfx950.)
 template <class P, int NTH, int LAYERS, bool HP, bool FULL>   // FULL: dim_in = 32 (plane indices and store guards constant)
-__global__ __launch_bounds__(kWave *kWavesPerWG, (MI3D_MLP_BWD_TIMING_CUT & 4) ? 3 : 2) void k_mlp_bwd_g(const float *x, uint32_t x_planes,
+__global__ __launch_bounds__(kWave *kWavesPerWG, 2) void k_mlp_bwd_g(const float *x, uint32_t x_planes,
                                                                         const float *__restrict__ dout, uint32_t n,
                                                                         uint32_t din, Weights w, float *dx,
                                                                         uint32_t dx_planes, Grads g) {
@@ -1152,14 +1072,13 @@ __global__ __launch_bounds__(kWave *kWavesPerWG, (MI3D_MLP_BWD_TIMING_CUT & 4) ?
                 dor = load_dout_raw(dout, rn, n);
             }
         };
-        constexpr bool late_prefetch = P::kLdsTranspose && HP && MI3D_MLP_BWD_LATE_PREFETCH != 0;
+        constexpr bool late_prefetch = P::kLdsTranspose && HP;
         if constexpr (!late_prefetch) prefetch();
         // ---- forward recompute, lane = sample (the activations double as their own ReLU masks).  The order below keeps
         // the live set small (it is what decides spills at 256 registers): every orientation-1 tile is transposed
         // as soon as its last orientation-1 use is over, and the hidden-1 gradient is formed directly in orientation 2,
         // where its mask (the transposed activations) already is.
         KB H1p[NTH], HL[NTH];
-        KB dgH1[(MI3D_MLP_BWD_TIMING_CUT & 4) ? NTH : 1];   // (timing cut 4: hidden 1 kept in the "lane = sample" orientation)
         {
             KB H1[NTH];
 #pragma unroll
@@ -1167,7 +1086,6 @@ __global__ __launch_bounds__(kWave *kWavesPerWG, (MI3D_MLP_BWD_TIMING_CUT & 4) ?
                 f32x16 acc = bias(t);
                 P::mma(acc, blk(B::W1 + t), X);
                 H1[t] = P::relu(acc);
-                if constexpr ((MI3D_MLP_BWD_TIMING_CUT & 4) != 0) dgH1[t] = H1[t];
             }
             if constexpr (LAYERS == 3) {
 #pragma unroll
@@ -1181,10 +1099,8 @@ __global__ __launch_bounds__(kWave *kWavesPerWG, (MI3D_MLP_BWD_TIMING_CUT & 4) ?
 #pragma unroll
                 for (int t = 0; t < NTH; ++t) HL[t] = H1[t];
             }
-            if constexpr ((MI3D_MLP_BWD_TIMING_CUT & 4) == 0) {
 #pragma unroll
             for (int t = 0; t < NTH; ++t) H1p[t] = transpose(H1[t], B::IDD);  // lane = hidden-1 feature, values = samples
-            }
         }
         // ---- gradient wrt the last hidden layer (lane = sample); dW_last and db_last from the transposed operands
         KB dHL[NTH];
@@ -1192,48 +1108,18 @@ __global__ __launch_bounds__(kWave *kWavesPerWG, (MI3D_MLP_BWD_TIMING_CUT & 4) ?
         for (int t = 0; t < NTH; ++t) {
             f32x16 acc = splat(0.f);
             P::mma_lo(acc, blk(B::W3T + t), dO);
-            dHL[t] = (MI3D_MLP_BWD_TIMING_CUT & 2) ? P::cast(acc) : P::masked(acc, HL[t]);
-        }
-        if constexpr ((MI3D_MLP_BWD_TIMING_CUT & 4) != 0) {
-            // recompute + dgrad only: dH1 = relu'(H1) (W2^T dH2) with the W2T block as the A operand (rows = hidden-1
-            // feature, lane = sample - the layout H1 has), then dX = W1^T dH1
-            if constexpr (late_prefetch) prefetch();
-            f32x16 accx = splat(0.f);
-#pragma unroll
-            for (int t = 0; t < NTH; ++t) {
-                KB dH1;
-                if constexpr (LAYERS == 3) {
-                    f32x16 acc = splat(0.f);
-#pragma unroll
-                    for (int tk = 0; tk < NTH; ++tk) P::mma(acc, blk(B::W2T + t * NTH + tk), dHL[tk]);
-                    dH1 = P::masked(acc, dgH1[t]);
-                } else {
-                    dH1 = dHL[t];
-                }
-                P::mma(accx, blk(B::W1T + t), dH1);
-            }
-            if constexpr (HP) {
-                if (valid) {
-                    uint32_t *dst = reinterpret_cast<uint32_t *>(dx) + row + (size_t)(2 * h) * dxp;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        dst[(size_t)(4 * c) * dxp] = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){accx[4 * c], accx[4 * c + 1]}, half2v));
-                        dst[(size_t)(4 * c + 1) * dxp] = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){accx[4 * c + 2], accx[4 * c + 3]}, half2v));
-                    }
-                }
-            }
-            continue;
+            dHL[t] = P::masked(acc, HL[t]);
         }
         {
             KB dOp;   // lane = output index, values = the tile's samples
-            if constexpr (P::kLdsTranspose && MI3D_MLP_DO_LDS != 0) {
-                dOp = transpose(dO, B::IDX);   // (kind X over the 4 outputs: through the wave's LDS like every other tile)
+            if constexpr (P::kLdsTranspose) {
+                dOp = transpose(dO, B::IDX);   // (kind X over the 4 outputs: through the wave's LDS like every other tile, DESIGN.md A.11)
             } else {
                 f32x16 tO = splat(0.f);
                 P::mma_lo(tO, dO, blk_fresh(B::IDX));
                 dOp = P::cast(tO);
             }
-            if (!(MI3D_MLP_BWD_TIMING_CUT & 1)) gb3 += P::sum(dOp);
+            gb3 += P::sum(dOp);
 #pragma unroll
             for (int t = 0; t < NTH; ++t) {
                 const KB HLp = LAYERS == 3 ? transpose(HL[t], B::IDD) : H1p[t];
@@ -1245,7 +1131,7 @@ __global__ __launch_bounds__(kWave *kWavesPerWG, (MI3D_MLP_BWD_TIMING_CUT & 4) ?
 #pragma unroll
             for (int ti = 0; ti < NTH; ++ti) {   // dW2[i][j] += sum_s dH2[s][i] H1[s][j]
                 const KB dHLp = transpose(dHL[ti], B::IDD);
-                if (!(MI3D_MLP_BWD_TIMING_CUT & 1)) gb2[ti] += P::sum(dHLp);
+                gb2[ti] += P::sum(dHLp);
 #pragma unroll
                 for (int tj = 0; tj < NTH; ++tj) P::mma(gW2[ti][tj], dHLp, H1p[tj]);
             }
@@ -1254,7 +1140,7 @@ __global__ __launch_bounds__(kWave *kWavesPerWG, (MI3D_MLP_BWD_TIMING_CUT & 4) ?
                 f32x16 acc = splat(0.f);
 #pragma unroll
                 for (int tk = 0; tk < NTH; ++tk) P::mma(acc, dHL[tk], blk(B::W2T + t * NTH + tk));
-                dH1p[t] = (MI3D_MLP_BWD_TIMING_CUT & 2) ? P::cast(acc) : P::masked(acc, H1p[t]);
+                dH1p[t] = P::masked(acc, H1p[t]);
             }
         } else {
 #pragma unroll
@@ -1265,7 +1151,7 @@ __global__ __launch_bounds__(kWave *kWavesPerWG, (MI3D_MLP_BWD_TIMING_CUT & 4) ?
             if constexpr (late_prefetch) prefetch();   // (this tile's rows are dead: the next tile's land in their registers)
 #pragma unroll
             for (int t = 0; t < NTH; ++t) {
-                if (!(MI3D_MLP_BWD_TIMING_CUT & 1)) gb1[t] += P::sum(dH1p[t]);
+                gb1[t] += P::sum(dH1p[t]);
                 P::mma(gW1[t], dH1p[t], Xp);
             }
         }
@@ -1549,8 +1435,8 @@ void launch_bwd(dim3 grid, hipStream_t st, const float *x, uint32_t x_planes, co
                 const Weights &w, float *dx, uint32_t dx_planes, const Grads &g) {
     using B = Blk<NTH, LAYERS>;
     // (binary16 planes at the full input width get their own instance: constant plane indices, no store guards)
-    if (MI3D_MLP_BWD_FULL != 0 && HP && P::kLdsTranspose && din == (uint32_t)DIN)
-        hipLaunchKernelGGL((k_mlp_bwd_g<P, NTH, LAYERS, HP, MI3D_MLP_BWD_FULL != 0 && HP && P::kLdsTranspose>), grid, dim3(kWave * kWavesPerWG),
+    if (HP && P::kLdsTranspose && din == (uint32_t)DIN)
+        hipLaunchKernelGGL((k_mlp_bwd_g<P, NTH, LAYERS, HP, HP && P::kLdsTranspose>), grid, dim3(kWave * kWavesPerWG),
                            lds_bytes_g<P>(B::ALL_COUNT, B::BIAS_TILES, true), st, x, x_planes, dout, n, din, w, dx, dx_planes, g);
     else
         hipLaunchKernelGGL((k_mlp_bwd_g<P, NTH, LAYERS, HP, false>), grid, dim3(kWave * kWavesPerWG),
@@ -1596,18 +1482,6 @@ int mi3d_mlp_forward_counted(const void *xv, uint32_t x_plane_rows, int planes_h
     const int nth = (int)dim_hidden / 32;
     hipStream_t st = as_stream(stream);
     const dim3 grid(grid_for(n, MI3D_TUNE(MI3D_T_MLP_FWD_WGS_PER_CU, 5)));
-#ifdef MI3D_DEV
-    if (MI3D_TUNE(MI3D_T_MLP_BWD_VARIANT, 0) == 3 && nth == 2 && layers == 3 && dim_in == (uint32_t)DIN) {  // round 2's kernel
-        const dim3 g2(grid_for(n, 2));
-        if (half_mode)
-            hipLaunchKernelGGL(k_mlp_forward<F16>, g2, dim3(kWave * kWavesPerWG), lds_bytes<F16>(B_FWD_COUNT), st, x,
-                               x_plane_rows, planes_half, n, w, out);
-        else
-            hipLaunchKernelGGL(k_mlp_forward<F32>, g2, dim3(kWave * kWavesPerWG), lds_bytes<F32>(B_FWD_COUNT), st, x,
-                               x_plane_rows, planes_half, n, w, out);
-        return (int)hipGetLastError();
-    }
-#endif
     if (half_mode && planes_half) MI3D_MLP_DISPATCH(launch_fwd, F16, true, nth, layers, grid, st, x, x_plane_rows, n, dim_in, w, out, count, n_stride);
     else if (half_mode) MI3D_MLP_DISPATCH(launch_fwd, F16, false, nth, layers, grid, st, x, x_plane_rows, n, dim_in, w, out, count, n_stride);
     else MI3D_MLP_DISPATCH(launch_fwd, F32, false, nth, layers, grid, st, x, x_plane_rows, n, dim_in, w, out, count, n_stride);
@@ -1634,20 +1508,9 @@ int mi3d_mlp_backward(const void *xv, uint32_t x_plane_rows, int planes_half, co
     const Weights w{W1, b1, W2, b2, W3, b3};
     const Grads g{dW1, db1, dW2, db2, dW3, db3};
     const int nth = (int)dim_hidden / 32;
-    const dim3 grid(grid_for(n, MI3D_TUNE(MI3D_T_MLP_WGS_PER_CU, (MI3D_MLP_BWD_TIMING_CUT & 4) ? 3 : 2))), block(kWave * kWavesPerWG);
+    const dim3 grid(grid_for(n, MI3D_TUNE(MI3D_T_MLP_WGS_PER_CU, 2))), block(kWave * kWavesPerWG);
     hipStream_t st = as_stream(stream);
     const bool classic = nth == 2 && layers == 3 && dim_in == (uint32_t)DIN;
-#ifdef MI3D_DEV
-    if (half_mode && classic && MI3D_TUNE(MI3D_T_MLP_BWD_VARIANT, 0) == 3) {  // round 2's kernel (one wave per SIMD, staged)
-        if (planes_half)
-            hipLaunchKernelGGL((k_mlp_backward<F16, 2, 1, true>), grid, block, lds_bytes<F16>(B_ALL_COUNT), st, x, x_plane_rows, 1,
-                               dout, n, w, dx, dx_plane_rows, g);
-        else
-            hipLaunchKernelGGL((k_mlp_backward<F16, 2, 1, false>), grid, block, lds_bytes<F16>(B_ALL_COUNT), st, x, x_plane_rows, 0,
-                               dout, n, w, dx, dx_plane_rows, g);
-        return (int)hipGetLastError();
-    }
-#endif
     if (half_mode && planes_half)
         MI3D_MLP_DISPATCH(launch_bwd, F16, true, nth, layers, grid, st, x, x_plane_rows, dout, n, dim_in, w, dx, dx_plane_rows, g);
     else if (half_mode)

@@ -196,20 +196,11 @@ __global__ __launch_bounds__(kWave *kWaves) void k_grid_encode(PointSet ps, uint
 // coarse levels, where it applies, are served by the L1 anyway and the extra compares made them 5-15 % slower).
 constexpr uint32_t kXcds = 8;
 constexpr int kMaxSegs = 16;
-#ifndef MI3D_ENCODE_TRIPLE
-// x-group evaluation on the fine hashed levels in a kernel instance of their own (encode_group_hash; VERDICT round 4 item 4:
-// "the x-triple row sharing").  Measured in round 5 (tools/kbench.py --what encode_r05, profiles/kbench_r05_encode_xgroup.json),
-// bit-identical planes: per level 1.44 -> 1.35 ms (level 9), 1.87 -> 1.75 (10), 2.33 -> 2.24 (11), 2.69 -> 2.65 (12), nothing from
-// level 13 on - 0.45 ms over all levels, less than the second launch costs (whole gather 22.3 -> 22.5-23.0 ms).  The fine
-// levels do not speed up in proportion to the lines they no longer ask for: NOT taken; the tools build keeps the switch.
-#define MI3D_ENCODE_TRIPLE 0
-#endif
 
 struct EncodeSeg { uint32_t level, tile0, tile1, wgs; };  // wgs: workgroups of the XCD that walk this segment
 struct EncodePlan {
     uint32_t n_seg[kXcds];
     EncodeSeg seg[kXcds][kMaxSegs];
-    uint32_t shared;   // 1: every XCD walks the SAME list - whole levels, in order - and all claim from one counter per level
 };
 
 template <bool PAIR>
@@ -278,27 +269,8 @@ __host__ __device__ __forceinline__ LevelFast level_fast(const GridLevel &L, int
 }
 struct __attribute__((packed, aligned(8))) EntryPair { float ax, ay, bx, by; };  // entries e, e + 1 of a level
 
-#ifndef MI3D_MUL24
-// Tried in round 6 and NOT taken (0): 24-bit multiplies in the emit.  The emit is bound by vector-instruction issue, and a
-// 32-bit integer multiply (v_mul_lo_u32) was assumed to hold the issue port four times as long as v_mul_u32_u24.  (1) The
-// gather table's slot hash - eight multiplies per table pass, ~40 per (tile, level) of the coarse role - by one 24-bit
-// product; (2) the spatial hash's c * prime (needed exactly mod 2^32) as two signed 24-bit products of the prime's halves,
-// c * (prime & 0x7FFFFF) + ((c * (prime >> 23)) << 23), three instructions.  Same entries, same gradient (7e-8 x max: the order
-// of the table's float atomics).  Product-grade builds in one process on one arena, four interleaved rounds
-// (profiles/scatter_ab_libs_r06_mul24.json): dense 49.83 -> 50.05 ms, real census 39.79 -> 40.28: slightly SLOWER - the 32-bit
-// multiplies are not what the issue port waits for (consistent with MI3D_TIMING_FAKE_PASS1's small ceiling).
-#define MI3D_MUL24 0
-#endif
-__device__ __forceinline__ uint32_t mul_prime(uint32_t c, uint32_t prime, bool c_fits_24) {
-    // (SIGNED 24-bit products with the prime split at bit 23: a coordinate may be base - 1 = 0xFFFFFFFF at the box's lower
-    //  face, and -1 * prime mod 2^32 comes out right this way; `c_fits_24` - uniform - says every coordinate of the level
-    //  lies in [-2^23, 2^23))
-    if (MI3D_MUL24 != 0 && c_fits_24)
-        return (uint32_t)__mul24((int)c, (int)(prime & 0x7FFFFFu)) + ((uint32_t)__mul24((int)c, (int)(prime >> 23)) << 23);
-    return c * prime;
-}
+// (24-bit multiplies for the spatial hash and the gather table's slot hash: tried in round 6, slightly slower - DESIGN.md 3.2, A.11)
 __device__ __forceinline__ uint32_t merge_slot(uint32_t e) {   // 9-bit slot of the per-wave gather table (kMergeSlots = 512)
-    if (MI3D_MUL24 != 0) return (__umul24(e, 0x9E3779u) >> 14) & 511u;
     return (e * 2654435761u) >> (32 - 9);
 }
 
@@ -307,8 +279,7 @@ __device__ __forceinline__ uint32_t merge_slot(uint32_t e) {   // 9-bit slot of 
 __device__ __forceinline__ void corner_entries4(const GridLevel &L, const LevelFast &F, uint32_t cx, uint32_t cy,
                                                 uint32_t cz, uint32_t zb, uint32_t (&e)[4]) {
     if (F.kind == kHashPow2) {
-        const bool f24 = (L.res >> 22) == 0u;   // (cells <= res + 1 < 2^23)
-        const uint32_t hy = mul_prime(cy, kPrimeY, f24), hz = mul_prime(cz + zb, kPrimeZ, f24), a = hy ^ hz, b = (hy + kPrimeY) ^ hz, cx1 = cx + 1u;
+        const uint32_t hy = cy * kPrimeY, hz = (cz + zb) * kPrimeZ, a = hy ^ hz, b = (hy + kPrimeY) ^ hz, cx1 = cx + 1u;
         e[0] = (a ^ cx) & F.last; e[1] = (a ^ cx1) & F.last; e[2] = (b ^ cx) & F.last; e[3] = (b ^ cx1) & F.last;
         return;
     }
@@ -323,10 +294,7 @@ __device__ __forceinline__ void corner_entries4(const GridLevel &L, const LevelF
 
 // one corner's entry by the same routes
 __device__ __forceinline__ uint32_t corner_entry1(const GridLevel &L, const LevelFast &F, uint32_t x, uint32_t y, uint32_t z) {
-    if (F.kind == kHashPow2) {
-        const bool f24 = (L.res >> 22) == 0u;   // (uniform; the coordinates lie in [-1, res + 1])
-        return (x ^ mul_prime(y, kPrimeY, f24) ^ mul_prime(z, kPrimeZ, f24)) & F.last;
-    }
+    if (F.kind == kHashPow2) return (x ^ (y * kPrimeY) ^ (z * kPrimeZ)) & F.last;
     if (F.kind == kDense3) {
         const uint32_t a = x + __umul24(y, L.res) + __umul24(z, F.res2), size = F.last + 1u;
         return min(a, a - size);
@@ -384,93 +352,15 @@ __device__ __forceinline__ bool gather_corners_fast(const GridLevel &L, const Le
     return true;
 }
 
-// Stencil points that differ in their x offset only - the sample, its +x and its -x neighbour; the +x / -x pair around the
-// jittered position - have the SAME (y, z) rows on a hashed level: entry = (cx ^ row hash) & mask, and cx +- a few cells
-// changes the low bits only, so the three points' corners of a row lie in the same 128-byte line (16 entries) with
-// probability ~ 1 - d / 16 for d cells of epsilon (level 11: 0.82, level 13: 0.67, level 15: 0.37).  Evaluated one point
-// at a time those lines are fetched from the L2 once PER POINT (a wave's 64 lanes touch ~32 KB of lines per point, twelve
-// waves share a 32 KB L1: nothing survives from one point to the next), and the fine levels are bound by exactly that,
-// the L2 -> L1 line rate.  Here the points of such a group are evaluated TOGETHER, row by row, the loads
-// of one row issued back to back: a request for a line whose miss is still pending merges with it (the mechanism the
-// straddling x + 1 corner already uses, ORDER above).  Same cells, same weights, same order of the fused multiply-adds per
-// point: the planes are bit-identical; the row hash and the (y, z) cell are computed once per group.
-template <bool NT>
-__device__ __forceinline__ void encode_group_hash(const PointSet &ps, const float (&base)[2][3], const GridLevel &L,
-                                                  const LevelFast &F, const float2 *__restrict__ lvl,
-                                                  float *__restrict__ planes, int out_half, size_t plane0, uint32_t n,
-                                                  uint32_t s, uint32_t p, uint32_t g /* 2 or 3, uniform */) {
-    uint32_t cx[3], cy = 0, cz = 0;
-    float fx[3], fy = 0.f, fz = 0.f;
-#pragma unroll
-    for (uint32_t i = 0; i < 3; ++i) {
-        if (i < g) {
-            float q[3];
-            point_of(ps, base, p + i, ps.offs[p + i], q);
-            grid_cell(q[0], L.scale, cx[i], fx[i]);
-            if (i == 0) { grid_cell(q[1], L.scale, cy, fy); grid_cell(q[2], L.scale, cz, fz); }   // (equal for the whole group)
-        } else { cx[i] = 0; fx[i] = 0.f; }
-    }
-    const uint32_t hy = cy * kPrimeY, hz = cz * kPrimeZ, hy1 = hy + kPrimeY, hz1 = hz + kPrimeZ;
-    const uint32_t yz[4] = {hy ^ hz, hy1 ^ hz, hy ^ hz1, hy1 ^ hz1};
-    const uint32_t slot_mask = F.last & ~1u;
-    float4 t[3][4];
-    float2 u[3][4];
-#pragma unroll
-    for (uint32_t j = 0; j < 4; ++j) {
-#pragma unroll
-        for (uint32_t i = 0; i < 3; ++i) {
-            if (i < g) {
-                t[i][j] = *reinterpret_cast<const float4 *>(lvl + ((yz[j] ^ cx[i]) & slot_mask));
-                if (cx[i] & 1u) u[i][j] = lvl[(yz[j] ^ (cx[i] + 1u)) & F.last];
-            }
-        }
-    }
-    const float gy = 1.0f - fy, gz = 1.0f - fz;
-#pragma unroll
-    for (uint32_t i = 0; i < 3; ++i) {
-        if (i < g) {
-            const bool cx_odd = cx[i] & 1u;
-            float2 v[8];
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) {
-                const bool e0_odd = (yz[j] ^ cx[i]) & 1u;
-                const float2 lo = make_float2(t[i][j].x, t[i][j].y), hi = make_float2(t[i][j].z, t[i][j].w);
-                v[2 * j] = e0_odd ? hi : lo;
-                v[2 * j + 1] = cx_odd ? u[i][j] : (e0_odd ? lo : hi);
-            }
-            const float gx = 1.0f - fx[i];
-            // weights in tcnn's multiplication order ((1 * wx) * wy) * wz, corners accumulated in its order (encode_points)
-            const float w00 = gx * gy, w10 = fx[i] * gy, w01 = gx * fy, w11 = fx[i] * fy;
-            const float w[8] = {w00 * gz, w10 * gz, w01 * gz, w11 * gz, w00 * fz, w10 * fz, w01 * fz, w11 * fz};
-            float r0 = 0.f, r1 = 0.f;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { r0 += w[k] * v[k].x; r1 += w[k] * v[k].y; }
-            store_plane_pair<NT>(planes, out_half, plane0 + (size_t)(p + i) * n + s, r0, r1);
-        }
-    }
-}
-
-// one (tile, level): the P points of the lane's sample -> plane pairs
-template <int KIND, bool PAIR, bool NT, bool TRIPLE = false>
+// one (tile, level): the P points of the lane's sample -> plane pairs.  (Evaluating the points that differ in their x offset
+// only together, row by row, so that their loads merge in the L1: tried in round 5, bit-identical, not faster - DESIGN.md A.2)
+template <int KIND, bool PAIR, bool NT>
 __device__ __forceinline__ void encode_points(const PointSet &ps, const float (&base)[2][3], const GridLevel &L,
                                               const LevelFast &F, const float2 *__restrict__ lvl,
                                               float *__restrict__ planes, int out_half, size_t plane0, uint32_t n,
                                               uint32_t s) {
     float4 o_next = ps.offs[0];
     for (uint32_t p = 0; p < ps.P; ++p) {
-        if (TRIPLE && KIND == kHashPow2 && PAIR && ps.mode == 1) {
-            // how many points from p on differ in their x offset only (uniform: the offsets are kernel arguments)
-            uint32_t g = 1;
-            while (g < 3u && p + g < ps.P && ps.offs[p + g].y == ps.offs[p].y && ps.offs[p + g].z == ps.offs[p].z &&
-                   ((p + g) < ps.P0) == (p < ps.P0))
-                ++g;
-            if (g > 1u) {
-                encode_group_hash<NT>(ps, base, L, F, lvl, planes, out_half, plane0, n, s, p, g);
-                p += g - 1u;
-                o_next = ps.offs[p + 1 < ps.P ? p + 1 : p];
-                continue;
-            }
-        }
         float q[3];
         const float4 o = o_next;
         o_next = ps.offs[p + 1 < ps.P ? p + 1 : p];  // (scalar load, a point ahead of its use)
@@ -494,13 +384,6 @@ __device__ __forceinline__ void encode_points(const PointSet &ps, const float (&
     }
 }
 
-#ifndef MI3D_ENCODE_STEAL
-// k_grid_encode_planes: an XCD that has finished its list helps the others with their last segments.  Measured between
-// product-grade builds in one process (tools/gather_ab_libs.py, profiles/gather_ab_libs_r06_steal.json): 22.25 -> 23.35 ms -
-// SLOWER: a helper starts on a table its L2 does not hold, and the tiles it claimed finish after the owner would have
-// finished them.  Not taken (0).
-#define MI3D_ENCODE_STEAL 0
-#endif
 // next unclaimed tile of every plan segment; one slot per launch in flight (zeroed in-stream before the launch)
 constexpr uint32_t kPlanSlots = 64;
 __device__ uint32_t g_encode_next[kPlanSlots * kXcds * kMaxSegs];
@@ -518,7 +401,7 @@ std::mutex g_slot_mutex;
 __device__ unsigned long long mi3d_dbg_encode[kXcds * (1 + kMaxSegs)];
 #endif
 
-template <bool PAIR, bool NT, bool TRIPLE = false>
+template <bool PAIR, bool NT>
 __global__ __launch_bounds__(kWave *kWaves) void k_grid_encode_planes(PointSet ps, uint32_t n,
                                                                        const float2 *__restrict__ table, GridTable T,
                                                                        EncodePlan plan, float *__restrict__ planes,
@@ -534,8 +417,8 @@ __global__ __launch_bounds__(kWave *kWaves) void k_grid_encode_planes(PointSet p
     if (threadIdx.x == 0) atomicMin(&mi3d_dbg_encode[xcd * (1 + kMaxSegs)], (unsigned long long)wall_clock64());
 #endif
     // one segment of XCD x's list: claim its tiles until none is left
-    auto walk = [&](uint32_t x, uint32_t sg, bool own) __attribute__((always_inline)) {
-        const EncodeSeg seg = plan.seg[x][sg];
+    auto walk = [&](uint32_t sg) __attribute__((always_inline)) {
+        const EncodeSeg seg = plan.seg[xcd][sg];
         const uint32_t l = seg.level;
         const GridLevel L = T.level[l];
         const float2 *lvl = table + L.offset;
@@ -550,8 +433,7 @@ __global__ __launch_bounds__(kWave *kWaves) void k_grid_encode_planes(PointSet p
         // the CU's oldest-first issue arbitration lets the first-dispatched workgroups finish a segment milliseconds
         // before the last-dispatched ones, they move on, and the XCD's 4 MB L2 then holds two or three levels' tables at
         // once (tools/kbench.py encode_xcds: level 7 still being walked at 28 ms of a 29.6 ms launch).
-        uint32_t *ctr = next ? next + x * kMaxSegs + sg : nullptr;
-        if (!ctr && !own) return;
+        uint32_t *ctr = next ? next + xcd * kMaxSegs + sg : nullptr;
         const uint32_t stride = seg.wgs * kWaves;
         auto claim = [&](uint32_t prev) __attribute__((always_inline)) {
             if (!ctr) return prev + stride;
@@ -567,41 +449,19 @@ __global__ __launch_bounds__(kWave *kWaves) void k_grid_encode_planes(PointSet p
             float base[2][3];
             load_bases(ps, s, true, base);
             if (F.kind == kDense3) encode_points<kDense3, PAIR, NT>(ps, base, L, F, lvl, planes, out_half, plane0, n, s);
-            else if (F.kind == kHashPow2) encode_points<kHashPow2, PAIR, NT, TRIPLE>(ps, base, L, F, lvl, planes, out_half, plane0, n, s);
+            else if (F.kind == kHashPow2) encode_points<kHashPow2, PAIR, NT>(ps, base, L, F, lvl, planes, out_half, plane0, n, s);
             else encode_points<kGeneral, PAIR, NT>(ps, base, L, F, lvl, planes, out_half, plane0, n, s);
         }
     };
-    // The XCD's own list; with MI3D_ENCODE_STEAL (measured: slower, off) then the LAST segment of every other XCD's - the
-    // cost model that cuts the list leaves the XCDs finishing 19.8 to 22.0 ms into a 22 ms launch.  One loop, so that the
-    // point loops are instantiated once.
-    // (plan.shared: all eight XCDs walk the levels TOGETHER - segment sg of every XCD is its eighth of level sg's tiles, and an
-    //  XCD that is through with its eighth claims from the others' before anybody moves on to the next level)
-    const uint32_t n_own = plan.n_seg[xcd];
-    const uint32_t n_walk = plan.shared ? n_own * (next ? kXcds : 1u) : n_own + ((MI3D_ENCODE_STEAL && next) ? kXcds - 1u : 0u);
-    for (uint32_t i = 0; i < n_walk; ++i) {
-        bool own;
-        uint32_t x, sg;
-        if (plan.shared) {
-            const uint32_t k = next ? i % kXcds : 0u;
-            sg = next ? i / kXcds : i;
-            own = k == 0u;
-            x = (xcd + k) % kXcds;
-        } else {
-            own = i < n_own;
-            x = own ? xcd : (xcd + 1u + (i - n_own)) % kXcds;
-            if (!own && plan.n_seg[x] == 0u) continue;
-            sg = own ? i : plan.n_seg[x] - 1u;
-        }
+    // (An XCD that is through with its list helping the others with their last segments, and all eight XCDs walking the
+    //  levels together: both tried in round 6, slower / no gain - DESIGN.md 3.1, A.11.)
+    for (uint32_t sg = 0; sg < plan.n_seg[xcd]; ++sg) {
+        walk(sg);
 #ifdef MI3D_DEV
-        if (!plan.shared && i > 0 && i <= n_own && threadIdx.x == 0)
-            atomicMax(&mi3d_dbg_encode[xcd * (1 + kMaxSegs) + i], (unsigned long long)wall_clock64());
+        if (threadIdx.x == 0)
+            atomicMax(&mi3d_dbg_encode[xcd * (1 + kMaxSegs) + sg + 1u], (unsigned long long)wall_clock64());
 #endif
-        walk(x, sg, own);
     }
-#ifdef MI3D_DEV
-    if (n_walk == n_own && threadIdx.x == 0)
-        atomicMax(&mi3d_dbg_encode[xcd * (1 + kMaxSegs) + n_own], (unsigned long long)wall_clock64());
-#endif
 }
 
 // The coarsest levels from LDS.  Levels whose tables fit a CU's LDS together (the default grid: level 0 = 4096 entries,
@@ -642,39 +502,18 @@ __global__ __launch_bounds__(kWave *kLdsWaves) void k_grid_encode_planes_lds(Poi
     }
 }
 
-#ifndef MI3D_ENCODE_SHARED_LEVELS
-// 1: all eight XCDs walk the levels TOGETHER (each its eighth of a level's tiles first, then the others' eighths) instead of
-// one contiguous stretch of the (level, tile) list per XCD cut by a cost model.  Round 6, product builds in one process
-// (tools/gather_ab_libs.py; planes bit-identical): per-XCD stretches 21.89-22.73 ms (mean 22.27), together 22.47-22.53
-// (profiles/gather_ab_libs_r06_shared_levels.json) - the perfect balance buys nothing once every level change is a change for
-// the whole chip; with ONE claim counter per level for all XCDs 32.5 ms (profiles/gather_ab_libs_r06_shared_one_counter.json:
-// ~75 M claims/s is what one address takes).  Not taken (0).
-#define MI3D_ENCODE_SHARED_LEVELS 0
-#endif
-#ifndef MI3D_ENCODE_COST_FIT
-#define MI3D_ENCODE_COST_FIT 6   // which round's fit of the per-level cost table make_encode_plan balances the XCDs with
-#endif
 // Relative cost of one tile of a level, as a function of x = (marching step) x (level scale) = how many cells of the
 // level two consecutive samples of a ray are apart: the measured per-level times above, tabulated against x (C2: step
 // 2 sqrt(3) / 1024 in a box of side 2) and interpolated, so other step sizes and grid configurations balance too.
 inline double encode_level_cost(double x, bool dense_fast) {
-    // round 3, after the short index routes (profiles/kbench_r03_encode_fast.json): ms per level at C2 with 6 workgroups
-    // per CU up to x = 0.26 and 3 beyond.  A dense level on the short route is instruction-bound and flat.
+    // ms per level at C2 with 6 workgroups per CU up to x = 0.26 and 3 beyond; a dense level on the short route is
+    // instruction-bound and flat.  Round 6's fit, IN SITU: what a tile of each level costs its XCD while the other seven walk
+    // theirs, from the per-XCD, per-segment timestamps of the whole gather (tools/encode_xcd_timeline.py,
+    // profiles/encode_xcd_timeline_r06*.json).  Round 3's table (per-level launches of the whole chip) was equal within the
+    // run-to-run spread: the balance of the XCDs is worth <= 0.9 ms and a static table cannot have it.
     static const double xs[] = {0.0, 0.136, 0.19, 0.26, 0.36, 0.50, 0.69, 0.95, 1.30, 1.80, 2.50, 3.50};
-#if MI3D_ENCODE_COST_FIT == 3
-    if (dense_fast) return 0.44;
-    static const double cs[] = {0.74, 0.76, 0.84, 0.94, 1.10, 1.50, 1.98, 2.55, 2.87, 3.03, 3.06, 3.08};
-#else
-    // round 6: re-fitted IN SITU - what a tile of each level costs its XCD while the other seven walk theirs, from the
-    // per-XCD, per-segment timestamps of the whole gather (tools/encode_xcd_timeline.py, profiles/encode_xcd_timeline_r06*.json;
-    // tile-weighted ms per 1000 tiles of one XCD x 170 / 8, segments of 20 000 tiles and more, two plans).  Round 3's table came from per-level launches of the whole chip; under it the
-    // XCDs finished 20.3 to 21.9 ms into the launch; under this one 20.6 to 22.2 on another box (what an XCD's tile costs moves
-    // by ~5 % with the box and with what the other XCDs are doing): 22.25-22.98 ms against 22.37-23.0 for round 3's table between
-    // product builds in one process (profiles/gather_ab_libs_r06_cost_fit.json) - equal within the run-to-run spread.  The
-    // balance of the XCDs is worth <= 0.9 ms (mean end 21.0 against the last one's 21.9) and a static table cannot have it.
     if (dense_fast) return 0.383;
     static const double cs[] = {0.67, 0.685, 0.80, 0.853, 0.982, 1.416, 1.819, 2.246, 2.656, 2.72, 2.895, 2.78};
-#endif
     constexpr int N = sizeof(xs) / sizeof(xs[0]);
     if (x <= xs[0]) return cs[0];
     for (int i = 1; i < N; ++i)
@@ -688,31 +527,16 @@ inline uint32_t encode_level_wgs_per_cu(double x, uint32_t coarse, uint32_t fine
 // The (level, tile) list cut into kXcds contiguous segments of equal modelled cost.
 inline EncodePlan make_encode_plan(const GridTable &T, uint32_t n_tiles, float step01, int only_level,
                                    uint32_t wgs_coarse_per_xcd, uint32_t wgs_fine_per_xcd, uint32_t first_level = 0,
-                                   int point_mode = 1, uint32_t level_mask = 0xFFFFFFFFu) {
+                                   int point_mode = 1) {
     EncodePlan plan{};
     double cost[MI3D_MAX_LEVELS], total = 0.0;
     for (uint32_t l = 0; l < T.n_levels; ++l) {
         cost[l] = encode_level_cost((double)step01 * (double)T.level[l].scale,
                                     level_fast(T.level[l], point_mode).kind == kDense3);
         if (only_level >= 0) cost[l] = (int)l == only_level ? 1.0 : 0.0;
-        if (!((level_mask >> l) & 1u)) cost[l] = 0.0;  // another launch's levels
         if (l < first_level) cost[l] = 0.0;  // served from LDS by k_grid_encode_planes_lds
         total += cost[l];
     }
-#if MI3D_ENCODE_SHARED_LEVELS
-    // all eight XCDs walk level l together, each its eighth of the tiles first (its own claim counter: ONE counter for the
-    // whole chip was measured at 32.5 ms against 22.2 - ~75 M claims/s is what one address takes), then the others' eighths
-    // (the table is in every L2 by then): no cost model, no XCD finishing early
-    {
-        plan.shared = 1u;
-        for (uint32_t x = 0; x < kXcds; ++x)
-            for (uint32_t l = 0; l < T.n_levels; ++l)
-                if (cost[l] > 0.0 && plan.n_seg[x] < (uint32_t)kMaxSegs)
-                    plan.seg[x][plan.n_seg[x]++] = EncodeSeg{l, (uint32_t)((uint64_t)n_tiles * x / kXcds), (uint32_t)((uint64_t)n_tiles * (x + 1) / kXcds), encode_level_wgs_per_cu((double)step01 * (double)T.level[l].scale,
-                                                                                                  wgs_coarse_per_xcd, wgs_fine_per_xcd)};
-        return plan;
-    }
-#endif
     const double share = total / kXcds;
     uint32_t x = 0;
     double filled = 0.0;  // cost already given to XCD x
@@ -1032,8 +856,8 @@ uint32_t default_merge_levels(const GridTable &T, float step01) {
 // gather table); level 7 (cells of 3.9 marching steps at C2) is a record level now (merge_steps).
 // Round 5 (DESIGN.md 3.2''): the emit turned out to be bound by vector-instruction issue (0.71 of its SIMDs' slots at three
 // waves per SIMD), so what moved it was its instruction stream: the coarse role sums a run's lanes in registers before its
-// gather-table flush (MI3D_RUN_MERGE), a tile's gradient pairs are picked by relative register indexing instead of select
-// chains that hipcc had half-spilled to scratch (MI3D_DYN_IDX), and the reduce's record loads are unconditional, so that
+// gather-table flush (flush_group), a tile's gradient pairs are picked by relative register indexing instead of select
+// chains that hipcc had half-spilled to scratch, and the reduce's record loads are unconditional, so that
 // they really are in flight (MI3D_REDUCE_U).  Variants are judged between PRODUCT-grade builds loaded into one process
 // (tools/scatter_ab_libs.py): the tools build, with every variant behind a run-time switch, allocates registers for all
 // of them.
@@ -1108,17 +932,6 @@ struct BinPlan {
 // a hashed level's region capacity over the uniform share of its records (plan_for)
 #define MI3D_HASHED_SLACK 1.25
 #endif
-#ifndef MI3D_LEVEL_PAD_BYTES
-// Padding behind every fine (pair-record) level's block of the arena.  At C2 the nine fine levels' blocks are 4.319 GB each,
-// i.e. 4 GiB + 24 MB: the regions a wave appends to at the same time - same (wave, bin), nine levels - lie almost exactly
-// 4 GiB apart, and the emit's time turned out to depend on the arena's PHYSICAL base with a period of 4 GiB (a block whose
-// base is shifted by 2 GiB mod 4 GiB: 56.0 ms instead of 48.0, profiles/scatter_placement_r06.json `shift`).  See
-// Measured (tools/scatter_bimodal.py --shift --libs, profiles/scatter_placement_r06.json
-// `shift_pads`): paddings of 64 MiB / 455 MiB / 1100 MiB move the pattern (1100 MiB: 46.0 ms where the product takes 48.2 - and
-// 48.5 where it takes 46.7) but every variant still swings with the placement (53.5 against 54.5 on the worst block): the
-// padding is NOT the fix; 0 stays.
-#define MI3D_LEVEL_PAD_BYTES 0
-#endif
 __host__ __device__ inline uint32_t level_bins(const GridLevel &L) { return (L.size + kBinEntries - 1) / kBinEntries; }
 
 inline uint32_t round_waves(uint64_t w, uint32_t cap_waves) {
@@ -1172,7 +985,6 @@ inline BinPlan plan_for(const GridTable &T, uint64_t n_slice, uint32_t P, float 
         p.total_bytes += (uint64_t)p.level_waves[l] * bins * p.level_cap[l] *
                          (row ? (p.rec12 ? sizeof(Row12) : sizeof(RowRecord)) : sizeof(BinRecord));
         p.total_bytes = (p.total_bytes + 255u) / 256u * 256u;
-        if (row) p.total_bytes += (uint64_t)MI3D_LEVEL_PAD_BYTES;   // (see MI3D_LEVEL_PAD_BYTES)
         p.total_counts += p.level_waves[l] * bins;
         p.total_max += p.level_waves[l];
     }
@@ -1267,52 +1079,6 @@ __device__ __forceinline__ unsigned long long fixed_point(float x) {
 // handful of bins to reduce them in.  This merges across lanes, runs AND stencil points.)  A contribution that finds no
 // slot within kMergeProbes goes out as a record of its own.
 constexpr uint32_t kMergeSlots = 512, kMergeProbes = 16, kMergeEmpty = 0xFFFFFFFFu;
-#ifndef MI3D_RUN_MERGE
-// the coarse role's group flush sums a run's lanes in registers first (flush_group).  Round 5, one box, tools/kbench.py --what
-// scatter_r05, three interleaved pairs each: dense gradients 54.4-54.6 -> 53.3-53.5 ms, real census 37.7-37.8 -> 36.3-36.4;
-// the coarse role alone 36.3 -> 34.2 / 25.9 -> 24.2 (profiles/kbench_r05_scatter_run_merge.json)
-#define MI3D_RUN_MERGE 1
-#endif
-#ifndef MI3D_DYN_IDX
-// a tile's 13 gradient pairs wait in registers; the point loops pick theirs by a UNIFORM index.  Written as select chains
-// (round 3: "picked by a select chain (p is uniform)") that is 12 v_cndmask per pick, and hipcc kept part of the array in
-// scratch memory on top (96 bytes of private segment); indexed directly, hipcc uses gfx9's relative register addressing
-// (s_set_gpr_idx_on + one move) and the scratch array goes (28 bytes).  Product-grade builds in ONE process
-// (tools/scatter_ab_libs.py, profiles/scatter_ab_libs_r05.json), three interleaved rounds: dense gradients 52.56-52.69 ->
-// 50.74-50.78 ms, real census 43.01-43.03 -> 40.67-40.77; same gradient (1.7e-8 x max: the order of the float atomics).
-#define MI3D_DYN_IDX 1
-#endif
-#ifndef MI3D_TIMING_SEQ_FLUSH
-// TIMING ONLY (round 6; the reduce then reads garbage): the fine role's flush stores a chunk's 512 sorted records as one
-// contiguous 6 KB page of the wave's region instead of ~64 runs of ~8 records at the 64 bins' append points - the store
-// pattern a page-structured arena would have.  What leaves the L2s today is 740 M partial 64-byte write requests for 1.72 G
-// records per slice launch, and how well HBM takes them depends on where the arena lies (13.7-18.7 ms per slice,
-// profiles/scatter_placement_r06.json); this build says what the emit costs when its stores are perfectly sequential, i.e.
-// the most ANY re-organisation of the stores could buy.  Result: profiles/scatter_ab_libs_r06_seq_flush.json.
-#define MI3D_TIMING_SEQ_FLUSH 0
-#endif
-#ifndef MI3D_EMIT_ORDER_DEFAULT
-// bit 0 = the fine role walks its (tile, level) pairs level-major (see k_bin_emit); 0 = tile-major, the product's order
-#define MI3D_EMIT_ORDER_DEFAULT 0
-#endif
-#ifndef MI3D_TIMING_FAKE_PASS1
-// TIMING ONLY (round 6; a variant build for tools/scatter_ab_libs.py - the gradient is garbage):
-// the fine role's pass 1 without its position / cell / hash arithmetic.  What the forward gather could hand over in an index
-// plane (item 1a: entry, the y / z hash differences, three fractions - 16 bytes per (evaluation, fine level)) or a delta
-// hash could shorten (1b) is exactly this arithmetic: point_of (~10 vector instructions), three grid_cell (12), two
-// quarter-rate 32-bit multiplies (8 issue slots), the +1 bases and the flip (9).  Here it is replaced by what UNPACKING such
-// a plane would cost (a few shifts, masks and three converts) on bits that are already in registers - i.e. the index plane
-// with its loads for free: an upper bound of what either idea can buy.  Result: profiles/scatter_ab_libs_r06_fake_pass1.json.
-#define MI3D_TIMING_FAKE_PASS1 0
-#endif
-#ifndef MI3D_MASK_FMA
-// the coarse role's register sums by fused multiply-add with a 0 / 1 lane mask instead of select + add.  Round 5: in the
-// tools build (both forms behind a run-time switch, profiles/kbench_r05_scatter_mask_fma.json) real census 36.55-37.09 ->
-// 36.34-36.60 ms, dense 53.70-54.16 -> 53.46-53.52; between two PRODUCT-grade builds in one process
-// (profiles/scatter_ab_libs_r05.json) no difference (43.02 vs 43.05, 52.62 vs 52.65): neutral, kept; same gradient to
-// 1e-7 x max
-#define MI3D_MASK_FMA 1
-#endif
 // Fine levels: the x-pair records of kChunkPts stencil points of a tile (64 lanes x 4 pairs each) are SORTED BY BIN in the
 // wave's LDS before they leave, so that what goes to a region is a contiguous run of records (consecutive lanes store
 // consecutive 16-byte slots) instead of one scattered 16-byte store per lane.  The staging area is the memory the coarse
@@ -1330,8 +1096,7 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                                                              uint32_t n_rows, const float *__restrict__ extra0,
                                                              GridTable T, BinPlan plan, uint32_t merge_levels,
                                                              uint32_t mask_a, uint32_t waves_a, uint32_t mask_b,
-                                                             uint32_t waves_b, uint32_t fine_level_major,
-                                                             BinRecord *__restrict__ arena,
+                                                             uint32_t waves_b, BinRecord *__restrict__ arena,
                                                              uint32_t *__restrict__ counts,
                                                              float *__restrict__ level_max,
                                                              float *__restrict__ grad_table) {
@@ -1354,62 +1119,35 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
     if (lane < MI3D_MAX_LEVELS) lmax_all[wave_in_wg][lane] = 0.f;
     if (gw >= n_waves) return;
 
-    // The (tile, level) pairs of this wave.  Tile-major (the product's order for both roles): the positions of a tile are
-    // loaded once for all its levels.  Level-major for the fine role is a development switch (csrc/mi3d_dev.h
-    // MI3D_T_EMIT_ORDER): the wave then appends to the 64 regions of ONE level at a time, 12.6 MB of open lines chip-wide
-    // instead of 100 MB - which doubles the rate of the bare store pattern (tools/store_bench.hip,
-    // profiles/store_bench_r02.txt: 184 G vs 75 G records/s) but not of this kernel: measured 2 ms slower, twice.
-    const uint32_t nl = (uint32_t)__popc(level_mask);
-    const uint32_t span = n_waves * kWave, first = s_begin + gw * kWave;
-    const uint32_t nt = first < s_end ? (s_end - first + span - 1) / span : 0u;
-    const bool level_major = !role_b && (fine_level_major & 1u);
+    // The (tile, level) pairs of this wave, tile-major: the positions of a tile are loaded once for all its levels.
+    // (Level-major for the fine role - the wave then appends to the 64 regions of ONE level at a time, 12.6 MB of open lines
+    // chip-wide instead of 100 MB - doubles the rate of the bare store pattern, tools/store_bench.hip, but not of this kernel:
+    // measured 2 ms slower, twice.  DESIGN.md 3.2, A.11.)
     // Tiles are CLAIMED from a per-role counter (round 6), not dealt: a tile's cost follows its non-zero gradient pairs,
     // and with tiles dealt statically (wave gw: tiles gw, gw + n_waves ...) the launch ended when the unluckiest of its
     // persistent waves did - the slots of all the others idle meanwhile, once per slice.  (Which wave emits a tile does
-    // not matter to the sums: the reduce adds integers.)  The dealt order stays behind bit 0x100000 of the order word.
-    const bool claim = !level_major && !(fine_level_major & 0x100000u);
+    // not matter to the sums: the reduce adds integers.)
     uint32_t *claim_ctr = reinterpret_cast<uint32_t *>(level_max + plan.claim0) + (role_b ? 1 : 0);
     const uint32_t n_tiles = (s_end - s_begin + kWave - 1) / kWave;
-    uint32_t claimed = 0;
-#ifdef MI3D_DEV  // tools build: 0x10000 = the coarse role's shared-face pass off (A/B against round 3's pair passes);
-                 // 0x20000 toggles the run-merged group flush against its product default
-    const bool face_on = !(fine_level_major & 0x10000u);
-    const bool run_merge = ((fine_level_major & 0x20000u) != 0u) != (MI3D_RUN_MERGE != 0);
-    const bool mask_fma = ((fine_level_major & 0x40000u) != 0u) != (MI3D_MASK_FMA != 0);   // 0x40000 flips the masked fma
-    const bool dyn_idx = ((fine_level_major & 0x80000u) != 0u) != (MI3D_DYN_IDX != 0);     // 0x80000 flips the register indexing
-#else
-    constexpr bool face_on = true;
-    constexpr bool run_merge = MI3D_RUN_MERGE != 0;
-    constexpr bool mask_fma = MI3D_MASK_FMA != 0;
-    constexpr bool dyn_idx = MI3D_DYN_IDX != 0;
-#endif
-    uint32_t cur_tile = 0xFFFFFFFFu, s = 0;
+    uint32_t s = 0, rest = 0u;   // rest: the levels of the role's mask the current tile has still to go through
     bool valid = false;
     float b00 = 0.f, b01 = 0.f, b02 = 0.f, b10 = 0.f, b11 = 0.f, b12 = 0.f;  // the tile's positions
-    for (uint32_t it = 0; claim || it < nl * nt; ++it) {
-        uint32_t ti = level_major ? it % nt : it / nl;
-        const uint32_t li = level_major ? it / nt : it % nl;
-        if (claim) {
-            if (li == 0u) {
-                uint32_t t = 0;
-                if (lane == 0) t = atomicAdd(claim_ctr, 1u);
-                claimed = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
-            }
-            if (claimed >= n_tiles) break;
-            ti = claimed;
-        }
-        uint32_t rest = level_mask;
-        for (uint32_t k = 0; k < li; ++k) rest &= rest - 1u;
-        const uint32_t l = (uint32_t)__builtin_ctz(rest);  // the li-th level of the role's mask
-        if (ti != cur_tile) {
-            cur_tile = ti;
-            s = claim ? s_begin + ti * kWave + lane : first + ti * span + lane;
+    for (;;) {
+        if (rest == 0u) {   // a new tile: claim it, load its positions
+            uint32_t t = 0;
+            if (lane == 0) t = atomicAdd(claim_ctr, 1u);
+            const uint32_t ti = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+            if (ti >= n_tiles) break;
+            rest = level_mask;
+            s = s_begin + ti * kWave + lane;
             valid = s < s_end;
             float fresh[2][3];
             load_bases(ps, s, valid, fresh);
             b00 = fresh[0][0]; b01 = fresh[0][1]; b02 = fresh[0][2];
             b10 = fresh[1][0]; b11 = fresh[1][1]; b12 = fresh[1][2];
         }
+        const uint32_t l = (uint32_t)__builtin_ctz(rest);
+        rest &= rest - 1u;
         {
             const float base[2][3] = {{b00, b01, b02}, {b10, b11, b12}};
             const GridLevel L = T.level[l];
@@ -1425,7 +1163,7 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
             // counter for vector loads and stores (vmcnt), and the compiler cannot count the conditional stores between a
             // load and its use - so a load consumed inside the point loop costs "s_waitcnt vmcnt(0)": a full drain of the
             // wave's scattered stores, once per point.  Up front it is one drain per 13 points; the pairs wait in
-            // registers as raw bits and are picked by a select chain (p is uniform).
+            // registers as raw bits and are picked by relative register indexing (p is uniform).
             // point-major rows: the pair of (sample s, point p) sits at plane[p * n_rows + s] - 512 contiguous bytes per wave
             // (unconditional loads from clamped rows - a predicated load makes the compiler wait for it on the spot; what
             // an invalid lane or a point >= P fetched is never looked at)
@@ -1506,11 +1244,6 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
             // finds its slot taken by another entry (rare at 512 slots for a few hundred entries) walks on alone.
             auto gather8 = [&](uint32_t ex, uint32_t ey, uint32_t ez, const float (&g0)[8], const float (&g1)[8]) __attribute__((always_inline)) {
                 static_assert(kMergeSlots == 512, "the slot hash keeps 9 bits");
-#ifdef MI3D_DEV  // tools build: what the gather table's atomics cost (timing only - the sums are wrong with either bit)
-                const bool dbg_no_add = fine_level_major & 0x100u, dbg_no_cas = fine_level_major & 0x200u;
-#else
-                constexpr bool dbg_no_add = false, dbg_no_cas = false;
-#endif
 #pragma unroll
                 for (uint32_t half = 0; half < 2; ++half) {  // two batches of four probes in flight (registers)
                     uint32_t e[4], slot[4], old[4];
@@ -1520,7 +1253,7 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
 #pragma unroll
                     for (uint32_t j = 0; j < 4; ++j) {
                         const uint32_t k = 4 * half + j;
-                        old[j] = ((g0[k] != 0.f || g1[k] != 0.f) && !dbg_no_cas) ? atomicCAS(&keys[slot[j]], kMergeEmpty, e[j]) : e[j];
+                        old[j] = (g0[k] != 0.f || g1[k] != 0.f) ? atomicCAS(&keys[slot[j]], kMergeEmpty, e[j]) : e[j];
                     }
 #pragma unroll
                     for (uint32_t j = 0; j < 4; ++j) {
@@ -1533,10 +1266,8 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                             placed = o == kMergeEmpty || o == e[j];
                         }
                         if (placed) {
-                            if (!dbg_no_add) {
-                                atomicAdd(&sums[2 * slot[j]], fixed_point(g0[k] * merge_scale));
-                                atomicAdd(&sums[2 * slot[j] + 1], fixed_point(g1[k] * merge_scale));
-                            }
+                            atomicAdd(&sums[2 * slot[j]], fixed_point(g0[k] * merge_scale));
+                            atomicAdd(&sums[2 * slot[j] + 1], fixed_point(g1[k] * merge_scale));
                         } else {
                             emit_record(plan, L, l, gw, e[j], g0[k], g1[k], fill, arena, grad_table, lmax);
                         }
@@ -1577,19 +1308,11 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
             auto face_pass = [&](auto axis_tag, bool fa, bool fb, const float (&a0)[8], const float (&a1)[8],
                                  const float (&b0)[8], const float (&b1)[8]) __attribute__((always_inline)) {
                 constexpr uint32_t AXIS = decltype(axis_tag)::value, m = 1u << AXIS;
-                if (mask_fma) {
-                    const float mfa = fa ? 1.0f : 0.0f, mfb = fb ? 1.0f : 0.0f;
-#pragma unroll
-                    for (uint32_t k = 0; k < 8; ++k) {
-                        if (!(k & m)) { acc0[k | m] = fmaf(a0[k], mfa, acc0[k | m]); acc1[k | m] = fmaf(a1[k], mfa, acc1[k | m]); }
-                        else { acc0[k & ~m] = fmaf(b0[k], mfb, acc0[k & ~m]); acc1[k & ~m] = fmaf(b1[k], mfb, acc1[k & ~m]); }
-                    }
-                } else {
+                const float mfa = fa ? 1.0f : 0.0f, mfb = fb ? 1.0f : 0.0f;   // (0 / 1 lane masks, see the register sums below)
 #pragma unroll
                 for (uint32_t k = 0; k < 8; ++k) {
-                    if (!(k & m)) { acc0[k | m] += fa ? a0[k] : 0.f; acc1[k | m] += fa ? a1[k] : 0.f; }   // +: its near face
-                    else { acc0[k & ~m] += fb ? b0[k] : 0.f; acc1[k & ~m] += fb ? b1[k] : 0.f; }          // -: its near face
-                }
+                    if (!(k & m)) { acc0[k | m] = fmaf(a0[k], mfa, acc0[k | m]); acc1[k | m] = fmaf(a1[k], mfa, acc1[k | m]); }   // +: its near face
+                    else { acc0[k & ~m] = fmaf(b0[k], mfb, acc0[k & ~m]); acc1[k & ~m] = fmaf(b1[k], mfb, acc1[k & ~m]); }     // -: its near face
                 }
                 uint32_t e[4];
                 float f0[4], f1[4];
@@ -1610,47 +1333,40 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
             };
             auto flush_group = [&]() __attribute__((always_inline)) {
                 if (acc_any) {
-                    if (run_merge) {
-                        // Consecutive samples of a ray sit in ONE cell of a coarse level for a whole run of lanes (37
-                        // marching steps per cell on level 0, 5 on level 6), so in the flush below most of a wave's lanes
-                        // add into the SAME 8 slots: LDS atomics on one address serialise, and these 24 instructions - with
-                        // every lane active - are where the gather table's time goes (an atomic here retires ~70 cycles per
-                        // instruction and CU against ~12 for distinct addresses, profiles/lds_atomics_r01.txt).  So the
-                        // register sums of a run are first added up ACROSS its lanes, in segments of at most 8 lanes that
-                        // never cross an 8-lane boundary (three steps of row_shr, pure VALU: no LDS), and only a segment's
-                        // last lane goes to the table - 8 x fewer lanes per address for 3 x 16 DPP moves + adds.
-                        const uint32_t pbx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bx, 0x111, 0xf, 0xf, true);
-                        const uint32_t pby = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)by, 0x111, 0xf, 0xf, true);
-                        const uint32_t pbz = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bz, 0x111, 0xf, 0xf, true);
-                        const bool head = (lane & 7) == 0 || pbx != bx || pby != by || pbz != bz;
-                        const unsigned long long heads = __ballot(head);
-                        const uint32_t first = 63u - (uint32_t)__builtin_clzll(heads & ((2ull << lane) - 1ull));
-                        const uint32_t pos = (uint32_t)lane - first;                        // 0 .. 7 inside the segment
-                        const bool tail = lane == 63 || (((heads >> 1) >> lane) & 1ull) != 0ull;
-                        auto seg_step = [&](auto ctrl_tag, uint32_t off) __attribute__((always_inline)) {
-                            constexpr int CTRL = decltype(ctrl_tag)::value;   // (the DPP control is an instruction immediate)
-                            float u0[8], u1[8];
+                    // Consecutive samples of a ray sit in ONE cell of a coarse level for a whole run of lanes (37
+                    // marching steps per cell on level 0, 5 on level 6), so in the flush below most of a wave's lanes
+                    // add into the SAME 8 slots: LDS atomics on one address serialise, and these 24 instructions - with
+                    // every lane active - are where the gather table's time goes (an atomic here retires ~70 cycles per
+                    // instruction and CU against ~12 for distinct addresses, profiles/lds_atomics_r01.txt).  So the
+                    // register sums of a run are first added up ACROSS its lanes, in segments of at most 8 lanes that
+                    // never cross an 8-lane boundary (three steps of row_shr, pure VALU: no LDS), and only a segment's
+                    // last lane goes to the table - 8 x fewer lanes per address for 3 x 16 DPP moves + adds.
+                    const uint32_t pbx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bx, 0x111, 0xf, 0xf, true);
+                    const uint32_t pby = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)by, 0x111, 0xf, 0xf, true);
+                    const uint32_t pbz = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bz, 0x111, 0xf, 0xf, true);
+                    const bool head = (lane & 7) == 0 || pbx != bx || pby != by || pbz != bz;
+                    const unsigned long long heads = __ballot(head);
+                    const uint32_t first = 63u - (uint32_t)__builtin_clzll(heads & ((2ull << lane) - 1ull));
+                    const uint32_t pos = (uint32_t)lane - first;                        // 0 .. 7 inside the segment
+                    const bool tail = lane == 63 || (((heads >> 1) >> lane) & 1ull) != 0ull;
+                    auto seg_step = [&](auto ctrl_tag, uint32_t off) __attribute__((always_inline)) {
+                        constexpr int CTRL = decltype(ctrl_tag)::value;   // (the DPP control is an instruction immediate)
+                        float u0[8], u1[8];
 #pragma unroll
-                            for (uint32_t k = 0; k < 8; ++k) {   // (moved under the full exec mask: a masked DPP source reads 0)
-                                u0[k] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc0[k]), CTRL, 0xf, 0xf, true));
-                                u1[k] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc1[k]), CTRL, 0xf, 0xf, true));
-                            }
-                            const bool take = pos >= off;
-                            if (mask_fma) {
-                                const float mt = take ? 1.0f : 0.0f;
+                        for (uint32_t k = 0; k < 8; ++k) {   // (moved under the full exec mask: a masked DPP source reads 0)
+                            u0[k] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc0[k]), CTRL, 0xf, 0xf, true));
+                            u1[k] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc1[k]), CTRL, 0xf, 0xf, true));
+                        }
+                        const bool take = pos >= off;
+                        const float mt = take ? 1.0f : 0.0f;
 #pragma unroll
-                                for (uint32_t k = 0; k < 8; ++k) { acc0[k] = fmaf(u0[k], mt, acc0[k]); acc1[k] = fmaf(u1[k], mt, acc1[k]); }
-                            } else {
+                        for (uint32_t k = 0; k < 8; ++k) { acc0[k] = fmaf(u0[k], mt, acc0[k]); acc1[k] = fmaf(u1[k], mt, acc1[k]); }
+                    };
+                    seg_step(std::integral_constant<int, 0x111>{}, 1u);   // row_shr:1
+                    seg_step(std::integral_constant<int, 0x112>{}, 2u);   // row_shr:2
+                    seg_step(std::integral_constant<int, 0x114>{}, 4u);   // row_shr:4
 #pragma unroll
-                            for (uint32_t k = 0; k < 8; ++k) { acc0[k] += take ? u0[k] : 0.f; acc1[k] += take ? u1[k] : 0.f; }
-                            }
-                        };
-                        seg_step(std::integral_constant<int, 0x111>{}, 1u);   // row_shr:1
-                        seg_step(std::integral_constant<int, 0x112>{}, 2u);   // row_shr:2
-                        seg_step(std::integral_constant<int, 0x114>{}, 4u);   // row_shr:4
-#pragma unroll
-                        for (uint32_t k = 0; k < 8; ++k) { acc0[k] = tail ? acc0[k] : 0.f; acc1[k] = tail ? acc1[k] : 0.f; }
-                    }
+                    for (uint32_t k = 0; k < 8; ++k) { acc0[k] = tail ? acc0[k] : 0.f; acc1[k] = tail ? acc1[k] : 0.f; }
                     gather8(bx, by, bz, acc0, acc1);
 #pragma unroll
                     for (uint32_t k = 0; k < 8; ++k) { acc0[k] = 0.f; acc1[k] = 0.f; }
@@ -1716,21 +1432,12 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                     // cycles at 1.5 waves per SIMD, profiles/pmc_r03_emit_roles.json)
                     uint32_t ccx[kChunkPts], ce0[kChunkPts][4], cpm[kChunkPts];
                     float cfx[kChunkPts], cfy[kChunkPts], cfz[kChunkPts], cd0[kChunkPts], cd1[kChunkPts];
-                    // the chunk's gradient pairs out of the tile's (p0 is uniform and even: one select chain per chunk)
-                    uint32_t craw0[kChunkPts], craw1[kChunkPts];
+                    // the chunk's gradient pairs out of the tile's (p0 is uniform: relative register indexing.  As select
+                    // chains hipcc kept part of the array in scratch: DESIGN.md A.5)
                     static_assert(kChunkPts == 2, "the pick below walks the points two at a time");
-                    craw0[0] = raw0[0]; craw0[1] = raw0[1]; craw1[0] = raw1[0]; craw1[1] = raw1[HP ? 0 : 1];
-                    if (dyn_idx) {
-                        const uint32_t ka = p0 < (uint32_t)kMaxPts ? p0 : 0u, kb = ka + 1 < (uint32_t)kMaxPts ? ka + 1 : ka;
-                        craw0[0] = raw0[ka]; craw0[1] = raw0[kb]; craw1[0] = raw1[HP ? 0 : ka]; craw1[1] = raw1[HP ? 0 : kb];
-                    } else {
-#pragma unroll
-                    for (uint32_t k = 2; k < (uint32_t)kMaxPts; k += 2) {
-                        const uint32_t k1 = k + 1 < (uint32_t)kMaxPts ? k + 1 : k;
-                        craw0[0] = (p0 == k) ? raw0[k] : craw0[0]; craw0[1] = (p0 == k) ? raw0[k1] : craw0[1];
-                        craw1[0] = (p0 == k) ? raw1[HP ? 0 : k] : craw1[0]; craw1[1] = (p0 == k) ? raw1[HP ? 0 : k1] : craw1[1];
-                    }
-                    }
+                    const uint32_t ka = p0 < (uint32_t)kMaxPts ? p0 : 0u, kb = ka + 1 < (uint32_t)kMaxPts ? ka + 1 : ka;
+                    uint32_t craw0[kChunkPts], craw1[kChunkPts];
+                    craw0[0] = raw0[ka]; craw0[1] = raw0[kb]; craw1[0] = raw1[HP ? 0 : ka]; craw1[1] = raw1[HP ? 0 : kb];
                     // pass 1: cells, entries, and how many records each bin gets
 #pragma unroll
                     for (uint32_t c = 0; c < kChunkPts; ++c) {
@@ -1744,34 +1451,19 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                         if (!HP && p == 0u) { d.x += ex0x; d.y += ex0y; }   // (uniform; fp32 planes: summed in place)
                         const bool has = valid && p < Pf && (d.x != 0.f || d.y != 0.f);
                         const bool finite = fabsf(d.x) <= 3.4028234663852886e38f && fabsf(d.y) <= 3.4028234663852886e38f;
-#if MI3D_TIMING_FAKE_PASS1   // TIMING ONLY (see the switch's comment above k_bin_emit): no position, no cells, no hash
-                        uint32_t cy = 0, cz = 0;
-                        const uint32_t fk = r0 ^ (r0 >> 9) ^ (s << 7) ^ (p * 0x51ED27u);
-                        ccx[c] = fk >> 13;
-                        cfx[c] = (float)(fk & 1023u) * (1.0f / 1024.0f);
-                        cfy[c] = (float)((fk >> 10) & 1023u) * (1.0f / 1024.0f);
-                        cfz[c] = (float)((fk >> 20) & 1023u) * (1.0f / 1024.0f);
-#else
                         float q[3];
                         point_of(ps, base, p < ps.P ? p : 0u, q);
                         uint32_t cy, cz;
                         grid_cell(q[0], L.scale, ccx[c], cfx[c]);
                         grid_cell(q[1], L.scale, cy, cfy[c]);
                         grid_cell(q[2], L.scale, cz, cfz[c]);
-#endif
                         cd0[c] = d.x; cd1[c] = d.y;
                         const bool ok = has && finite;
                         if (ok) lmax = fmaxf(lmax, fmaxf(fabsf(d.x), fabsf(d.y)));
                         uint32_t e1s[4], pm = 0u;
                         if (L.hashed) {  // e(x + 1) = e(x) ^ flip, flip = the bits a +1 carry changes in cx (x enters with prime 1)
-#if MI3D_TIMING_FAKE_PASS1
-                            (void)cy; (void)cz;
-                            const uint32_t yz[4] = {fk, fk ^ 0x2F3A5u, fk ^ 0x5C1B3u, fk ^ 0x73216u};
-#else
-                            const bool f24 = (L.res >> 22) == 0u;
-                            const uint32_t hy = mul_prime(cy, kPrimeY, f24), hz = mul_prime(cz, kPrimeZ, f24), hy1 = hy + kPrimeY, hz1 = hz + kPrimeZ;
+                            const uint32_t hy = cy * kPrimeY, hz = cz * kPrimeZ, hy1 = hy + kPrimeY, hz1 = hz + kPrimeZ;
                             const uint32_t yz[4] = {hy ^ hz, hy1 ^ hz, hy ^ hz1, hy1 ^ hz1};
-#endif
                             const uint32_t flip = (ccx[c] ^ (ccx[c] + 1u)) & mask;
 #pragma unroll
                             for (uint32_t j = 0; j < 4; ++j) { ce0[c][j] = (ccx[c] ^ yz[j]) & mask; e1s[j] = ce0[c][j] ^ flip; }
@@ -1804,9 +1496,6 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                             }
                         }
                     }
-#ifdef MI3D_DEV  // tools build: 0x1000 = cells, entries and the bin histogram only (timing only)
-                    if (fine_level_major & 0x1000u) { hist[lane] = 0u; continue; }
-#endif
                     __builtin_amdgcn_wave_barrier();
                     // lane = bin: where the bin's run starts in the staging area and in its region
                     const uint32_t cnt = hist[lane], g = fill_l[lane];
@@ -1834,9 +1523,6 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                     if (cnt) fill_l[lane] = g + cnt;
                     hist[lane] = 0u;
                     __builtin_amdgcn_wave_barrier();
-#ifdef MI3D_DEV  // tools build: 0x2000 = stop after the scan (timing only)
-                    if (fine_level_major & 0x2000u) continue;
-#endif
                     // pass 2: the records, each to its place
 #pragma unroll
                     for (uint32_t c = 0; c < kChunkPts; ++c) {
@@ -1863,30 +1549,17 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                         }
                     }
                     __builtin_amdgcn_wave_barrier();
-#ifdef MI3D_DEV  // tools build: 0x4000 = stop after the records are staged (timing only)
-                    if (fine_level_major & 0x4000u) continue;
-#endif
                     // the sorted records leave: consecutive lanes, consecutive slots of a region
                     for (uint32_t i = lane; i < total; i += kWave) {
                         const uint4 rec = stage[i];
                         if (HP) {
-#if MI3D_TIMING_SEQ_FLUSH   // TIMING ONLY: the chunk's sorted records leave as ONE contiguous 6 KB page (see the switch's comment)
-                            const uint32_t bin = rec.w, at = (ti * 7u + (p0 >> 1)) * 512u + i + 0u * gdelta[bin];
-#else
                             const uint32_t bin = rec.w, at = i + gdelta[bin];   // = bin * cap + slot
-#endif
                             if (all_fit) {
-#ifdef MI3D_DEV
-                                if (!(fine_level_major & 0x800u))
-#endif
                                 region12[at] = Row12{rec.x, rec.y, rec.z};
                                 continue;
                             }
                             const uint32_t slot = at - __umul24(bin, cap);
                             if (slot < cap) {
-#ifdef MI3D_DEV  // tools build: 0x800 = the records are sorted but not stored (timing only)
-                                if (!(fine_level_major & 0x800u))
-#endif
                                 region12[__umul24(bin, cap) + slot] = Row12{rec.x, rec.y, rec.z};
                             } else {  // region full: straight to the table
                                 uint32_t el, tt;
@@ -1902,9 +1575,6 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                         const uint32_t e0 = rec.x & ((1u << kRowEntryBits) - 1u), bin = e0 >> kBinShift;
                         const uint32_t slot = i + gdelta[bin];
                         if (slot < cap) {
-#ifdef MI3D_DEV  // tools build: 0x800 = the records are sorted but not stored (timing only)
-                            if (!(fine_level_major & 0x800u))
-#endif
                             reinterpret_cast<uint4 *>(region0)[__umul24(bin, cap) + slot] = rec;
                         } else {  // region full: straight to the table
                             const float a = __uint_as_float(rec.y), b = __uint_as_float(rec.z), fx = __uint_as_float(rec.w);
@@ -1926,13 +1596,8 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                 auto eval_point = [&](uint32_t p, uint32_t &cx, uint32_t &cy, uint32_t &cz, float (&v0)[8], float (&v1)[8])
                     __attribute__((always_inline)) {
                     uint32_t r0 = raw0[0], r1 = raw1[0];
-                    if (dyn_idx) {   // (p is uniform: one relative register move instead of a 12-step select chain)
-                        const uint32_t pc = p < (uint32_t)kMaxPts ? p : 0u;
-                        r0 = raw0[pc]; r1 = raw1[HP ? 0 : pc];
-                    } else {
-#pragma unroll
-                    for (uint32_t k = 1; k < (uint32_t)kMaxPts; ++k) { r0 = (p == k) ? raw0[k] : r0; r1 = (p == k) ? raw1[HP ? 0 : k] : r1; }
-                    }
+                    const uint32_t pc = p < (uint32_t)kMaxPts ? p : 0u;   // (p is uniform: one relative register move, not a 12-step select chain)
+                    r0 = raw0[pc]; r1 = raw1[HP ? 0 : pc];
                     float2 d = HP
                         ? make_float2((float)__builtin_bit_cast(_Float16, (unsigned short)(r0 & 0xFFFFu)),
                                       (float)__builtin_bit_cast(_Float16, (unsigned short)(r0 >> 16)))
@@ -1982,31 +1647,23 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                     }
                     if (__ballot(same_a || same_b) != 0ull) {
                         acc_any = true;
-                        if (mask_fma) {
-                            // (one fused multiply-add per value by a 0 / 1 lane mask instead of select + add: the emit is
-                            // bound by vector-instruction issue, DESIGN.md 3.2''; every value here is finite - a tile with a
-                            // non-finite gradient took the `dead` route - so x * 0 is 0)
-                            const float ma = same_a ? 1.0f : 0.0f;
+                        // (one fused multiply-add per value by a 0 / 1 lane mask instead of select + add: the emit is
+                        // bound by vector-instruction issue, DESIGN.md 3.2''; every value here is finite - a tile with a
+                        // non-finite gradient took the `dead` route - so x * 0 is 0)
+                        const float ma = same_a ? 1.0f : 0.0f;
 #pragma unroll
-                            for (uint32_t k = 0; k < 8; ++k) { acc0[k] = fmaf(a0[k], ma, acc0[k]); acc1[k] = fmaf(a1[k], ma, acc1[k]); }
-                            if (paired) {
-                                const float mb = same_b ? 1.0f : 0.0f;
+                        for (uint32_t k = 0; k < 8; ++k) { acc0[k] = fmaf(a0[k], ma, acc0[k]); acc1[k] = fmaf(a1[k], ma, acc1[k]); }
+                        if (paired) {
+                            const float mb = same_b ? 1.0f : 0.0f;
 #pragma unroll
-                                for (uint32_t k = 0; k < 8; ++k) { acc0[k] = fmaf(b0[k], mb, acc0[k]); acc1[k] = fmaf(b1[k], mb, acc1[k]); }
-                            }
-                        } else {
-#pragma unroll
-                        for (uint32_t k = 0; k < 8; ++k) {
-                            acc0[k] += (same_a ? a0[k] : 0.f) + (same_b ? b0[k] : 0.f);
-                            acc1[k] += (same_a ? a1[k] : 0.f) + (same_b ? b1[k] : 0.f);
-                        }
+                            for (uint32_t k = 0; k < 8; ++k) { acc0[k] = fmaf(b0[k], mb, acc0[k]); acc1[k] = fmaf(b1[k], mb, acc1[k]); }
                         }
                     }
                     bool ex_a = has_a && !same_a, ex_b = has_b && !same_b;
                     // the pair is (+eps, -eps) along one axis (the reference's stencil, network_tcnn.py:117-122: +x -x +y -y
                     // +z -z): a point that left the base cell is in the cell next to it - see face_pass
                     int axis = -1;
-                    if (paired && ps.mode == 1 && face_on) {
+                    if (paired && ps.mode == 1) {
                         const float4 oa = ps.offs[p], ob = ps.offs[p + 1u];
                         const int nz = (oa.x != 0.f) + (oa.y != 0.f) + (oa.z != 0.f);
                         if (nz == 1 && ob.x == -oa.x && ob.y == -oa.y && ob.z == -oa.z && oa.x + oa.y + oa.z > 0.f)
@@ -2180,13 +1837,6 @@ __global__ __launch_bounds__(kWave *kReduceWaves) void k_bin_reduce(const char *
 // its loads (16 waves per CU hid that already): a small gain, and the short batch wins.
 #define MI3D_REDUCE_U 4
 #endif
-#ifndef MI3D_TIMING_REDUCE_NO_FLUSH
-// TIMING ONLY: a reduce workgroup ends with up to 16 384 float atomics into the table (49 M per slice, at the chip's 21 G/s that
-// would be 2.3 ms).  Without them (round 6, product builds in one process, three slices: profiles/scatter_ab_libs_r06_reduce_flush_33GiB.json)
-// dense 47.51 -> 47.21 ms, captured real step 32.70 -> 32.65: they cost nothing - the wave ends behind them, the next workgroup's
-// LDS atomics run meanwhile.  (2 / 3 workgroups per bin instead of 4, same file: nothing either.)
-#define MI3D_TIMING_REDUCE_NO_FLUSH 0
-#endif
 #ifndef MI3D_REDUCE_BASE_SPLIT
 // reduce workgroups per average bin for slices of 30 M evaluations and more (plan_reduce_splits).  Round 6, product-grade builds
 // in one process (profiles/scatter_ab_libs_r06_reduce_split.json; dense / synthetic census / captured real step, ms): 3: 44.78 /
@@ -2194,57 +1844,24 @@ __global__ __launch_bounds__(kWave *kReduceWaves) void k_bin_reduce(const char *
 // its time goes
 #define MI3D_REDUCE_BASE_SPLIT 4
 #endif
-#ifndef MI3D_REDUCE_PIPE
-// the next batch's record loads issued BEFORE this batch's LDS atomics (two register sets, loop unrolled by two; the ISA
-// shows the older batch waited for with the newer one in flight).  Round 6, product-grade builds in one process
-// (profiles/scatter_ab_libs_r06_reduce_pipe.json; dense / synthetic census / captured real step): off 46.34 / 37.04 / 31.88 ms,
-// on 46.17 / 36.97 / 32.05, on with batches of 2: 46.14 / 36.87 / 31.82, of 8: 46.33 / 37.20 / 32.19 - nothing: the reduce does
-// not wait for its loads, it is bound by the LDS atomics themselves.  Off.
-#define MI3D_REDUCE_PIPE 0
-#endif
     constexpr uint32_t U = MI3D_REDUCE_U;  // records per lane and batch
-    // A region's records in batches of U per lane.  MI3D_REDUCE_PIPE: the NEXT batch's loads are issued before this batch's
-    // LDS atomics (the loads come back in order, so the wave waits for the older batch only): a wave that loads, waits ~2 us
-    // and then issues its 16 atomic instructions leaves the LDS idle whenever the CU's 16 waves happen to wait together.
+    // A region's records in batches of U per lane.  (The next batch's loads issued before this batch's LDS atomics, two
+    // register sets: tried in round 6, nothing - the reduce is bound by the atomics themselves)
     auto stream = [&](uint32_t cnt, auto load, auto add) __attribute__((always_inline)) {
-        if (cnt == 0u) return;
         using Rec = decltype(load(0u));
-        if (MI3D_REDUCE_PIPE) {
-            // two register sets, the loop unrolled by two so that neither is ever copied (a copy would wait for its loads);
-            // every load is unconditional from a clamped index (a conditional one is waited for where its block ends)
-            Rec ra[U], rb[U];
-            auto fetch = [&](Rec (&dst)[U], uint32_t at) __attribute__((always_inline)) {
+        for (uint32_t i0 = 0; i0 < cnt; i0 += kWave * U) {
+            Rec rec[U];
 #pragma unroll
-                for (uint32_t u = 0; u < U; ++u) { const uint32_t i = at + u * kWave + lane; dst[u] = load(i < cnt ? i : cnt - 1u); }
-            };
-            auto consume = [&](const Rec (&src)[U], uint32_t at) __attribute__((always_inline)) {
-#pragma unroll
-                for (uint32_t u = 0; u < U; ++u)
-                    if (at + u * kWave + lane < cnt) add(src[u]);
-            };
-            constexpr uint32_t B = kWave * U;
-            fetch(ra, 0u);
-            for (uint32_t i0 = 0; i0 < cnt; i0 += 2u * B) {
-                fetch(rb, i0 + B);
-                consume(ra, i0);
-                fetch(ra, i0 + 2u * B);
-                consume(rb, i0 + B);
+            for (uint32_t u = 0; u < U; ++u) {
+                // (unconditional, from a clamped index: a predicated load makes hipcc wait for it on the spot - the eight
+                // records "in flight" were eight HBM round trips in a row, each behind its own s_waitcnt vmcnt(0), until
+                // round 5 read the ISA; what a lane beyond cnt fetched is never looked at)
+                const uint32_t i = i0 + u * kWave + lane;
+                rec[u] = load(i < cnt ? i : cnt - 1u);
             }
-        } else {
-            for (uint32_t i0 = 0; i0 < cnt; i0 += kWave * U) {
-                Rec rec[U];
 #pragma unroll
-                for (uint32_t u = 0; u < U; ++u) {
-                    // (unconditional, from a clamped index: a predicated load makes hipcc wait for it on the spot - the eight
-                    // records "in flight" were eight HBM round trips in a row, each behind its own s_waitcnt vmcnt(0), until
-                    // round 5 read the ISA; what a lane beyond cnt fetched is never looked at)
-                    const uint32_t i = i0 + u * kWave + lane;
-                    rec[u] = load(i < cnt ? i : cnt - 1u);
-                }
-#pragma unroll
-                for (uint32_t u = 0; u < U; ++u)
-                    if (i0 + u * kWave + lane < cnt) add(rec[u]);
-            }
+            for (uint32_t u = 0; u < U; ++u)
+                if (i0 + u * kWave + lane < cnt) add(rec[u]);
         }
     };
     for (uint32_t r = split * kReduceWaves + wave_in_wg; r < n_waves; r += n_split * kReduceWaves) {
@@ -2302,14 +1919,10 @@ __global__ __launch_bounds__(kWave *kReduceWaves) void k_bin_reduce(const char *
     const uint32_t e0 = lb * kBinEntries;
     const uint32_t live = T.level[lvl].size - e0 < kBinEntries ? T.level[lvl].size - e0 : kBinEntries;  // last bin of a level
     float *dst = grad_table + ((size_t)T.level[lvl].offset + e0) * 2;
-#if MI3D_TIMING_REDUCE_NO_FLUSH   // TIMING ONLY (the gradient is lost): what the float atomics that end a reduce workgroup cost
-    if (live == 0xFFFFFFFFu) dst[threadIdx.x] = (float)((double)(long long)acc[threadIdx.x] * unscale);
-#else
     for (uint32_t i = threadIdx.x; i < live * 2; i += blockDim.x) {
         const long long a = (long long)acc[(i & 1u) * kBinEntries + (i >> 1)];
         if (a != 0) unsafeAtomicAdd(dst + i, (float)((double)a * unscale));
     }
-#endif
 }
 
 // grad[i] += sum over the n_rep private copies
@@ -2438,21 +2051,9 @@ int mi3d_grid_encode_points_planes_counted(const float *x, const float *x2, uint
                            st, ps, n, tab, T, n_lds, out, out_half, count);
         if (n_lds == T.n_levels) return (int)hipGetLastError();
     }
-    // The launch (or launches) of the XCD-planned kernel.  With the x-group evaluation (encode_group_hash, TRIPLE) the fine
-    // levels - hashed, x = cells per marching step >= 0.30: 3 workgroups per CU anyway - go to a kernel instance of their
-    // own: holding three points' rows in flight takes ~2 x the registers, which the coarse levels' 6 workgroups per CU
-    // cannot afford.  Each launch balances its own levels over the XCDs and claims tiles from its own counter slot.
-    uint32_t fine_mask = 0u;
-    for (uint32_t l = n_lds; l < T.n_levels; ++l) {
-        const double x = (double)step01 * (double)T.level[l].scale;
-        if (level_fast(T.level[l], 1).kind == kHashPow2 && encode_level_wgs_per_cu(x, 6u, 3u) == 3u) fine_mask |= 1u << l;
-    }
-    const int triple = MI3D_TUNE(MI3D_T_ENCODE_TRIPLE, MI3D_ENCODE_TRIPLE);
-    const bool split = triple != 0 && fine_mask != 0u && (variant & 3) == 3;
-    // One counter slot per launch, a ring of 64, zeroed in-stream right before the kernel; a hipEvent recorded behind the
-    // kernel says when the slot is free again: a slot is handed out only once that event has completed (whatever the
-    // stream) - otherwise the launch leaves the slot alone and deals
-    // its tiles statically (next == nullptr: the round-2 order, same planes, a few ms slower at C2 size) - never two live
+    // The XCD-planned kernel.  One counter slot per launch, a ring of 64, zeroed in-stream right before the kernel; a hipEvent
+    // recorded behind the kernel says when the slot is free again: a slot is handed out only once that event has completed
+    // (whatever the stream) - otherwise the launch leaves the slot alone and deals its tiles statically (next == nullptr: the round-2 order, same planes, a few ms slower at C2 size) - never two live
     // launches on one set of counters.  (Round 4 asked the previous owner's STREAM with hipStreamQuery: a destroyed
     // stream's handle is not a valid argument, and a launch captured into a hipGraph recorded the idle capture stream as
     // owner while the graph later replays elsewhere - ADVICE round 4.)  A launch that is being CAPTURED always deals
@@ -2513,33 +2114,23 @@ int mi3d_grid_encode_points_planes_counted(const float *x, const float *x2, uint
         }
     };
     const dim3 block(kWave * kWaves);
-    int rc = 0;
-    for (int part = 0; part < (split ? 2 : 1) && rc == 0; ++part) {
-        const uint32_t mask = split ? (part == 0 ? ~fine_mask : fine_mask) : 0xFFFFFFFFu;
-        const EncodePlan plan = make_encode_plan(T, tiles, step01, only_level, wgs_coarse, wgs_fine, n_lds, 1, mask);
-        uint32_t segs = 0;
-        for (uint32_t x = 0; x < kXcds; ++x) segs += plan.n_seg[x];
-        if (segs == 0) continue;   // (no level of this class)
-        const bool fine_part = split && part == 1;
-        const dim3 grid((fine_part ? wgs_fine : wgs_coarse) * kXcds);
-        uint32_t *next = nullptr;
-        int slot_used = -1;
-        rc = acquire_slot(next, slot_used);
-        if (rc != 0) break;
-#if defined(MI3D_DEV) || MI3D_ENCODE_TRIPLE   // (the product is built without the instance: measured, not taken - see MI3D_ENCODE_TRIPLE)
-        if (fine_part)
-            hipLaunchKernelGGL((k_grid_encode_planes<true, true, true>), grid, block, 0, st, ps, n, tab, T, plan, out, out_half, count, next);
-        else
-#endif
-        if ((variant & 3) == 3)
-            hipLaunchKernelGGL((k_grid_encode_planes<true, true>), grid, block, 0, st, ps, n, tab, T, plan, out, out_half, count, next);
-        else if (variant & 1)
-            hipLaunchKernelGGL((k_grid_encode_planes<true, false>), grid, block, 0, st, ps, n, tab, T, plan, out, out_half, count, next);
-        else
-            hipLaunchKernelGGL((k_grid_encode_planes<false, false>), grid, block, 0, st, ps, n, tab, T, plan, out, out_half, count, next);
-        rc = (int)hipGetLastError();
-        slot_done(slot_used);
-    }
+    const EncodePlan plan = make_encode_plan(T, tiles, step01, only_level, wgs_coarse, wgs_fine, n_lds);
+    uint32_t segs = 0;
+    for (uint32_t x = 0; x < kXcds; ++x) segs += plan.n_seg[x];
+    if (segs == 0) return 0;   // (no level left for this kernel)
+    const dim3 grid(wgs_coarse * kXcds);
+    uint32_t *next = nullptr;
+    int slot_used = -1;
+    int rc = acquire_slot(next, slot_used);
+    if (rc != 0) return rc;
+    if ((variant & 3) == 3)
+        hipLaunchKernelGGL((k_grid_encode_planes<true, true>), grid, block, 0, st, ps, n, tab, T, plan, out, out_half, count, next);
+    else if (variant & 1)
+        hipLaunchKernelGGL((k_grid_encode_planes<true, false>), grid, block, 0, st, ps, n, tab, T, plan, out, out_half, count, next);
+    else
+        hipLaunchKernelGGL((k_grid_encode_planes<false, false>), grid, block, 0, st, ps, n, tab, T, plan, out, out_half, count, next);
+    rc = (int)hipGetLastError();
+    slot_done(slot_used);
     return rc;
 }
 
@@ -2647,7 +2238,6 @@ int mi3d_grid_scatter_binned_plus(const float *x, const float *x2, uint32_t n, c
     coarse_mask &= dev_mask;
     const uint32_t fine_waves = fine_mask ? plan.level_waves[__builtin_ctz(fine_mask)] : 0u;
     const uint32_t coarse_waves = coarse_mask ? plan.level_waves[__builtin_ctz(coarse_mask)] : 0u;
-    const uint32_t emit_order = (uint32_t)MI3D_TUNE(MI3D_T_EMIT_ORDER, MI3D_EMIT_ORDER_DEFAULT);
     for (uint64_t s0 = 0; s0 < n; s0 += n_slice) {
         const uint32_t s1 = (uint32_t)((s0 + n_slice < n) ? s0 + n_slice : n);
         if (fine_waves + coarse_waves)
@@ -2656,11 +2246,11 @@ int mi3d_grid_scatter_binned_plus(const float *x, const float *x2, uint32_t n, c
             (void)hipMemsetAsync(level_max + plan.claim0, 0, 4 * sizeof(uint32_t), st);   // the roles' tile-claim counters
             if (dout_half)
                 hipLaunchKernelGGL(k_bin_emit<true>, eg, eb, lds, st, ps, (uint32_t)s0, s1, dout_planes, plane_rows, n, extra0, T,
-                                   plan, merge_levels, fine_mask, fine_waves, coarse_mask, coarse_waves, emit_order,
+                                   plan, merge_levels, fine_mask, fine_waves, coarse_mask, coarse_waves,
                                    reinterpret_cast<BinRecord *>(arena), counts, level_max, grad_params);
             else
                 hipLaunchKernelGGL(k_bin_emit<false>, eg, eb, lds, st, ps, (uint32_t)s0, s1, dout_planes, plane_rows, n, extra0, T,
-                                   plan, merge_levels, fine_mask, fine_waves, coarse_mask, coarse_waves, emit_order,
+                                   plan, merge_levels, fine_mask, fine_waves, coarse_mask, coarse_waves,
                                    reinterpret_cast<BinRecord *>(arena), counts, level_max, grad_params);
         }
         const uint32_t n_split = (uint64_t)(s1 - s0) * P >= 30000000ull ? (uint32_t)MI3D_REDUCE_BASE_SPLIT : ((uint64_t)(s1 - s0) * P >= 8000000ull ? 2u : 1u);

@@ -1,6 +1,6 @@
 """A/B of the plane gather (k_grid_encode_planes + the LDS levels' kernel) across several PRODUCT-GRADE builds of the library in
 ONE process, like tools/scatter_ab_libs.py for the scatter:
-    python tools/gather_ab_libs.py --libs make-it-3d_amd/csrc/libmi3d.so,tools/bin/libmi3d_nosteal.so --out gpurun_out/gather_ab_libs.json
+    python tools/gather_ab_libs.py --libs make-it-3d_amd/csrc/libmi3d.so,tools/bin/libmi3d_variant.so --out gather_ab_libs.json
 The 13-point gather of the C2-dense view into binary16 planes (the autocast layout), the libraries interleaved (A B A B ...)
 `--rounds` times; every library's planes must be bit-identical to the first one's."""
 import argparse

@@ -15,7 +15,7 @@ os.environ.setdefault("MI3D_LIB", os.path.join(ROOT, "tools", "bin", "libmi3d_de
 import torch  # noqa: E402
 
 T_ENCODE_VARIANT, T_ENCODE_WGS, T_ENCODE_ONLY_LEVEL, T_EMIT_FINE, T_EMIT_COARSE = 0, 1, 2, 3, 4
-T_MLP_WGS, T_REUSE_LEVELS = 7, 10
+T_MLP_WGS = 7
 
 
 def timeit(fn, iters=3, warmup=1):
@@ -38,7 +38,7 @@ def main():
     ap.add_argument("--bitfield", default="dense")
     ap.add_argument("--out", default="gpurun_out/kbench.json")
     ap.add_argument("--half-planes", action="store_true", help="binary16 feature / gradient planes (the autocast layout)")
-    ap.add_argument("--dev", default="", help="tunables set before anything runs, e.g. 10=1,3=2048 (csrc/mi3d_dev.h)")
+    ap.add_argument("--dev", default="", help="tunables set before anything runs, e.g. 4=8192,3=2048 (csrc/mi3d_dev.h)")
     ap.add_argument("--real-census", action="store_true",
                     help="scatter benchmarks: zero the random gradient pairs independently with the per-level non-zero "
                          "fractions bench.py's census measured on a real step (regulariser pass + deferred point 0)")
@@ -111,26 +111,6 @@ def main():
         res["encode_ms"] = timeit(encode, 5)
         it = torch.int16 if feats.dtype == torch.float16 else torch.int32   # bit-level checksum per level (A/B across builds)
         res["encode_checksum"] = [int(feats[l].view(it).to(torch.int64).sum()) for l in range(feats.shape[0])]
-    if "encode_r05" in what:  # round 5: the x-group evaluation of the fine hashed levels (tunable 18), whole gather and per level
-        tune(18, 0)
-        encode()
-        ref = feats.clone()
-        out = {}
-        for rep in range(3):
-            for v in (0, 1):
-                tune(18, v)
-                feats.zero_()
-                out[f"triple{v}_rep{rep}_ms"] = timeit(encode, a.iters)
-                out[f"triple{v}_rep{rep}_bitexact"] = bool(torch.equal(feats, ref))
-        for l in range(5, 16):
-            tune(T_ENCODE_ONLY_LEVEL, l)
-            for v in (0, 1):
-                tune(18, v)
-                out[f"level{l}_triple{v}_ms"] = timeit(encode, a.iters)
-        tune(T_ENCODE_ONLY_LEVEL, -1)
-        tune(18, -1)
-        del ref
-        res["encode_r05"] = out
     if "encode_sweep" in what:  # workgroups per CU for the coarse / fine segments, tiles claimed
         out = {}
         for c in (4, 6, 7):
@@ -201,14 +181,10 @@ def main():
             L.call("mi3d_mlp_backward", L.ptr(feats), P * n, int(feats.dtype == torch.float16), L.ptr(dh), rows,
                    *[L.ptr(t) for t in ws], 32, 64, 4, 1,
                    L.ptr(dplanes), rows, *[L.ptr(g) for g in grads], L.stream())
-        for v in (0, 3):   # 0: round 3's kernels (two waves per SIMD, VGPR-form MFMA, transposes); 3: round 2's
-            tune(6, v)
-            res[f"mlp_fwd_variant{v}_ms"] = timeit(fwd, a.iters)
-            for w in (1, 2):
-                tune(T_MLP_WGS, w)
-                res[f"mlp_bwd_variant{v}_wgs{w}_ms"] = timeit(bwd, a.iters)
-            tune(T_MLP_WGS, -1)
-        tune(6, -1)
+        for w in (1, 2):
+            tune(T_MLP_WGS, w)
+            res[f"mlp_bwd_wgs{w}_ms"] = timeit(bwd, a.iters)
+        tune(T_MLP_WGS, -1)
         for w in (2, 3, 4, 5, 6):
             tune(11, w)   # MI3D_T_MLP_FWD_WGS_PER_CU
             res[f"mlp_fwd_wgs{w}_ms"] = timeit(fwd, a.iters)
@@ -233,7 +209,7 @@ def main():
         for census in (False, True):
             a.real_census = census
             g = gradient_planes(feats.dtype)
-            for name, kvs in (("base", {}), ("no_face_pass", {10: 0x10000}), ("merge30", {15: 30}), ("merge58", {15: 58}),
+            for name, kvs in (("base", {}), ("merge30", {15: 30}), ("merge58", {15: 58}),
                               ("fine_waves1024", {3: 1024}), ("fine_waves1280", {3: 1280}), ("fine_waves2048", {3: 2048}),
                               ("coarse_waves8192", {4: 8192}), ("base_again", {})):
                 for k, v in kvs.items():
@@ -244,79 +220,6 @@ def main():
                     tune(k, -1)
             del g
         res["scatter13_plus_ms"] = out
-    if "scatter_r05" in what:  # round 5: the coarse role's run-merged group flush, alone and in the whole scatter, with the level
-        # threshold and the fine wave count re-swept around it; wall-clock stamps per configuration so that a clock / power
-        # log sampled beside this process can be laid over the timings.  Dev bit 0x20000 of tunable 10 FLIPS the flush
-        # against the build's default (MI3D_RUN_MERGE: 0 when profiles/kbench_r05_scatter_run_merge.json was taken - its
-        # "run_merge" rows are the merged flush - and 1 since)
-        import time
-        out, stamps = {}, []
-        ex = torch.randn(16, n, 2, device=dev).to(feats.dtype)
-        RM = 0x20000
-        for census in (False, True):
-            a.real_census = census
-            g = gradient_planes(feats.dtype)
-            tag = "real_" if census else "dense_"
-            ref = None
-            MF = 0x40000   # flips the masked fused multiply-add of the coarse role's register sums (MI3D_MASK_FMA)
-            for name, kvs in (("base", {}), ("run_merge", {10: RM}), ("base_2", {}), ("run_merge_2", {10: RM}),
-                              ("mask_fma", {10: MF}), ("base_2b", {}), ("mask_fma_2", {10: MF}), ("base_2c", {}),
-                              ("mask_fma_3", {10: MF}),
-                              ("coarse_only_mask_fma", {5: 0x007F, 10: MF}),
-                              ("dyn_idx", {10: 0x80000}), ("base_2d", {}), ("dyn_idx_2", {10: 0x80000}), ("base_2e", {}),
-                              ("dyn_idx_3", {10: 0x80000}),
-                              ("coarse_only_base", {5: 0x007F}), ("coarse_only_run_merge", {5: 0x007F, 10: RM}),
-                              ("fine_only", {5: 0xFF80}),
-                              ("run_merge_merge30", {10: RM, 15: 30}), ("run_merge_merge58", {10: RM, 15: 58}),
-                              ("run_merge_fine1280", {10: RM, 3: 1280}), ("run_merge_fine2048", {10: RM, 3: 2048}),
-                              ("base_3", {}), ("run_merge_3", {10: RM})):
-                for k, v in kvs.items():
-                    tune(k, v)
-                t0 = time.time()
-                out[tag + name] = timeit(lambda: field_ops.scatter_binned(
-                    xs, xs2, offs, P0, 1.0, g, cfg, 2 * 3 ** 0.5 / 1024, 12196240, extra0=ex), a.iters)
-                stamps.append((tag + name, t0, time.time()))
-                if name in ("base", "run_merge", "mask_fma", "dyn_idx"):   # same gradient, up to the fp32 rounding of the register sums
-                    got = field_ops.scatter_binned(xs, xs2, offs, P0, 1.0, g, cfg, 2 * 3 ** 0.5 / 1024, 12196240, extra0=ex)
-                    if ref is None:
-                        ref = got
-                    else:
-                        out[tag + name + "_max_err_rel"] = float((got - ref).abs().max() / ref.abs().max())
-                    del got
-                for k in kvs:
-                    tune(k, -1)
-            del g, ref
-        res["scatter_r05_ms"] = out
-        res["scatter_r05_stamps"] = stamps
-    if "scatter_diag" in what:  # the coarse role alone, with its gather-table atomics switched off (timing only)
-        g = gradient_planes(feats.dtype)
-        out = {}
-        tune(5, 0x00FF)
-        for name, flags in (("all", 0), ("no_sum_adds", 0x100), ("no_cas", 0x200), ("neither", 0x300)):
-            tune(10, flags)
-            out[name] = timeit(lambda: field_ops.scatter_binned(xs, xs2, offs, P0, 1.0, g, cfg, 2 * 3 ** 0.5 / 1024,
-                                                                12196240), 2)
-        tune(10, -1)
-        for l in (0, 2, 4, 5, 7):
-            tune(5, 1 << l)
-            for name, flags in (("all", 0), ("neither", 0x300)):
-                tune(10, flags)
-                out[f"level{l}_{name}"] = timeit(lambda: field_ops.scatter_binned(
-                    xs, xs2, offs, P0, 1.0, g, cfg, 2 * 3 ** 0.5 / 1024, 12196240), 2)
-        tune(10, -1)
-        tune(5, -1)
-        res["scatter13_dense_coarse_role_ms"] = out
-        out = {}
-        tune(5, 0xFF00)   # the fine role alone: sorted but not stored / cells, entries and histogram only
-        for name, flags in (("all", 0), ("no_region_stores", 0x800), ("through_pass2", 0x4000), ("through_scan", 0x2000),
-                            ("pass1_only", 0x1000), ("all_again", 0)):
-            tune(10, flags)
-            out[name] = timeit(lambda: field_ops.scatter_binned(xs, xs2, offs, P0, 1.0, g, cfg, 2 * 3 ** 0.5 / 1024,
-                                                                12196240), 2)
-        tune(10, -1)
-        tune(5, -1)
-        res["scatter13_dense_fine_role_ms"] = out
-        del g
     if "scatter_levels" in what:  # the 13-point scatter per role and per level (dev level mask), dense random gradients
         g = gradient_planes(feats.dtype)
         masks = {"all": 0xFFFF, "fine_8_15": 0xFF00, "coarse_0_7": 0x00FF}
@@ -352,14 +255,11 @@ def main():
         res["planes_dtype"] = str(feats.dtype)
         res["scatter_fp32_P1_ms"] = timeit(lambda: field_ops.scatter_binned(
             xs, None, offs[:1], 1, 1.0, g1, cfg, step, 12196240), a.iters)
-        for order in (0, 1):  # csrc/mi3d_dev.h MI3D_T_EMIT_ORDER: the fine role tile-major / level-major
-            tune(10, order)
-            for fw in (768, 1024, 1536, 2048, 3072):
-                tune(T_EMIT_FINE, fw)
-                res[f"scatter_fp32_P13_order{order}_fine_waves{fw}_ms"] = timeit(lambda: field_ops.scatter_binned(
-                    xs, xs2, offs, P0, 1.0, g, cfg, step, 12196240), a.iters)
+        for fw in (768, 1024, 1536, 2048, 3072):
+            tune(T_EMIT_FINE, fw)
+            res[f"scatter_fp32_P13_fine_waves{fw}_ms"] = timeit(lambda: field_ops.scatter_binned(
+                xs, xs2, offs, P0, 1.0, g, cfg, step, 12196240), a.iters)
         tune(T_EMIT_FINE, -1)
-        tune(10, -1)
     print(json.dumps(res, indent=1))
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
     json.dump(res, open(a.out, "w"), indent=1)

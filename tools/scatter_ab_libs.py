@@ -1,8 +1,8 @@
 """A/B of the binned scatter across several PRODUCT-GRADE builds of the library in ONE process (the tools build carries
 every variant's code behind run-time switches, which changes the register allocation of all of them: a switch that is
 'off' there is not the product).  Variant builds: `python make-it-3d_amd/build.py`-style, e.g.
-    python -c "import sys; sys.path.insert(0,'make-it-3d_amd'); import build; build.build(out='tools/bin/libmi3d_dyn1.so', defines=('-DMI3D_DYN_IDX=1',))"
-    python tools/scatter_ab_libs.py --libs make-it-3d_amd/csrc/libmi3d.so,tools/bin/libmi3d_dyn1.so --out gpurun_out/scatter_ab_libs.json
+    python -c "import sys; sys.path.insert(0,'make-it-3d_amd'); import build; build.build(out='tools/bin/libmi3d_u8.so', defines=('-DMI3D_REDUCE_U=8',))"
+    python tools/scatter_ab_libs.py --libs make-it-3d_amd/csrc/libmi3d.so,tools/bin/libmi3d_u8.so --out scatter_ab_libs.json
 The 13-point scatter + deferred point-0 pair of the C2-dense view on dense random binary16 gradients and on a real step's
 zero census, the libraries interleaved (A B A B ...) `--rounds` times; every library's gradient against the first one's."""
 import argparse
