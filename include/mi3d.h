@@ -380,8 +380,29 @@ int mi3d_adan_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq,
  * `workspace` holds the per-tile point lists (mi3d_points_rasterize_workspace bytes cover the worst case).
  * mi3d_points_composite_forward = alphas = 1 - sqrt(clamp(0.1 dists / radius^2, 1e-3, 1)) (refine_utils.py:321-326)
  * followed by compositing.alpha_composite: out [C,H,W] from features [P,C] (C <= 32), front to back.
- * mi3d_points_composite_backward ACCUMULATES d out / d features into grad_features [P,C] (caller zeroes it); the point
- * positions carry no gradient on this path (the reference optimises colours and features, nerf/utils.py:826-831). */
+ * mi3d_points_composite_backward ACCUMULATES d out / d features into grad_features [P,C] (caller zeroes it).
+ *
+ * Gradient for the point positions (and, through the caller's projection, the camera) - this project's own contract:
+ * pytorch3d differentiates rasterize_points through `dists` and alpha_composite through `alphas`, but it is absent and
+ * unpinned, the standing of the rest of this Part.  For one pixel let its used slots be k = 0 .. n-1, front to back as
+ * idx stores them (slots with idx < 0 are skipped, exactly as in the forward), and
+ *     u_k = 0.1 dist_k / radius^2,   a_k = 1 - sqrt(clamp(u_k, 1e-3, 1)),   T_k = prod_{j<k} (1 - a_j),
+ *     s_k = sum_c grad_out[c, pixel] * features[idx_k, c].
+ * Back to front, R_{n-1} = 0 and R_{k-1} = a_k s_k + (1 - a_k) R_k.  Then
+ *     dL/da_k    = T_k (s_k - R_k)                      (no division by 1 - a; pytorch3d divides by 1 - a + eps, we do not)
+ *     dL/ddist_k = dL/da_k * (-0.05 / (radius^2 sqrt(u_k)))   where 1e-3 <= u_k <= 1, and 0 outside
+ *                  (the closed interval is torch.clamp's gradient; since dist < radius^2 only the lower clamp ever binds,
+ *                  for points within a tenth of the radius of the pixel centre)
+ *     dL/dx_p   += 2 (x_p - xf) dL/ddist_k, y likewise, with (xf, yf) the pixel centre mi3d_points_rasterize measures
+ *                  dist from (pix_to_ndc of the mirrored pixel index);   dL/dz_p = 0: depth decides only the order.
+ * This is the exact derivative of the forward for FIXED idx, i.e. almost everywhere.  The jump at the edge of a point's
+ * disc - alpha drops from 1 - sqrt(0.1) = 0.68 to nothing - and the changes of the depth order are NOT differentiated.
+ * mi3d_points_composite_backward_dists writes grad_dists [H,W,K] with plain stores (0 in unused slots and where the
+ * clamp binds): reproducible run to run.  K <= 8, C <= 32; argument checks otherwise those of
+ * mi3d_points_composite_backward.
+ * mi3d_points_rasterize_backward ACCUMULATES into the x and y columns of grad_points [P,3] (caller zeroes it; the z
+ * column is never touched) with float atomics, for every slot idx names - no test against the disc; an index outside
+ * [0, P) is skipped.  The sum's last bits depend on the arrival order. */
 size_t mi3d_points_rasterize_workspace(uint32_t P, uint32_t H, uint32_t W, float radius);
 int mi3d_points_rasterize(const float *points_ndc, uint32_t P, uint32_t H, uint32_t W, float radius,
                           uint32_t points_per_pixel, void *workspace, size_t workspace_bytes, int32_t *idx, float *zbuf,
@@ -391,6 +412,11 @@ int mi3d_points_composite_forward(const int32_t *idx, const float *dists, uint32
 int mi3d_points_composite_backward(const int32_t *idx, const float *dists, uint32_t H, uint32_t W,
                                    uint32_t points_per_pixel, const float *grad_out, uint32_t C, double radius,
                                    float *grad_features, void *stream);
+int mi3d_points_composite_backward_dists(const int32_t *idx, const float *dists, uint32_t H, uint32_t W,
+                                         uint32_t points_per_pixel, const float *grad_out, const float *features,
+                                         uint32_t C, double radius, float *grad_dists, void *stream);
+int mi3d_points_rasterize_backward(const float *points_ndc, uint32_t P, const int32_t *idx, const float *grad_dists,
+                                   uint32_t H, uint32_t W, uint32_t points_per_pixel, float *grad_points, void *stream);
 
 /* ------------------------------------------------------------------ Part 8: marching cubes (mesh export) */
 

@@ -15,6 +15,9 @@
 //   k_points_composite_fwd / _bwd   thread = pixel, front-to-back over the K slots, C feature channels in registers;
 //       the backward adds w_k * dout into the 76-byte feature row of each hit point with float atomics (a few million
 //       requests per 512^2 image - far below the rate that forced the hash-grid scatter through memory).
+//   k_points_composite_bwd_dists / k_raster_bwd_points   the position gradient, launched only when something upstream
+//       of the projection requires grad: d out / d dists with plain stores (reproducible), then two float atomics per
+//       slot into the (x, y) of the hit point - 2/C of the feature gradient's requests.
 #include <hip/hip_runtime.h>
 
 #include "../../include/mi3d.h"
@@ -235,6 +238,70 @@ __global__ void k_points_composite_bwd(const int32_t *__restrict__ idx, const fl
     }
 }
 
+// d out / d dists for fixed idx (include/mi3d.h Part 7, "gradient for the point positions"): thread = pixel.  Pass 1
+// walks the slots front to back as the forward does and keeps a_k, s_k = <dout, features[idx_k]>, T_k and the clamp's
+// own derivative factor in registers; pass 2 runs R back to front.  No division by 1 - a anywhere, plain stores only.
+__global__ __launch_bounds__(256) void k_points_composite_bwd_dists(const int32_t *__restrict__ idx, const float *__restrict__ dists,
+                                             uint32_t n_pix, uint32_t K, const float *__restrict__ dout,
+                                             const float *__restrict__ feats, uint32_t C, float radius2,
+                                             float *__restrict__ grad_dists) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= n_pix) return;
+    float g[kMaxC];
+#pragma unroll
+    for (int c = 0; c < kMaxC; ++c) g[c] = (uint32_t)c < C ? dout[(size_t)c * n_pix + pix] : 0.f;
+    float a[kMaxK], s[kMaxK], Tk[kMaxK], da[kMaxK];  // da = d a_k / d dist_k (0: unused slot or the clamp binds)
+    float T = 1.0f;
+#pragma unroll
+    for (int k = 0; k < kMaxK; ++k) {
+        a[k] = 0.f; s[k] = 0.f; Tk[k] = 0.f; da[k] = 0.f;
+        if ((uint32_t)k >= K) continue;
+        const int32_t p = idx[(size_t)pix * K + k];
+        if (p < 0) continue;
+        const float u = (0.1f * dists[(size_t)pix * K + k]) / radius2;  // point_alpha's own operations
+        const float r = sqrtf(fminf(1.0f, fmaxf(1e-3f, u)));
+        a[k] = 1.0f - r;
+        if (u >= 1e-3f && u <= 1.0f) da[k] = -0.05f / (radius2 * r);
+        const float *f = feats + (size_t)p * C;
+        float dot = 0.f;
+#pragma unroll
+        for (int c = 0; c < kMaxC; ++c)
+            if ((uint32_t)c < C) dot += g[c] * f[c];
+        s[k] = dot;
+        Tk[k] = T;
+        T *= 1.0f - a[k];
+    }
+    float R = 0.f;
+#pragma unroll
+    for (int k = kMaxK - 1; k >= 0; --k) {
+        if ((uint32_t)k >= K) continue;
+        // an unused slot has a = s = 0: it leaves R as it is, and its da = 0 writes the 0 the contract asks for
+        grad_dists[(size_t)pix * K + k] = da[k] != 0.f ? Tk[k] * (s[k] - R) * da[k] : 0.f;
+        R = a[k] * s[k] + (1.0f - a[k]) * R;
+    }
+}
+
+// d dists / d (x, y) of the points: dist = (x_p - xf)^2 + (y_p - yf)^2 with (xf, yf) the pixel centre k_raster_tiles
+// uses.  Thread = pixel, two float atomics per slot that carries a gradient; idx is the truth (no disc test), z is never
+// written.  An index outside [0, P) is skipped.
+__global__ __launch_bounds__(256) void k_raster_bwd_points(const float *__restrict__ ndc, uint32_t P, const int32_t *__restrict__ idx,
+                                    const float *__restrict__ grad_dists, int H, int W, uint32_t K,
+                                    float *__restrict__ grad_points) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= (uint32_t)H * (uint32_t)W) return;
+    const int xi = (int)(pix % (uint32_t)W), yi = (int)(pix / (uint32_t)W);
+    const float xf = pix_to_ndc(W - 1 - xi, W, H), yf = pix_to_ndc(H - 1 - yi, H, W);
+    for (uint32_t k = 0; k < K; ++k) {
+        const int32_t p = idx[(size_t)pix * K + k];
+        if (p < 0 || (uint32_t)p >= P) continue;
+        const float gd = grad_dists[(size_t)pix * K + k];
+        if (gd == 0.f) continue;
+        const float x = ndc[(size_t)p * 3], y = ndc[(size_t)p * 3 + 1];
+        unsafeAtomicAdd(grad_points + (size_t)p * 3, 2.0f * (x - xf) * gd);
+        unsafeAtomicAdd(grad_points + (size_t)p * 3 + 1, 2.0f * (y - yf) * gd);
+    }
+}
+
 uint32_t tiles_per_point_max(const RasterGeom &g) {
     const float rx = g.radius * (float)g.W / g.range_x + 1.0f, ry = g.radius * (float)g.H / g.range_y + 1.0f;
     const uint32_t nx = (uint32_t)((2.0f * rx + 2.0f) / kTilePx) + 2u, ny = (uint32_t)((2.0f * ry + 2.0f) / kTilePx) + 2u;
@@ -296,6 +363,29 @@ int mi3d_points_composite_backward(const int32_t *idx, const float *dists, uint3
     if (n_pix == 0) return 0;
     hipLaunchKernelGGL(k_points_composite_bwd, dim3((n_pix + 255) / 256), dim3(256), 0, as_stream(stream), idx, dists,
                        n_pix, points_per_pixel, grad_out, C, (float)(radius * radius), grad_features);
+    return (int)hipGetLastError();
+}
+
+int mi3d_points_composite_backward_dists(const int32_t *idx, const float *dists, uint32_t H, uint32_t W,
+                                         uint32_t points_per_pixel, const float *grad_out, const float *features,
+                                         uint32_t C, double radius, float *grad_dists, void *stream) {
+    if (C == 0 || C > (uint32_t)kMaxC || !(radius > 0.f)) return (int)hipErrorInvalidValue;
+    if (points_per_pixel > (uint32_t)kMaxK) return (int)hipErrorInvalidValue;  // the slots live in registers here
+    const uint32_t n_pix = H * W;
+    if (n_pix == 0 || points_per_pixel == 0) return 0;
+    hipLaunchKernelGGL(k_points_composite_bwd_dists, dim3((n_pix + 255) / 256), dim3(256), 0, as_stream(stream), idx,
+                       dists, n_pix, points_per_pixel, grad_out, features, C, (float)(radius * radius), grad_dists);
+    return (int)hipGetLastError();
+}
+
+int mi3d_points_rasterize_backward(const float *points_ndc, uint32_t P, const int32_t *idx, const float *grad_dists,
+                                   uint32_t H, uint32_t W, uint32_t points_per_pixel, float *grad_points, void *stream) {
+    if (H == 0 || W == 0 || points_per_pixel == 0 || points_per_pixel > (uint32_t)kMaxK)
+        return (int)hipErrorInvalidValue;  // mi3d_points_rasterize's own checks on these arguments
+    if (P == 0) return 0;
+    const uint32_t n_pix = H * W;
+    hipLaunchKernelGGL(k_raster_bwd_points, dim3((n_pix + 255) / 256), dim3(256), 0, as_stream(stream), points_ndc, P, idx,
+                       grad_dists, (int)H, (int)W, points_per_pixel, grad_points);
     return (int)hipGetLastError();
 }
 

@@ -72,6 +72,8 @@ _SIGNATURES = {
     "mi3d_points_rasterize": [vp, u32, u32, u32, f32, u32, vp, C.c_size_t, vp, vp, vp, vp],
     "mi3d_points_composite_forward": [vp, vp, u32, u32, u32, vp, u32, C.c_double, vp, vp],
     "mi3d_points_composite_backward": [vp, vp, u32, u32, u32, vp, u32, C.c_double, vp, vp],
+    "mi3d_points_composite_backward_dists": [vp, vp, u32, u32, u32, vp, vp, u32, C.c_double, vp, vp],
+    "mi3d_points_rasterize_backward": [vp, u32, vp, vp, u32, u32, u32, vp, vp],
     # Part 8 ------------------------------------------------------------------------------------------
     "mi3d_mc_count": [vp, u32, u32, u32, f32, vp, C.c_size_t, vp, vp],
     "mi3d_mc_scan": [u32, u32, u32, vp, C.c_size_t, vp, vp],

@@ -4,7 +4,8 @@
 pytorch3d calls (rasterize_points, compositing.alpha_composite) replaced by the HIP kernels of csrc/raster.hip
 (C ABI Part 7); the projection in front of them is the reference's own handful of torch ops, kept verbatim in
 meaning so the NDC coordinates are the ones pytorch3d would have been given.  Differentiable w.r.t. the point
-features (colours + 16 learned channels), which is what the reference optimises (nerf/utils.py:826-831).
+features (colours + 16 learned channels), which is what the reference optimises (nerf/utils.py:826-831), and - as
+pytorch3d's two calls are - w.r.t. the point positions and the camera, for fixed visibility (include/mi3d.h Part 7).
 
 `UNet` restates nerf/unet.py:111-172 (gated convolutions, multi-scale input, bilinear upsampling) on stock torch
 modules with the reference's module names, so its state_dict loads reference checkpoints.
@@ -38,29 +39,33 @@ class _PointComposite(Function):
         out = torch.empty(Cn, H, W, dtype=torch.float32, device=feats.device)
         L.launch("mi3d_points_composite_forward", feats, L.ptr(idx), L.ptr(dists), H, W, K, L.ptr(feats), Cn,
                  C.c_double(radius), L.ptr(out))
-        ctx.save_for_backward(idx, dists)
+        # the features are kept only when `dists` wants a gradient (learnable positions or camera): s_k needs them
+        want_dists = ctx.needs_input_grad[2]
+        ctx.save_for_backward(idx, dists, *((feats,) if want_dists else ()))
         ctx.meta = (P, Cn, float(radius))
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        idx, dists = ctx.saved_tensors
+        idx, dists = ctx.saved_tensors[:2]
         P, Cn, radius = ctx.meta
         H, W, K = idx.shape
         dout = L.dev_f32(dout.float().contiguous(), "grad")
-        grad = torch.zeros(P, Cn, dtype=torch.float32, device=dout.device)
-        L.launch("mi3d_points_composite_backward", dout, L.ptr(idx), L.ptr(dists), H, W, K, L.ptr(dout), Cn,
-                 C.c_double(radius), L.ptr(grad))
-        return grad, None, None, None
+        grad = gdists = None
+        if ctx.needs_input_grad[0]:
+            grad = torch.zeros(P, Cn, dtype=torch.float32, device=dout.device)
+            L.launch("mi3d_points_composite_backward", dout, L.ptr(idx), L.ptr(dists), H, W, K, L.ptr(dout), Cn,
+                     C.c_double(radius), L.ptr(grad))
+        if ctx.needs_input_grad[2]:
+            feats = ctx.saved_tensors[2]
+            gdists = torch.empty(H, W, K, dtype=torch.float32, device=dout.device)
+            L.launch("mi3d_points_composite_backward_dists", dout, L.ptr(idx), L.ptr(dists), H, W, K, L.ptr(dout),
+                     L.ptr(feats), Cn, C.c_double(radius), L.ptr(gdists))
+        return grad, None, gdists, None
 
 
-def rasterize_points(points_ndc, image_size, radius, points_per_pixel):
-    """pytorch3d.renderer.points.rasterize_points for one cloud: (idx int32 [H,W,K], zbuf, dists) from NDC points
-    [P,3]; unused slots hold -1."""
-    H, W = (image_size, image_size) if isinstance(image_size, int) else image_size
-    pts = L.dev_f32(points_ndc.detach().contiguous(), "points", 3)
+def _rasterize(pts, H, W, radius, K):
     P, dev = pts.shape[0], pts.device
-    K = int(points_per_pixel)
     need = L.lib().mi3d_points_rasterize_workspace(P, H, W, float(radius))
     ws = torch.empty(max(int(need), 64), dtype=torch.uint8, device=dev)
     idx = torch.empty(H, W, K, dtype=torch.int32, device=dev)
@@ -71,19 +76,53 @@ def rasterize_points(points_ndc, image_size, radius, points_per_pixel):
     return idx, zbuf, dists
 
 
+class _RasterizePoints(Function):
+    """The rasteriser with `dists` differentiable w.r.t. the NDC x, y of the points for fixed idx (include/mi3d.h
+    Part 7); idx and zbuf stay non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, points_ndc, H, W, radius, K):
+        pts = L.dev_f32(points_ndc.detach().contiguous(), "points", 3)
+        idx, zbuf, dists = _rasterize(pts, H, W, radius, K)
+        ctx.save_for_backward(pts, idx)
+        ctx.mark_non_differentiable(idx, zbuf)
+        return idx, zbuf, dists
+
+    @staticmethod
+    def backward(ctx, _gidx, _gzbuf, gdists):
+        pts, idx = ctx.saved_tensors
+        H, W, K = idx.shape
+        gdists = L.dev_f32(gdists.float().contiguous(), "grad")
+        grad = torch.zeros_like(pts)
+        L.launch("mi3d_points_rasterize_backward", pts, L.ptr(pts), pts.shape[0], L.ptr(idx), L.ptr(gdists), H, W, K,
+                 L.ptr(grad))
+        return grad, None, None, None, None
+
+
+def rasterize_points(points_ndc, image_size, radius, points_per_pixel):
+    """pytorch3d.renderer.points.rasterize_points for one cloud: (idx int32 [H,W,K], zbuf, dists) from NDC points
+    [P,3]; unused slots hold -1.  When `points_ndc` requires grad, `dists` carries the gradient to its x and y columns
+    (for fixed idx: neither the disc's edge nor the depth order is differentiated)."""
+    H, W = (image_size, image_size) if isinstance(image_size, int) else image_size
+    if torch.is_grad_enabled() and points_ndc.requires_grad:
+        return _RasterizePoints.apply(points_ndc, H, W, float(radius), int(points_per_pixel))
+    pts = L.dev_f32(points_ndc.detach().contiguous(), "points", 3)
+    return _rasterize(pts, H, W, radius, int(points_per_pixel))
+
+
 def render_point(points_xyz_org, points_color, H, W, K, world2cam, image_size, radius, ppp, bg_feat=None,
                  acc="alphacomposite"):
     """refine_utils.py:306-333.  points [P,3] world, features [P,C] -> [1,C,H,W].  (`bg_feat` and `acc` are accepted
-    and unused, as in the reference.)"""
-    if points_xyz_org.requires_grad:
-        raise NotImplementedError("point positions carry no gradient on this path (the reference optimises features)")
+    and unused, as in the reference.)  Differentiable w.r.t. the features and, through `dists`, w.r.t. whatever the
+    projection is built from: the points, `world2cam`, `K`."""
     proj_xyz = torch.matmul(points_xyz_org, world2cam[:3, :3].T) + world2cam[:3, 3]
     proj_xyz = torch.matmul(proj_xyz, K.T)                       # perspective projection
-    proj_xyz[:, 0:2] = proj_xyz[:, 0:2] / proj_xyz[:, 2:]
-    proj_xyz[:, 0] = proj_xyz[:, 0] / W * 2 - 1.0
-    proj_xyz[:, 1] = proj_xyz[:, 1] / H * 2 - 1.0
-    proj_xyz[:, 0] = proj_xyz[:, 0] * -1
-    proj_xyz[:, 1] = proj_xyz[:, 1] * -1
+    # the reference writes the columns in place (:311-315); the division's inputs would not survive that under
+    # autograd, so the same fp32 operations in the same order run out of place
+    xy = proj_xyz[:, 0:2] / proj_xyz[:, 2:]
+    x = (xy[:, 0] / W * 2 - 1.0) * -1
+    y = (xy[:, 1] / H * 2 - 1.0) * -1
+    proj_xyz = torch.stack((x, y, proj_xyz[:, 2]), 1)
     idx, _, dists = rasterize_points(proj_xyz, image_size, radius, ppp)
     return _PointComposite.apply(points_color.float(), idx, dists, float(radius)).unsqueeze(0)
 
@@ -244,7 +283,7 @@ def refine_render(unet, points, feats, world2cam, focal, H, W, radius, ppp):
 
 def refine_train_step(unet, params, optimizer, guidance, text_z, points, world2cam, focal, H, W, radius, ppp,
                       colour_origin, guidance_scale=5.0, t=None, clip_model=None, ref_rgb=None, ref_text=None,
-                      is_front=False, gt_mask=None, cx_model=None):
+                      is_front=False, gt_mask=None, cx_model=None, points_origin=None, lambda_points=1e3):
     """One iteration of nerf/utils.py:839-894.  params = dict(colour [P,3], feat [P,16]) (nn.Parameters).
 
     Front view (`is_front`, utils.py:872-874): 1000 x L1 between the masked render and the masked reference image
@@ -253,7 +292,12 @@ def refine_train_step(unet, params, optimizer, guidance, text_z, points, world2c
     gradient: the reference decodes under no_grad); without a CLIP model that branch cannot run, so t is then
     drawn from the SDS part of the range instead of raising mid-training - then, when `clip_model` and `ref_rgb` are given,
     the trainer's own 10 x CLIP image-image term and, with `cx_model`, the contextual loss; both back-propagate into the
-    render.  Every view: background regulariser on the dilated coverage mask, colour regulariser, Adam."""
+    render.  Every view: background regulariser on the dilated coverage mask, colour regulariser, Adam.
+
+    `points` may be an nn.Parameter held by the optimiser: the image losses then reach the positions through the
+    renderer's position gradient (include/mi3d.h Part 7).  With `points_origin` [P,3] given the step adds
+    `lambda_points` x mse(points, points_origin), the sibling of the colour regulariser - this project's own choice,
+    the reference never moves its points.  The defaults leave the reference's step as it is."""
     feats = torch.cat((params["colour"], params["feat"]), -1).float()
     rgb, mask = refine_render(unet, points, feats, world2cam, focal, H, W, radius, ppp)
     if is_front:
@@ -275,6 +319,8 @@ def refine_train_step(unet, params, optimizer, guidance, text_z, points, world2c
     bg_loss = 1e-3 * (1 - rgb * (1 - mask)).sum()
     reg_loss = F.mse_loss(params["colour"], colour_origin) * 1e3
     loss = clip_loss + reg_loss + bg_loss
+    if points_origin is not None:
+        loss = loss + F.mse_loss(points, points_origin) * lambda_points
     # ... and the reference then zeroes the gradients before its own backward (nerf/utils.py:888-890): on the SDS
     # branch the guidance gradient never reaches the optimiser.  Kept as the reference has it - the work is the same.
     optimizer.zero_grad()
