@@ -32,9 +32,6 @@ using namespace mi3d;
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kTile = 64;   // samples per workgroup
-constexpr int kWaves = 4;   // waves per workgroup
 constexpr int kMaxFeat = MI3D_MAX_LEVELS * 2;
 constexpr int kMaxPts = MI3D_MAX_POINTS;
 
@@ -194,14 +191,6 @@ __global__ __launch_bounds__(kWave *kWaves) void k_grid_encode(PointSet ps, uint
 // per CU (+2-6 ms); evaluating the stencil three points at a time with the +-eps x-neighbours adjacent and all 24 loads
 // in flight (35.6 -> 36.0 ms: the coarse levels lose to the lower occupancy what the fine ones gain); keeping the corner values of the sample's own cell in registers for its +-eps neighbours (the
 // coarse levels, where it applies, are served by the L1 anyway and the extra compares made them 5-15 % slower).
-constexpr uint32_t kXcds = 8;
-constexpr int kMaxSegs = 16;
-
-struct EncodeSeg { uint32_t level, tile0, tile1, wgs; };  // wgs: workgroups of the XCD that walk this segment
-struct EncodePlan {
-    uint32_t n_seg[kXcds];
-    EncodeSeg seg[kXcds][kMaxSegs];
-};
 
 template <bool PAIR>
 __device__ __forceinline__ void gather_corners(const GridLevel &L, const float2 *__restrict__ lvl, uint32_t cx,
@@ -236,37 +225,6 @@ __device__ __forceinline__ void gather_corners(const GridLevel &L, const float2 
     }
 }
 
-// Fast index paths.  grid_entry() is the general rule (any dims, any table size, any input): ~30 instructions and four
-// uniform branches per corner pair, and with them the gather's coarse levels were INSTRUCTION-bound - ~300 issued
-// instructions per (point, level) = the 0.84-1.05 ms those levels cost whether their table sat in the L1 or in LDS.
-// Two level shapes cover every level the reference's configurations build, and a stencil point (PointSet mode 1) is
-// clamped into [0, 1], so its cell coordinates never exceed res - 1:
-//   kDense3    3-D strided index, cy * res and cz * res^2 in 24-bit multiplies.  The index wraps (grid_entry's
-//              `index >= size`) only for the +1 corners of the box's last cells: ONE compare on the largest of the
-//              four (y, z) bases decides for all eight corners, and a wave with such a lane takes the general path for
-//              that point.  Everywhere else entries e and e + 1 are neighbours in memory: one 8-byte-aligned 16-byte
-//              load per (y, z) pair, no select.
-//   kHashPow2  power-of-two table: (cx ^ cy p1 ^ cz p2) & mask, the +1 bases by adding the prime; the x+1 corner is
-//              the other half of the aligned 16-byte slot exactly when cx is even (x enters with prime 1): ONE
-//              predicate for the four pairs, the odd lanes fetch their four x+1 corners behind the slots.
-// Same entries, same weights, same order of the eight fused multiply-adds: the planes are bit-identical.
-enum LevelKind : int { kGeneral = 0, kDense3 = 1, kHashPow2 = 2 };
-struct LevelFast {
-    int kind;
-    uint32_t res2;     // res * res (kDense3)
-    uint32_t last;     // size - 1: the mask (kHashPow2), the entry whose x+1 neighbour wraps (kDense3)
-};
-__host__ __device__ __forceinline__ LevelFast level_fast(const GridLevel &L, int mode) {
-    LevelFast f = {kGeneral, L.res * L.res, L.size - 1u};
-    if (mode == 0) return f;  // raw positions may lie outside [0, 1]
-    if (L.hashed) {
-        if ((L.size & (L.size - 1u)) == 0u && L.size >= 2u) f.kind = kHashPow2;
-    } else if (L.dims == 3 && L.res >= 2u && (uint64_t)L.res * L.res * L.res < (1ull << 31) &&
-               (uint64_t)L.res * L.res * L.res <= (uint64_t)L.size) {
-        f.kind = kDense3;  // the largest corner index, res (1 + res + res^2), is below 2 size: it wraps at most once
-    }
-    return f;
-}
 struct __attribute__((packed, aligned(8))) EntryPair { float ax, ay, bx, by; };  // entries e, e + 1 of a level
 
 // (24-bit multiplies for the spatial hash and the gather table's slot hash: tried in round 6, slightly slower - DESIGN.md 3.2, A.11)
@@ -387,13 +345,82 @@ __device__ __forceinline__ void encode_points(const PointSet &ps, const float (&
 // next unclaimed tile of every plan segment; one slot per launch in flight (zeroed in-stream before the launch)
 constexpr uint32_t kPlanSlots = 64;
 __device__ uint32_t g_encode_next[kPlanSlots * kXcds * kMaxSegs];
-// host side of the ring (mi3d_grid_encode_points_planes_counted): who used a slot last, and the event behind that launch
-// (`broken`: the event behind the slot's last launch could not be recorded - nobody can tell any more when that launch is
-//  over, so the slot is never handed out again: launches that draw it deal their tiles statically)
-struct PlanSlot { bool used = false; bool broken = false; hipEvent_t done = nullptr; int device = -1; };
-PlanSlot g_slots[kPlanSlots];
-uint32_t g_slot_launches = 0;
-std::mutex g_slot_mutex;
+// Host side of the ring: one counter slot per launch of the XCD-planned kernel, a ring of 64, zeroed in-stream right before
+// the kernel; a hipEvent recorded behind the kernel says when the slot is free again: a slot is handed out only once that
+// event has completed (whatever the stream) - otherwise the launch leaves the slot alone and deals its tiles statically
+// (next == nullptr: the round-2 order, same planes, a few ms slower at C2 size) - never two live launches on one set of
+// counters.  (Round 4 asked the previous owner's STREAM with hipStreamQuery: a destroyed stream's handle is not a valid
+// argument, and a launch captured into a hipGraph recorded the idle capture stream as owner while the graph later replays
+// elsewhere - ADVICE round 4.)  A launch that is being CAPTURED always deals statically: a graph replays any number of
+// times on any stream, it must not own a slot.
+struct EncodeSlotRing {
+    // who used a slot last, and the event behind that launch
+    // (`broken`: the event behind the slot's last launch could not be recorded - nobody can tell any more when that launch is
+    //  over, so the slot is never handed out again: launches that draw it deal their tiles statically)
+    struct Slot { bool used = false; bool broken = false; hipEvent_t done = nullptr; int device = -1; };
+    Slot slots[kPlanSlots];
+    uint32_t launches = 0;
+    std::mutex mutex;
+
+    // Before the kernel.  next: the launch's counters, zeroed on `st` (nullptr: deal the tiles statically); slot: what
+    // release() wants behind the kernel (-1: nothing).  Returns a HIP error code; 0 also where no slot was free.
+    int acquire(hipStream_t st, bool claim_tiles, uint32_t *&next, int &slot_used) {
+        next = nullptr;
+        slot_used = -1;
+        hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &capturing) != hipSuccess) { (void)hipGetLastError(); capturing = hipStreamCaptureStatusNone; }
+        if (!claim_tiles || capturing != hipStreamCaptureStatusNone) return 0;
+        uint32_t *base = nullptr;
+        hipError_t e = hipGetSymbolAddress(reinterpret_cast<void **>(&base), HIP_SYMBOL(g_encode_next));
+        if (e != hipSuccess) return (int)e;
+        std::lock_guard<std::mutex> guard(mutex);
+        const uint32_t slot = launches++ % kPlanSlots;
+        Slot &ps_slot = slots[slot];
+        // free = never used, or the event recorded behind its last launch has completed.  (Round 5 also took a slot whose
+        // last user was "this stream" by comparing raw handles: a destroyed stream's address can come back as another
+        // stream's while the old launch is still running - ADVICE round 5.  The event is the only witness now; a slot that
+        // comes round on a stream with 64 gathers still in flight deals statically instead.)
+        bool free_now = !ps_slot.used;
+        if (!free_now && !ps_slot.broken && ps_slot.done != nullptr) {   // (hipEventQuery does not block; hipErrorNotReady is not a failure)
+            free_now = hipEventQuery(ps_slot.done) == hipSuccess;
+            if (!free_now) (void)hipGetLastError();
+        }
+        int dev_now = -1;
+        (void)hipGetDevice(&dev_now);
+        if (free_now && ps_slot.done != nullptr && ps_slot.device != dev_now) {
+            // (an event belongs to the device it was created on: the ring is shared by the process's devices)
+            free_now = hipEventQuery(ps_slot.done) == hipSuccess;
+            if (free_now) { (void)hipEventDestroy(ps_slot.done); ps_slot.done = nullptr; } else (void)hipGetLastError();
+        }
+        if (free_now && ps_slot.done == nullptr) {
+            if (hipEventCreateWithFlags(&ps_slot.done, hipEventDisableTiming) != hipSuccess) {
+                (void)hipGetLastError();
+                ps_slot.done = nullptr;
+                free_now = false;
+            }
+            ps_slot.device = dev_now;
+        }
+        if (free_now) {
+            ps_slot.used = true;
+            next = base + (size_t)slot * kXcds * kMaxSegs;
+            e = hipMemsetAsync(next, 0, sizeof(uint32_t) * kXcds * kMaxSegs, st);
+            if (e != hipSuccess) return (int)e;
+            slot_used = (int)slot;
+        }
+        return 0;
+    }
+    // behind the kernel: the slot's counters are free once this event has completed
+    void release(int slot_used, hipStream_t st) {
+        if (slot_used >= 0) {
+            std::lock_guard<std::mutex> guard(mutex);
+            if (hipEventRecord(slots[slot_used].done, st) != hipSuccess) {
+                (void)hipGetLastError();
+                slots[slot_used].broken = true;   // a stale event would report "complete" while the kernel still runs
+            }
+        }
+    }
+};
+EncodeSlotRing g_encode_ring;
 
 #ifdef MI3D_DEV
 // tools build only: when each XCD started, and when it finished each of its segments (100 MHz wall clock), so
@@ -500,68 +527,6 @@ __global__ __launch_bounds__(kWave *kLdsWaves) void k_grid_encode_planes_lds(Poi
             else encode_points<kGeneral, false, NT>(ps, base, L, F, lvl, planes, out_half, plane0, n, s);
         }
     }
-}
-
-// Relative cost of one tile of a level, as a function of x = (marching step) x (level scale) = how many cells of the
-// level two consecutive samples of a ray are apart: the measured per-level times above, tabulated against x (C2: step
-// 2 sqrt(3) / 1024 in a box of side 2) and interpolated, so other step sizes and grid configurations balance too.
-inline double encode_level_cost(double x, bool dense_fast) {
-    // ms per level at C2 with 6 workgroups per CU up to x = 0.26 and 3 beyond; a dense level on the short route is
-    // instruction-bound and flat.  Round 6's fit, IN SITU: what a tile of each level costs its XCD while the other seven walk
-    // theirs, from the per-XCD, per-segment timestamps of the whole gather (tools/encode_xcd_timeline.py,
-    // profiles/encode_xcd_timeline_r06*.json).  Round 3's table (per-level launches of the whole chip) was equal within the
-    // run-to-run spread: the balance of the XCDs is worth <= 0.9 ms and a static table cannot have it.
-    static const double xs[] = {0.0, 0.136, 0.19, 0.26, 0.36, 0.50, 0.69, 0.95, 1.30, 1.80, 2.50, 3.50};
-    if (dense_fast) return 0.383;
-    static const double cs[] = {0.67, 0.685, 0.80, 0.853, 0.982, 1.416, 1.819, 2.246, 2.656, 2.72, 2.895, 2.78};
-    constexpr int N = sizeof(xs) / sizeof(xs[0]);
-    if (x <= xs[0]) return cs[0];
-    for (int i = 1; i < N; ++i)
-        if (x < xs[i]) return cs[i - 1] + (cs[i] - cs[i - 1]) * (x - xs[i - 1]) / (xs[i] - xs[i - 1]);
-    return cs[N - 1];
-}
-// workgroups per CU a level is walked with: measured per level (same file) - 0.84 ms at 6 against 1.06 at 3 for the
-// coarse levels, 1.53 at 3 against 1.67 at 6 where a wave's lanes sit in different lines (x = cells per marching step)
-inline uint32_t encode_level_wgs_per_cu(double x, uint32_t coarse, uint32_t fine) { return x < 0.30 ? coarse : fine; }
-
-// The (level, tile) list cut into kXcds contiguous segments of equal modelled cost.
-inline EncodePlan make_encode_plan(const GridTable &T, uint32_t n_tiles, float step01, int only_level,
-                                   uint32_t wgs_coarse_per_xcd, uint32_t wgs_fine_per_xcd, uint32_t first_level = 0,
-                                   int point_mode = 1) {
-    EncodePlan plan{};
-    double cost[MI3D_MAX_LEVELS], total = 0.0;
-    for (uint32_t l = 0; l < T.n_levels; ++l) {
-        cost[l] = encode_level_cost((double)step01 * (double)T.level[l].scale,
-                                    level_fast(T.level[l], point_mode).kind == kDense3);
-        if (only_level >= 0) cost[l] = (int)l == only_level ? 1.0 : 0.0;
-        if (l < first_level) cost[l] = 0.0;  // served from LDS by k_grid_encode_planes_lds
-        total += cost[l];
-    }
-    const double share = total / kXcds;
-    uint32_t x = 0;
-    double filled = 0.0;  // cost already given to XCD x
-    for (uint32_t l = 0; l < T.n_levels; ++l) {
-        if (cost[l] <= 0.0) continue;
-        uint32_t t0 = 0;
-        while (t0 < n_tiles) {
-            // tiles of this level that still fit XCD x's share (the last XCD takes whatever is left)
-            const double room = share - filled;
-            uint32_t take = (x + 1 == kXcds) ? n_tiles - t0 : (uint32_t)ceil(room / cost[l] * (double)n_tiles - 1e-9);
-            if (take > n_tiles - t0) take = n_tiles - t0;
-            if (take > 0 && plan.n_seg[x] < (uint32_t)kMaxSegs) {
-                const uint32_t wgs = encode_level_wgs_per_cu((double)step01 * (double)T.level[l].scale,
-                                                             wgs_coarse_per_xcd, wgs_fine_per_xcd);
-                plan.seg[x][plan.n_seg[x]++] = EncodeSeg{l, t0, t0 + take, wgs};
-                filled += cost[l] * (double)take / (double)n_tiles;
-                t0 += take;
-            }
-            if (t0 < n_tiles || filled >= share - 1e-12) {
-                if (x + 1 < kXcds) { ++x; filled = 0.0; }
-                else if (take == 0) break;  // cannot happen: the last XCD takes everything
-            }
-        }
-    }
-    return plan;
 }
 
 // ---------------------------------------------------------------- backward
@@ -793,28 +758,6 @@ int launch_scatter(const PointSet &ps, uint32_t n, const int32_t *count, const f
     return (int)hipGetLastError();
 }
 
-// The record path sums a tile in the gather table only where it pays: on levels whose cells are at least this many
-// marching steps long (divided by default_merge_levels' own 1.05); the others emit per-point x-pair records.  4 steps =
-// levels 0-6 at C2.  The gathered role is bound by its instruction stream and its LDS atomics whatever the gradients
-// are, the record role by records, i.e. by how many gradient pairs are not zero.  Round 3 measured the threshold at 16-byte
-// records (3 steps: level 7 gathered) - a real field iteration preferred 4.2 (89.5 -> 86.4 ms) but the dense-gradient
-// scatter paid 58 -> 66 ms.  With 12-byte binary16 records and the shared-face pass (round 4) level 7 as records wins
-// on both: 13-point scatter + deferred point-0 pair, one box, tools/kbench.py --what scatter_ab: dense gradients 62.25 ->
-// 61.57 ms, a real step's zero census 40.87 -> 39.77 ms, whole steps -1.9 ms (tools/step_ab.py, anchored A/B); 5.8 steps
-// (level 6 as records too): real 39.1, dense 66.2 - not taken (profiles/kbench_r04_scatter_ab.json).
-#ifndef MI3D_MERGE_STEPS_X10_DEFAULT
-#define MI3D_MERGE_STEPS_X10_DEFAULT 42
-#endif
-inline float merge_steps() { return (float)MI3D_TUNE(MI3D_T_MERGE_STEPS_X10, MI3D_MERGE_STEPS_X10_DEFAULT) / 10.5f; }
-
-// levels whose cells are longer than one marching step `step01` (in [0,1] units) try to merge neighbours
-uint32_t default_merge_levels(const GridTable &T, float step01) {
-    uint32_t m = 0;
-    for (uint32_t l = 0; l < T.n_levels; ++l)
-        if (1.0f / (float)T.level[l].res >= 1.05f * step01) m = l + 1;
-    return m;
-}
-
 
 // ================================================================ binned scatter (no global atomics)
 //
@@ -861,35 +804,15 @@ uint32_t default_merge_levels(const GridTable &T, float step01) {
 // they really are in flight (MI3D_REDUCE_U).  Variants are judged between PRODUCT-grade builds loaded into one process
 // (tools/scatter_ab_libs.py): the tools build, with every variant behind a run-time switch, allocates registers for all
 // of them.
-constexpr uint32_t kBinShift = 13, kBinEntries = 1u << kBinShift;
-#ifndef MI3D_EMIT_FINE_WAVES_DEFAULT
-#define MI3D_EMIT_FINE_WAVES_DEFAULT 1536
-#endif
-constexpr uint32_t kEmitWavesMax = MI3D_EMIT_FINE_WAVES_DEFAULT;
-constexpr uint32_t kReduceWavesC = 16;  // waves of a reduce workgroup (= kReduceWaves below)
-
-struct __attribute__((packed, aligned(4))) BinRecord {
-    uint32_t entry;  // level-local entry index
-    float g0, g1;
-};
-// One record for the TWO x-neighbours of a (y, z) corner pair on a fine level.  The four values of such a pair have rank
-// one - (1 - fx) (a, b) for the corner at x, fx (a, b) for the one at x + 1, with (a, b) = w_y w_z (dfeature0, dfeature1)
-// - and the two entries differ in their low bits only (hashed: e1 = e0 ^ (2^t - 1), t = 1 + trailing ones of cx, because x
-// enters the hash with prime 1; dense: e1 = e0 + 1), so 16 bytes carry what two 12-byte records did: half the
-// lane-stores and LDS counter updates of the emit and two thirds of the bytes.
-// hdr = e0 | t << 19 (t = 0: dense "+1").  fx == 0 marks a single (only e0 receives (a, b)): pairs that straddle a bin.
-struct __attribute__((aligned(16))) RowRecord {
-    uint32_t hdr;
-    float a, b, fx;
-};
-constexpr uint32_t kRowEntryBits = 19;
-// ... and with BINARY16 gradient planes (torch.autocast: the pair (dfeature0, dfeature1) is two binary16 numbers) the same
+// (BinRecord, RowRecord, BinPlan and the planners - plan_for, plan_reduce_splits, slice_for - live in mi3d_grid_plan.h.)
+//
+// With BINARY16 gradient planes (torch.autocast: the pair (dfeature0, dfeature1) is two binary16 numbers) the same
 // pair record takes 12 bytes: the gradient pair travels as its 32 raw bits, the weight w = w_y w_z and the x fraction as
 // 23-bit fixed point (|error| <= 2^-24: the last bit of an fp32 weight near 1; the gradient beside it carries binary16's
 // 2^-11), and the entry as its 13 bits inside the bin - the region a record lies in IS its bin:
 //   word 0 = entry & 8191 | t << 13 | (w_q >> 16) << 18 | (fx_q >> 16) << 25      word 1 = raw binary16 pair
 //   word 2 = (w_q & 0xFFFF) | (fx_q & 0xFFFF) << 16            w_q = round(w 2^23), fx_q = round(fx 2^23), both < 2^23
-// The reduce forms (1 - fx) w (a, b) and fx w (a, b) from them.  fx_q == 0 marks a single, as fx == 0 does above.
+// The reduce forms (1 - fx) w (a, b) and fx w (a, b) from them.  fx_q == 0 marks a single, as fx == 0 does in a RowRecord.
 // A quarter less of the arena, of the emit's stores and of the reduce's loads - which is what bounds the reduce (it
 // reads its records at the HBM rate: 72 GB per dense 13-point pass with 16-byte records, profiles/pmc_r03.json).
 // (Row12, pack_row12 / unpack_row12 and the x-pair rule pair_flip_t live in mi3d_common.h: tests/test_host_math.py
@@ -899,146 +822,6 @@ __device__ __forceinline__ void unpack_row12(uint32_t w0, uint32_t w1, uint32_t 
     unpack_row12_fields(w0, w2, e_local, t, w, fx);
     dx = (float)__builtin_bit_cast(_Float16, (unsigned short)(w1 & 0xFFFFu));
     dy = (float)__builtin_bit_cast(_Float16, (unsigned short)(w1 >> 16));
-}
-
-struct BinPlan {
-    uint32_t level_bin0[MI3D_MAX_LEVELS];   // first bin of each level (bins are numbered level by level)
-    uint32_t level_cap[MI3D_MAX_LEVELS];    // records one (wave, bin) region of that level holds
-    uint32_t level_waves[MI3D_MAX_LEVELS];  // emitting waves of that level (coarse levels: many, fine levels: 2048)
-    uint64_t level_base[MI3D_MAX_LEVELS];   // BYTE offset of the level in the arena; inside: [wave][bin][cap] records
-    uint32_t level_cnt0[MI3D_MAX_LEVELS];   // first entry of the level in counts[]; inside: [wave][bin]
-    uint32_t level_max0[MI3D_MAX_LEVELS];   // first entry of the level in level_max[]; inside: [wave]
-    uint64_t total_bytes;
-    uint32_t row_mask;                      // fine levels stored as x-pair records (RowRecord, 16 bytes; Row12 with rec12)
-    uint32_t rec12;                         // binary16 gradient planes: the pair records are 12 bytes (Row12)
-    uint32_t level_split[MI3D_MAX_LEVELS];  // reduce workgroups that share one bin of the level
-    uint32_t level_wg0[MI3D_MAX_LEVELS];    // first reduce workgroup of the level; inside: [bin][split]
-    uint32_t n_reduce_wgs;
-    uint32_t total_counts, total_max;
-    uint32_t n_levels, n_bins;
-    uint32_t claim0;                        // level_max[claim0 ..+1] as uint32: the two roles' tile-claim counters (k_bin_emit)
-};
-
-#ifndef MI3D_EMIT_COARSE_WAVES_DEFAULT
-// Emitting waves of the coarse role = regions per coarse bin the reduce has to walk (a fixed cost per slice).  The chip holds
-// 3072 emitting waves at a time (256 CUs x 4 SIMDs x 3), 1536 of them the fine role's: 3072 coarse waves are two full rounds
-// of the other half.  Round 6, product-grade builds in one process on a placed arena (tools/scatter_ab_libs.py,
-// profiles/scatter_ab_libs_r06_coarse_waves_{56,30}GiB.json; dense / real census, ms): 16384 (rounds 3-5) 47.8 / 41.1,
-// 4096 48.7 / 43.3, 3072 47.1 / 40.6, 2048 53.9 / 48.3, 1536 47.0 / 40.6, 1024 55.5 / 49.3, 512 81.3 / 75.2 - whole rounds or
-// many; with four slices (30 GiB) 16384 54.4 / 44.6, 3072 51.9 / 41.8, 1536 51.7 / 41.9.
-#define MI3D_EMIT_COARSE_WAVES_DEFAULT 3072
-#endif
-#ifndef MI3D_HASHED_SLACK
-// a hashed level's region capacity over the uniform share of its records (plan_for)
-#define MI3D_HASHED_SLACK 1.25
-#endif
-__host__ __device__ inline uint32_t level_bins(const GridLevel &L) { return (L.size + kBinEntries - 1) / kBinEntries; }
-
-inline uint32_t round_waves(uint64_t w, uint32_t cap_waves) {
-    uint32_t nw = (uint32_t)(w < cap_waves ? w : cap_waves);
-    nw = (nw + kWaves - 1) / kWaves * kWaves;
-    return nw ? nw : kWaves;
-}
-
-// The plan for slices of n_slice samples.  Fine levels are emitted by at most 1536 waves (the lines being appended to
-// must fit the L2s); the coarse levels' run merging is latency-bound and emits few records, so it gets up to 3072 (see MI3D_EMIT_COARSE_WAVES_DEFAULT).
-// Region capacities - hashed levels: the uniform share of the UNMERGED record count plus 25 % (the hash spreads them
-// evenly).  Dense levels: bins are spatial, a wave's samples cluster in few of them, and merging thins the records by
-// an unknown factor: the share assumes a quarter of the geometric run length and two-fold imbalance.  A full region is
-// not an error - the overflow goes to the table by atomics.
-inline BinPlan plan_for(const GridTable &T, uint64_t n_slice, uint32_t P, float step01, uint32_t merge_levels,
-                        bool half_planes = false) {
-    const uint32_t fine_waves = (uint32_t)MI3D_TUNE(MI3D_T_EMIT_FINE_WAVES, kEmitWavesMax);
-    const uint32_t coarse_waves = (uint32_t)MI3D_TUNE(MI3D_T_EMIT_COARSE_WAVES, MI3D_EMIT_COARSE_WAVES_DEFAULT);
-    BinPlan p{};
-    p.n_levels = T.n_levels;
-    p.rec12 = half_planes ? 1u : 0u;
-    const uint64_t tiles = (n_slice + kWave - 1) / kWave;
-    for (uint32_t l = 0; l < T.n_levels; ++l) {
-        const GridLevel &L = T.level[l];
-        const uint32_t bins = level_bins(L);
-        const bool merged = l < merge_levels;
-        p.level_waves[l] = round_waves(tiles, merged ? coarse_waves : fine_waves);
-        const double pts_per_wave = (double)n_slice * P / p.level_waves[l];
-        double per = pts_per_wave * 8.0 / bins;
-        if (L.hashed) {
-            per *= MI3D_HASHED_SLACK;
-        } else {
-            double run = merged ? (1.0 / (double)L.res) / (1.5 * (double)step01) / 4.0 : 1.0;
-            run = run < 1.0 ? 1.0 : run;
-            per = per / run * 2.0;
-        }
-        // merged (coarse) levels emit one record per distinct entry a tile touched: measured 3-6 % of the per-contribution
-        // count (tools/scatter_fill.py, profiles/scatter_fill_r02.json) - their regions get a fifth of it (round 2 sized
-        // them for every contribution: 52 of the arena's 92 GiB at C2).  A full region is not an error (float atomics).
-        if (merged) per *= 0.2;
-        p.level_cap[l] = (uint32_t)per + 64u;
-        // fine fp32 levels whose x-neighbour entries are derivable from each other: one 16-byte record per corner pair
-        const bool row = !merged && L.size <= (1u << kRowEntryBits) &&
-                         (!L.hashed || (L.size & (L.size - 1u)) == 0u);
-        if (row) { p.row_mask |= 1u << l; p.level_cap[l] = p.level_cap[l] / 2u + 64u; }
-        p.level_bin0[l] = p.n_bins;
-        p.level_base[l] = p.total_bytes;
-        p.level_cnt0[l] = p.total_counts;
-        p.level_max0[l] = p.total_max;
-        p.n_bins += bins;
-        p.total_bytes += (uint64_t)p.level_waves[l] * bins * p.level_cap[l] *
-                         (row ? (p.rec12 ? sizeof(Row12) : sizeof(RowRecord)) : sizeof(BinRecord));
-        p.total_bytes = (p.total_bytes + 255u) / 256u * 256u;
-        p.total_counts += p.level_waves[l] * bins;
-        p.total_max += p.level_waves[l];
-    }
-    p.claim0 = p.total_max;
-    p.total_max += 4u;
-    return p;
-}
-// How many reduce workgroups share a bin.  A bin's records are spread over the level's emitting waves, so `split`
-// workgroups can each take every split-th group of 16 regions.  The bins are NOT equally heavy: a fine level puts ~4.4 M
-// x-pair records into each of its 64 bins at C2, but level 0 is ONE bin that receives 80 M run-merged records, level 1
-// two bins with 54 M each (tools/scatter_fill.py) - with the same split for every bin the reduce waited 12 ms for those
-// few workgroups.  So the split follows the expected work per bin (region capacity x waves x the usual fill - 0.78 for
-// per-point records, a few per cent for the gathered records of the coarse levels, whose regions are sized for the worst
-// case; an x-pair record costs two single ones), normalised so that the average bin gets `base_split` workgroups.
-inline void plan_reduce_splits(BinPlan &p, const GridTable &T, uint32_t base_split, uint32_t merge_levels) {
-    double work[MI3D_MAX_LEVELS], total = 0.0;
-    uint32_t bins_total = 0;
-    for (uint32_t l = 0; l < T.n_levels; ++l) {
-        const bool row = (p.row_mask >> l) & 1u;
-        work[l] = (double)p.level_waves[l] * p.level_cap[l] * (row ? 0.78 * 2.0 : (l < merge_levels ? 0.05 : 0.78));
-        total += work[l] * level_bins(T.level[l]);
-        bins_total += level_bins(T.level[l]);
-    }
-    const double target = total / bins_total / base_split;  // work one reduce workgroup should get
-    p.n_reduce_wgs = 0;
-    for (uint32_t l = 0; l < T.n_levels; ++l) {
-        uint32_t split = (uint32_t)(work[l] / target + 0.5);
-        const uint32_t most = p.level_waves[l] / kReduceWavesC ? p.level_waves[l] / kReduceWavesC : 1u;  // >= 1 region per wave
-        split = split < 1u ? 1u : (split > most ? most : split);
-        p.level_split[l] = split;
-        p.level_wg0[l] = p.n_reduce_wgs;
-        p.n_reduce_wgs += level_bins(T.level[l]) * split;
-    }
-}
-
-inline size_t bin_workspace_bytes(const BinPlan &p) {
-    return (size_t)p.total_bytes + (size_t)p.total_counts * sizeof(uint32_t) +
-           (size_t)p.total_max * sizeof(float);
-}
-
-// The slice length of a call over n samples: ceil(n / k) for the smallest k whose plan fits the workspace (k = 1, 2, 3 ...
-// up to 64, doubling from there).  Round 2-5 halved the slice (k = 1, 2, 4 ...): at C2 an arena between 31 and 46 GiB then
-// ran the four-slice plan of 24.7 GB although three slices (33 GB) fit - and every slice has a fixed cost (the emit's and
-// the reduce's tails, the regions the reduce walks).  `plan` receives the slice's plan (which may still not fit: the caller
-// checks and takes the atomic path).
-inline uint64_t slice_for(const GridTable &T, uint64_t n, uint32_t P, float step01, uint32_t merge_levels, bool half_planes,
-                          size_t workspace_bytes, BinPlan &plan) {
-    uint64_t n_slice = n;
-    plan = plan_for(T, n_slice, P, step01, merge_levels, half_planes);
-    for (uint64_t k = 2; n_slice > kWave && bin_workspace_bytes(plan) > workspace_bytes; k = k < 64 ? k + 1 : 2 * k) {
-        n_slice = (n + k - 1) / k;
-        plan = plan_for(T, n_slice, P, step01, merge_levels, half_planes);
-    }
-    return n_slice;
 }
 
 __device__ __forceinline__ void emit_record(const BinPlan &plan, const GridLevel &L, uint32_t l, uint32_t gw, uint32_t e,
@@ -1078,7 +861,7 @@ __device__ __forceinline__ unsigned long long fixed_point(float x) {
 // than contributions on level 0, 1.6x on level 7 - 1.66 G records per slice at C2, more than the fine levels', and a
 // handful of bins to reduce them in.  This merges across lanes, runs AND stencil points.)  A contribution that finds no
 // slot within kMergeProbes goes out as a record of its own.
-constexpr uint32_t kMergeSlots = 512, kMergeProbes = 16, kMergeEmpty = 0xFFFFFFFFu;
+constexpr uint32_t kMergeProbes = 16, kMergeEmpty = 0xFFFFFFFFu;   // (kMergeSlots = 512: mi3d_grid_plan.h)
 // Fine levels: the x-pair records of kChunkPts stencil points of a tile (64 lanes x 4 pairs each) are SORTED BY BIN in the
 // wave's LDS before they leave, so that what goes to a region is a contiguous run of records (consecutive lanes store
 // consecutive 16-byte slots) instead of one scattered 16-byte store per lane.  The staging area is the memory the coarse
@@ -1086,9 +869,6 @@ constexpr uint32_t kMergeSlots = 512, kMergeProbes = 16, kMergeEmpty = 0xFFFFFFF
 constexpr uint32_t kChunkPts = 2, kStageRecs = kWave * 4 * kChunkPts;
 static_assert(kStageRecs * 16 == 2 * kMergeSlots * 8, "the staging area is the gather table's sums");
 static_assert(3 * 64 <= kMergeSlots, "histogram, cursors and region deltas live in the gather table's keys");
-__host__ __device__ inline uint32_t emit_wave_words(uint32_t n_bins) {  // 32-bit words of LDS per emitting wave (even)
-    return 4u * kMergeSlots + kMergeSlots + ((n_bins + 1u) & ~1u);
-}
 
 template <bool HP>
 __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint32_t s_begin, uint32_t s_end,
@@ -1837,13 +1617,6 @@ __global__ __launch_bounds__(kWave *kReduceWaves) void k_bin_reduce(const char *
 // its loads (16 waves per CU hid that already): a small gain, and the short batch wins.
 #define MI3D_REDUCE_U 4
 #endif
-#ifndef MI3D_REDUCE_BASE_SPLIT
-// reduce workgroups per average bin for slices of 30 M evaluations and more (plan_reduce_splits).  Round 6, product-grade builds
-// in one process (profiles/scatter_ab_libs_r06_reduce_split.json; dense / synthetic census / captured real step, ms): 3: 44.78 /
-// 38.24 / 32.21, 4: 44.85 / 38.25 / 32.28, 6: 44.93 / 38.39 / 32.27, 8: 44.96 / 38.47 / 32.45 - flat: the reduce's tail is not where
-// its time goes
-#define MI3D_REDUCE_BASE_SPLIT 4
-#endif
     constexpr uint32_t U = MI3D_REDUCE_U;  // records per lane and batch
     // A region's records in batches of U per lane.  (The next batch's loads issued before this batch's LDS atomics, two
     // register sets: tried in round 6, nothing - the reduce is bound by the atomics themselves)
@@ -1937,6 +1710,14 @@ __global__ void k_replica_reduce(const float *__restrict__ rep, uint32_t n_rep, 
 
 constexpr uint32_t kReplicasDefault = 64;  // private table copies of the atomic fallback (same-line serialisation)
 
+// the level table of an entry point's grid arguments; false: n_levels is out of range
+bool grid_table_for(GridTable &T, uint32_t n_levels, uint32_t base_resolution, float per_level_scale,
+                    uint32_t log2_hashmap_size) {
+    if (!valid_levels(n_levels)) return false;
+    build_grid_table(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size);
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1945,7 +1726,7 @@ uint32_t mi3d_hashgrid_levels(uint32_t n_levels, uint32_t base_resolution, float
                               uint32_t log2_hashmap_size, uint32_t *offsets_host, uint32_t *resolutions_host,
                               float *scales_host) {
     GridTable T;
-    if (n_levels > MI3D_MAX_LEVELS) return 0;
+    if (n_levels != 0 && !valid_levels(n_levels)) return 0;   // (no levels: an empty table, offsets_host[0] = 0)
     const uint32_t total = build_grid_table(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size);
     for (uint32_t i = 0; i < n_levels; ++i) {
         if (offsets_host) offsets_host[i] = T.level[i].offset;
@@ -1959,10 +1740,9 @@ uint32_t mi3d_hashgrid_levels(uint32_t n_levels, uint32_t base_resolution, float
 int mi3d_hashgrid_forward(const float *x, uint32_t n, const float *params, uint32_t n_levels,
                           uint32_t base_resolution, float per_level_scale, uint32_t log2_hashmap_size, float *out,
                           void *stream) {
-    if (n_levels == 0 || n_levels > MI3D_MAX_LEVELS) return (int)hipErrorInvalidValue;
-    if (n == 0) return 0;
     GridTable T;
-    build_grid_table(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size);
+    if (!grid_table_for(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size)) return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
     const PointSet ps = make_points(x, nullptr, nullptr, 1, 1, 1.0f, 0);
     hipLaunchKernelGGL(k_grid_encode, dim3((n + kTile - 1) / kTile), dim3(kWave * kWaves), 0, as_stream(stream), ps, n,
                        (const int32_t *)nullptr, reinterpret_cast<const float2 *>(params), T, out);
@@ -1971,10 +1751,9 @@ int mi3d_hashgrid_forward(const float *x, uint32_t n, const float *params, uint3
 
 int mi3d_hashgrid_backward(const float *x, uint32_t n, const float *dout, uint32_t n_levels, uint32_t base_resolution,
                            float per_level_scale, uint32_t log2_hashmap_size, float *grad_params, void *stream) {
-    if (n_levels == 0 || n_levels > MI3D_MAX_LEVELS) return (int)hipErrorInvalidValue;
-    if (n == 0) return 0;
     GridTable T;
-    build_grid_table(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size);
+    if (!grid_table_for(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size)) return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
     const PointSet ps = make_points(x, nullptr, nullptr, 1, 1, 1.0f, 0);
     // no knowledge of the sampling step here: merge wherever a 1/512 step would linger in a cell
     return launch_scatter(ps, n, nullptr, dout, T, T.n_levels, grad_params,
@@ -1985,12 +1764,10 @@ int mi3d_grid_encode_points(const float *x, const float *x2, uint32_t n, const i
                             const float *offsets_host, uint32_t P0, uint32_t P, float bound, const float *params,
                             uint32_t n_levels, uint32_t base_resolution, float per_level_scale,
                             uint32_t log2_hashmap_size, float *out, void *stream) {
-    if (n_levels == 0 || n_levels > MI3D_MAX_LEVELS || P == 0 || P > MI3D_MAX_POINTS || P0 > P ||
-        (P0 < P && x2 == nullptr))
+    GridTable T;
+    if (!grid_table_for(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size) || !valid_stencil(P0, P, x2))
         return (int)hipErrorInvalidValue;
     if (n == 0) return 0;
-    GridTable T;
-    build_grid_table(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size);
     const PointSet ps = make_points(x, x2, offsets_host, P0, P, bound, 1);
     hipLaunchKernelGGL(k_grid_encode, dim3((n + kTile - 1) / kTile), dim3(kWave * kWaves), 0, as_stream(stream), ps, n,
                        count, reinterpret_cast<const float2 *>(params), T, out);
@@ -2011,117 +1788,44 @@ int mi3d_grid_encode_points_planes_counted(const float *x, const float *x2, uint
                                            const float *params, uint32_t n_levels, uint32_t base_resolution,
                                            float per_level_scale, uint32_t log2_hashmap_size, float step, void *out_planes,
                                            int out_half, void *stream) {
-    if (n_levels == 0 || n_levels > MI3D_MAX_LEVELS || P == 0 || P > MI3D_MAX_POINTS || P0 > P ||
-        (P0 < P && x2 == nullptr))
+    GridTable T;
+    if (!grid_table_for(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size) || !valid_stencil(P0, P, x2))
         return (int)hipErrorInvalidValue;
     if (n == 0) return 0;
-    GridTable T;
-    build_grid_table(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size);
     const PointSet ps = make_points(x, x2, offsets_host, P0, P, bound, 1);
-    const uint32_t tiles = (n + kTile - 1) / kTile;
-    const float step01 = step > 0.f ? step / (2.0f * bound) : 1.0f / 512.0f;
     const int variant = MI3D_TUNE(MI3D_T_ENCODE_VARIANT, 3);
-    uint32_t need = (tiles + kWaves - 1) / kWaves;  // workgroups one XCD needs to give every tile its own wave
-    const uint32_t fine_cu = (uint32_t)MI3D_TUNE(MI3D_T_ENCODE_WGS_PER_CU, 3);
-    const uint32_t coarse_cu = (uint32_t)MI3D_TUNE(MI3D_T_ENCODE_COARSE_WGS_PER_CU, 6);
-    const uint32_t wgs_fine = need < 32 * fine_cu ? need : 32 * fine_cu;        // 32 CUs per XCD; persistent beyond
-    uint32_t wgs_coarse = need < 32 * coarse_cu ? need : 32 * coarse_cu;
-    if (wgs_coarse < wgs_fine) wgs_coarse = wgs_fine;
     const float2 *tab = reinterpret_cast<const float2 *>(params);
     float *out = reinterpret_cast<float *>(out_planes);
     hipStream_t st = as_stream(stream);
     // the longest prefix of levels whose tables fit the LDS of a CU together goes through the LDS kernel
     const int only_level = MI3D_TUNE(MI3D_T_ENCODE_ONLY_LEVEL, -1);
-    uint32_t n_lds = 0;
     size_t lds_bytes = 0;
-    while (n_lds < T.n_levels && (size_t)(T.level[n_lds].offset + T.level[n_lds].size) * sizeof(float2) <= (size_t)150 * 1024) {
-        lds_bytes = (size_t)(T.level[n_lds].offset + T.level[n_lds].size) * sizeof(float2);
-        ++n_lds;
-    }
+    uint32_t n_lds = lds_levels(T, &lds_bytes);
+    // (the launch alone, not the query: the tools build may force the count or time one level through the XCD kernel)
     if (MI3D_TUNE(MI3D_T_ENCODE_LDS_LEVELS, -1) >= 0) {  // dev: force the count (0 = off)
         n_lds = (uint32_t)MI3D_TUNE(MI3D_T_ENCODE_LDS_LEVELS, -1) < n_lds ? (uint32_t)MI3D_TUNE(MI3D_T_ENCODE_LDS_LEVELS, -1) : n_lds;
         lds_bytes = n_lds ? (size_t)(T.level[n_lds - 1].offset + T.level[n_lds - 1].size) * sizeof(float2) : 0;
     }
     if (only_level >= 0) n_lds = 0;
-    if (n_lds > 0) {
+    const EncodeLaunchPlan enc = plan_encode(T, n, step01_of(step, bound), n_lds, lds_bytes, only_level, false);
+    if (enc.n_lds > 0) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_grid_encode_planes_lds<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        const uint32_t wgs = (tiles + kLdsWaves - 1) / kLdsWaves;
-        hipLaunchKernelGGL((k_grid_encode_planes_lds<true>), dim3(wgs < 256u ? wgs : 256u), dim3(kWave * kLdsWaves), lds_bytes,
-                           st, ps, n, tab, T, n_lds, out, out_half, count);
-        if (n_lds == T.n_levels) return (int)hipGetLastError();
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)enc.lds_bytes);
+        const uint32_t wgs = ((n + kTile - 1) / kTile + kLdsWaves - 1) / kLdsWaves;
+        hipLaunchKernelGGL((k_grid_encode_planes_lds<true>), dim3(wgs < 256u ? wgs : 256u), dim3(kWave * kLdsWaves), enc.lds_bytes,
+                           st, ps, n, tab, T, enc.n_lds, out, out_half, count);
+        if (enc.n_lds == T.n_levels) return (int)hipGetLastError();
     }
-    // The XCD-planned kernel.  One counter slot per launch, a ring of 64, zeroed in-stream right before the kernel; a hipEvent
-    // recorded behind the kernel says when the slot is free again: a slot is handed out only once that event has completed
-    // (whatever the stream) - otherwise the launch leaves the slot alone and deals its tiles statically (next == nullptr: the round-2 order, same planes, a few ms slower at C2 size) - never two live
-    // launches on one set of counters.  (Round 4 asked the previous owner's STREAM with hipStreamQuery: a destroyed
-    // stream's handle is not a valid argument, and a launch captured into a hipGraph recorded the idle capture stream as
-    // owner while the graph later replays elsewhere - ADVICE round 4.)  A launch that is being CAPTURED always deals
-    // statically: a graph replays any number of times on any stream, it must not own a slot.
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &capturing) != hipSuccess) { (void)hipGetLastError(); capturing = hipStreamCaptureStatusNone; }
-    const bool claim_tiles = MI3D_TUNE(MI3D_T_ENCODE_STATIC_TILES, 0) == 0 && capturing == hipStreamCaptureStatusNone;
-    auto acquire_slot = [&](uint32_t *&next, int &slot_used) -> int {
-        next = nullptr;
-        slot_used = -1;
-        if (!claim_tiles) return 0;
-        uint32_t *base = nullptr;
-        hipError_t e = hipGetSymbolAddress(reinterpret_cast<void **>(&base), HIP_SYMBOL(g_encode_next));
-        if (e != hipSuccess) return (int)e;
-        std::lock_guard<std::mutex> guard(g_slot_mutex);
-        const uint32_t slot = g_slot_launches++ % kPlanSlots;
-        PlanSlot &ps_slot = g_slots[slot];
-        // free = never used, or the event recorded behind its last launch has completed.  (Round 5 also took a slot whose
-        // last user was "this stream" by comparing raw handles: a destroyed stream's address can come back as another
-        // stream's while the old launch is still running - ADVICE round 5.  The event is the only witness now; a slot that
-        // comes round on a stream with 64 gathers still in flight deals statically instead.)
-        bool free_now = !ps_slot.used;
-        if (!free_now && !ps_slot.broken && ps_slot.done != nullptr) {   // (hipEventQuery does not block; hipErrorNotReady is not a failure)
-            free_now = hipEventQuery(ps_slot.done) == hipSuccess;
-            if (!free_now) (void)hipGetLastError();
-        }
-        int dev_now = -1;
-        (void)hipGetDevice(&dev_now);
-        if (free_now && ps_slot.done != nullptr && ps_slot.device != dev_now) {
-            // (an event belongs to the device it was created on: the ring is shared by the process's devices)
-            free_now = hipEventQuery(ps_slot.done) == hipSuccess;
-            if (free_now) { (void)hipEventDestroy(ps_slot.done); ps_slot.done = nullptr; } else (void)hipGetLastError();
-        }
-        if (free_now && ps_slot.done == nullptr) {
-            if (hipEventCreateWithFlags(&ps_slot.done, hipEventDisableTiming) != hipSuccess) {
-                (void)hipGetLastError();
-                ps_slot.done = nullptr;
-                free_now = false;
-            }
-            ps_slot.device = dev_now;
-        }
-        if (free_now) {
-            ps_slot.used = true;
-            next = base + (size_t)slot * kXcds * kMaxSegs;
-            e = hipMemsetAsync(next, 0, sizeof(uint32_t) * kXcds * kMaxSegs, st);
-            if (e != hipSuccess) return (int)e;
-            slot_used = (int)slot;
-        }
-        return 0;
-    };
-    auto slot_done = [&](int slot_used) {   // behind the kernel: the slot's counters are free once this event has completed
-        if (slot_used >= 0) {
-            std::lock_guard<std::mutex> guard(g_slot_mutex);
-            if (hipEventRecord(g_slots[slot_used].done, st) != hipSuccess) {
-                (void)hipGetLastError();
-                g_slots[slot_used].broken = true;   // a stale event would report "complete" while the kernel still runs
-            }
-        }
-    };
+    // The XCD-planned kernel, its tiles claimed from a counter slot of the ring where one is free (EncodeSlotRing).
     const dim3 block(kWave * kWaves);
-    const EncodePlan plan = make_encode_plan(T, tiles, step01, only_level, wgs_coarse, wgs_fine, n_lds);
+    const EncodePlan &plan = enc.plan;
     uint32_t segs = 0;
     for (uint32_t x = 0; x < kXcds; ++x) segs += plan.n_seg[x];
     if (segs == 0) return 0;   // (no level left for this kernel)
-    const dim3 grid(wgs_coarse * kXcds);
+    const dim3 grid(enc.wgs_coarse * kXcds);
     uint32_t *next = nullptr;
     int slot_used = -1;
-    int rc = acquire_slot(next, slot_used);
+    int rc = g_encode_ring.acquire(st, MI3D_TUNE(MI3D_T_ENCODE_STATIC_TILES, 0) == 0, next, slot_used);
     if (rc != 0) return rc;
     if ((variant & 3) == 3)
         hipLaunchKernelGGL((k_grid_encode_planes<true, true>), grid, block, 0, st, ps, n, tab, T, plan, out, out_half, count, next);
@@ -2130,7 +1834,7 @@ int mi3d_grid_encode_points_planes_counted(const float *x, const float *x2, uint
     else
         hipLaunchKernelGGL((k_grid_encode_planes<false, false>), grid, block, 0, st, ps, n, tab, T, plan, out, out_half, count, next);
     rc = (int)hipGetLastError();
-    slot_done(slot_used);
+    g_encode_ring.release(slot_used, st);
     return rc;
 }
 
@@ -2139,24 +1843,20 @@ int mi3d_grid_scatter_points(const float *x, const float *x2, uint32_t n, const 
                              const float *offsets_host, uint32_t P0, uint32_t P, float bound, const float *dout,
                              uint32_t n_levels, uint32_t base_resolution, float per_level_scale,
                              uint32_t log2_hashmap_size, float step, float *grad_params, void *stream) {
-    if (n_levels == 0 || n_levels > MI3D_MAX_LEVELS || P == 0 || P > MI3D_MAX_POINTS || P0 > P ||
-        (P0 < P && x2 == nullptr))
+    GridTable T;
+    if (!grid_table_for(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size) || !valid_stencil(P0, P, x2))
         return (int)hipErrorInvalidValue;
     if (n == 0) return 0;
-    GridTable T;
-    build_grid_table(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size);
     const PointSet ps = make_points(x, x2, offsets_host, P0, P, bound, 1);
-    const float step01 = step > 0.f ? step / (2.0f * bound) : 1.0f / 512.0f;
-    return launch_scatter(ps, n, count, dout, T, default_merge_levels(T, step01), grad_params, as_stream(stream));
+    return launch_scatter(ps, n, count, dout, T, default_merge_levels(T, step01_of(step, bound)), grad_params, as_stream(stream));
 }
 
 size_t mi3d_grid_scatter_binned_workspace(uint32_t n, uint32_t P, float bound, float step, uint32_t n_levels,
                                           uint32_t base_resolution, float per_level_scale, uint32_t log2_hashmap_size) {
-    if (n_levels == 0 || n_levels > MI3D_MAX_LEVELS || n == 0) return 0;
     GridTable T;
-    build_grid_table(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size);
-    const float step01 = step > 0.f ? step / (2.0f * bound) : 1.0f / 512.0f;
-    return bin_workspace_bytes(plan_for(T, n, P, step01, default_merge_levels(T, step01 * merge_steps())));
+    if (!grid_table_for(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size) || n == 0) return 0;
+    // (P points and fp32 planes, where the launch plans with its record points and its plane type; any workspace: ONE slice)
+    return bin_workspace_bytes(plan_scatter(T, n, P, bound, step, false, ~(size_t)0).plan);
 }
 
 int mi3d_grid_scatter_binned(const float *x, const float *x2, uint32_t n, const float *offsets_host, uint32_t P0,
@@ -2173,27 +1873,24 @@ int mi3d_grid_scatter_binned_plus(const float *x, const float *x2, uint32_t n, c
                                   int dout_half, uint32_t n_levels, uint32_t base_resolution, float per_level_scale,
                                   uint32_t log2_hashmap_size, float step, void *workspace, size_t workspace_bytes,
                                   float *grad_params, void *stream) {
-    if (n_levels == 0 || n_levels > MI3D_MAX_LEVELS || P == 0 || P > MI3D_MAX_POINTS || P0 > P ||
-        (P0 < P && x2 == nullptr))
+    GridTable T;
+    if (!grid_table_for(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size) || !valid_stencil(P0, P, x2))
         return (int)hipErrorInvalidValue;
     if (n == 0) return 0;
     hipStream_t st = as_stream(stream);
     const float *dout_planes = reinterpret_cast<const float *>(dout_planes_v);
     const float *extra0 = reinterpret_cast<const float *>(extra_point0_planes);
-    GridTable T;
-    build_grid_table(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size);
     const PointSet ps = make_points(x, x2, offsets_host, P0, P, bound, 1);
-    const float step01 = step > 0.f ? step / (2.0f * bound) : 1.0f / 512.0f;
-    // the record path run-merges only where it pays (cells at least 3 marching steps long); levels with shorter runs
-    // emit per-point records (16-byte x-pair records where the level's entries allow it)
-    const uint32_t merge_atomic = default_merge_levels(T, step01);
-    const uint32_t merge_levels = default_merge_levels(T, step01 * merge_steps());
     const uint32_t plane_rows = n * P;
 
+    // the record path run-merges only where it pays (cells at least 3 marching steps long); levels with shorter runs
+    // emit per-point records (16-byte x-pair records where the level's entries allow it).
     // the slice: the samples are cut into the FEWEST equal slices whose record arena fits the workspace
     const uint32_t P_rec = P + ((extra0 != nullptr && dout_half) ? 1u : 0u);   // (binary16: the extra pair is a record of its own)
-    BinPlan plan;
-    const uint64_t n_slice = slice_for(T, n, P_rec, step01, merge_levels, dout_half != 0, workspace_bytes, plan);
+    ScatterPlan sp = plan_scatter(T, n, P_rec, bound, step, dout_half != 0, workspace_bytes);
+    BinPlan &plan = sp.plan;
+    const uint32_t merge_atomic = sp.merge_atomic, merge_levels = sp.merge_levels;
+    const uint64_t n_slice = sp.n_slice;
     if (workspace == nullptr || bin_workspace_bytes(plan) > workspace_bytes) {
         // no usable workspace: the atomic kernels, with private copies of the table against same-line serialisation
         // when the caller's scratch at least holds those
@@ -2253,8 +1950,7 @@ int mi3d_grid_scatter_binned_plus(const float *x, const float *x2, uint32_t n, c
                                    plan, merge_levels, fine_mask, fine_waves, coarse_mask, coarse_waves,
                                    reinterpret_cast<BinRecord *>(arena), counts, level_max, grad_params);
         }
-        const uint32_t n_split = (uint64_t)(s1 - s0) * P >= 30000000ull ? (uint32_t)MI3D_REDUCE_BASE_SPLIT : ((uint64_t)(s1 - s0) * P >= 8000000ull ? 2u : 1u);
-        plan_reduce_splits(plan, T, n_split, merge_levels);
+        plan_reduce_splits(plan, T, reduce_base_split((uint64_t)(s1 - s0) * P), merge_levels);
         hipLaunchKernelGGL(k_bin_reduce, dim3(plan.n_reduce_wgs), dim3(kWave * kReduceWaves), lds_reduce, st, arena,
                            counts, level_max, T, plan, grad_params);
     }
@@ -2262,27 +1958,28 @@ int mi3d_grid_scatter_binned_plus(const float *x, const float *x2, uint32_t n, c
 }
 
 
-// Host-side planning queries (no device work; they run without a GPU): what the two calls above will do.
+// Host-side planning queries (no device work; they run without a GPU): what the two calls above will do, from the planners
+// the calls themselves use (mi3d_grid_plan.h).
 int mi3d_grid_level_routes(uint32_t n_levels, uint32_t base_resolution, float per_level_scale, uint32_t log2_hashmap_size,
                            int stencil_points, int32_t *kinds) {
-    if (n_levels == 0 || n_levels > MI3D_MAX_LEVELS || kinds == nullptr) return (int)hipErrorInvalidValue;
     GridTable T;
-    build_grid_table(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size);
+    if (!grid_table_for(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size) || kinds == nullptr)
+        return (int)hipErrorInvalidValue;
     for (uint32_t l = 0; l < T.n_levels; ++l) kinds[l] = level_fast(T.level[l], stencil_points ? 1 : 0).kind;
     return 0;
 }
 
 int mi3d_grid_encode_plan(uint32_t n, float bound, float step, uint32_t n_levels, uint32_t base_resolution,
                           float per_level_scale, uint32_t log2_hashmap_size, uint32_t *n_segments, uint32_t *segments) {
-    if (n_levels == 0 || n_levels > MI3D_MAX_LEVELS || n_segments == nullptr || segments == nullptr)
-        return (int)hipErrorInvalidValue;
     GridTable T;
-    build_grid_table(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size);
-    const float step01 = step > 0.f ? step / (2.0f * bound) : 1.0f / 512.0f;
-    uint32_t n_lds = 0;  // as mi3d_grid_encode_points_planes: the levels served from LDS are not in the plan
-    while (n_lds < T.n_levels && (size_t)(T.level[n_lds].offset + T.level[n_lds].size) * sizeof(float2) <= (size_t)150 * 1024) ++n_lds;
+    if (!grid_table_for(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size) || n_segments == nullptr ||
+        segments == nullptr)
+        return (int)hipErrorInvalidValue;
+    uint32_t n_lds = lds_levels(T, nullptr);  // the levels served from LDS are not in the plan
+    // (the query alone: where every level fits LDS the launch ends behind its LDS kernel; the query reports them in the XCD plan)
     if (n_lds == T.n_levels) n_lds = 0;
-    const EncodePlan plan = make_encode_plan(T, (n + kTile - 1) / kTile, step01, -1, 32 * 6, 32 * 3, n_lds);
+    // (the full machine's workgroup counts whatever n is: the segments do not depend on them, and wgs is not exported)
+    const EncodePlan plan = plan_encode(T, n, step01_of(step, bound), n_lds, 0, -1, true).plan;
     for (uint32_t x = 0; x < kXcds; ++x) {
         n_segments[x] = plan.n_seg[x];
         for (uint32_t i = 0; i < (uint32_t)kMaxSegs; ++i) {
@@ -2298,17 +1995,15 @@ int mi3d_grid_encode_plan(uint32_t n, float bound, float step, uint32_t n_levels
 int mi3d_grid_scatter_plan(uint32_t n, uint32_t P, float bound, float step, uint32_t n_levels, uint32_t base_resolution,
                            float per_level_scale, uint32_t log2_hashmap_size, size_t workspace_bytes,
                            unsigned long long *out) {
-    if (n_levels == 0 || n_levels > MI3D_MAX_LEVELS || P == 0 || P > MI3D_MAX_POINTS || n == 0 || out == nullptr)
-        return (int)hipErrorInvalidValue;
     GridTable T;
-    build_grid_table(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size);
-    const float step01 = step > 0.f ? step / (2.0f * bound) : 1.0f / 512.0f;
-    const uint32_t merge_levels = default_merge_levels(T, step01 * merge_steps());
-    BinPlan p;
-    const uint64_t n_slice = slice_for(T, n, P, step01, merge_levels, false, workspace_bytes, p);  // as mi3d_grid_scatter_binned
-    const uint64_t evals = n_slice * P;
-    plan_reduce_splits(p, T, evals >= 30000000ull ? (uint32_t)MI3D_REDUCE_BASE_SPLIT : (evals >= 8000000ull ? 2u : 1u), merge_levels);
-    out[0] = n_slice; out[1] = bin_workspace_bytes(p); out[2] = merge_levels; out[3] = p.n_reduce_wgs;
+    if (!grid_table_for(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size) || !valid_stencil(P, P, nullptr) ||
+        n == 0 || out == nullptr)
+        return (int)hipErrorInvalidValue;
+    // (P points and fp32 planes, where the launch plans with its record points and its plane type)
+    ScatterPlan sp = plan_scatter(T, n, P, bound, step, false, workspace_bytes);
+    BinPlan &p = sp.plan;
+    plan_reduce_splits(p, T, reduce_base_split(sp.n_slice * P), sp.merge_levels);
+    out[0] = sp.n_slice; out[1] = bin_workspace_bytes(p); out[2] = sp.merge_levels; out[3] = p.n_reduce_wgs;
     out[4] = p.total_bytes; out[5] = p.total_counts;
     for (uint32_t l = 0; l < n_levels; ++l) {
         unsigned long long *o = out + 6 + 7 * l;
@@ -2317,7 +2012,6 @@ int mi3d_grid_scatter_plan(uint32_t n, uint32_t P, float bound, float step, uint
     }
     return 0;
 }
-
 
 }  // extern "C"
 

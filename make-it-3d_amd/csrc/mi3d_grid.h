@@ -1,46 +1,15 @@
 // Multiresolution hash-grid building blocks shared by hashgrid.hip (stand-alone tcnn.Encoding
 // replacement) and field.hip (fused field).  Algorithm provenance: oracle/hashgrid_ref.c.
+// The level table, the kernels' by-value structs and the host-side planners are in mi3d_grid_plan.h (no HIP header:
+// it also builds with plain g++); this file adds the device-only parts.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/mi3d.h"
 #include "mi3d_common.h"
+#include "mi3d_grid_plan.h"
 
 namespace mi3d {
-
-struct GridTable {
-    GridLevel level[MI3D_MAX_LEVELS];
-    uint32_t n_levels;
-    uint32_t n_entries;
-};
-
-// Host: the level table exactly as tiny-cuda-nn's GridEncodingTemplated constructor lays it out.
-inline uint32_t build_grid_table(GridTable &T, uint32_t n_levels, uint32_t base_resolution, float per_level_scale,
-                                 uint32_t log2_hashmap_size) {
-    const float l2 = log2f(per_level_scale);
-    uint32_t offset = 0;
-    T.n_levels = n_levels;
-    for (uint32_t i = 0; i < n_levels && i < MI3D_MAX_LEVELS; ++i) {
-        GridLevel &L = T.level[i];
-        L.scale = exp2f((float)i * l2) * (float)base_resolution - 1.0f;
-        L.res = (uint32_t)ceilf(L.scale) + 1u;
-        const uint32_t max_params = 0xFFFFFFFFu / 2;
-        uint32_t size = (powf((float)L.res, 3.0f) > (float)max_params) ? max_params : L.res * L.res * L.res;
-        size = (size + 7u) / 8u * 8u;
-        const uint32_t cap = 1u << log2_hashmap_size;
-        if (size > cap) size = cap;
-        L.size = size;
-        L.offset = offset;
-        // which dims the dense stride loop covers before the stride exceeds the level size
-        uint32_t stride = 1, dims = 0;
-        for (; dims < 3 && stride <= size; ++dims) stride *= L.res;
-        L.dims = dims;
-        L.hashed = size < stride ? 1u : 0u;
-        offset += size;
-    }
-    T.n_entries = offset;
-    return offset;
-}
 
 // The 8 lattice corners of one point at one level: entry indices (relative to the level) and weights.
 // Corner k: bit0 -> +x, bit1 -> +y, bit2 -> +z (the order tcnn accumulates in).

@@ -1,9 +1,11 @@
 // Test helper (NOT product code): compiles make-it-3d_amd/csrc/mi3d_common.h - the exact scalar
-// math the HIP kernels use - for the HOST, so tests can compare it bit-for-bit with the oracle
+// math the HIP kernels use - and csrc/mi3d_grid_plan.h - the hash grid's host-side planners - for the
+// HOST, so tests can compare them bit-for-bit with the oracle and with libmi3d.so's own plan queries
 // without a GPU.  Built by tests/test_host_math.py with g++ -ffp-contract=off.
 #include <cstdint>
 #include <cstring>
 #include "mi3d_common.h"
+#include "mi3d_grid_plan.h"
 using namespace mi3d;
 
 extern "C" {
@@ -85,5 +87,44 @@ void hm_tr_offsets(uint32_t* wr_d, uint32_t* wr_x, uint32_t* rd, int32_t* row_by
         wr_d[lane] = tr_write_offset_d(lane); wr_x[lane] = tr_write_offset_x(lane); rd[lane] = tr_read_offset(lane);
     }
     *row_bytes = kTrRowBytes;
+}
+
+// the hash grid's planners (csrc/mi3d_grid_plan.h) built for the host: the signatures and output layouts of
+// mi3d_grid_encode_plan / mi3d_grid_scatter_plan (include/mi3d.h), 1 for an invalid argument
+int hm_grid_encode_plan(uint32_t n, float bound, float step, uint32_t n_levels, uint32_t base_resolution,
+                        float per_level_scale, uint32_t log2_hashmap_size, uint32_t* n_segments, uint32_t* segments) {
+    if (!valid_levels(n_levels) || n_segments == nullptr || segments == nullptr) return 1;
+    GridTable T;
+    build_grid_table(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size);
+    uint32_t n_lds = lds_levels(T, nullptr);
+    if (n_lds == T.n_levels) n_lds = 0;   // the query's rule: with every level in LDS it reports them in the XCD plan
+    const EncodePlan plan = plan_encode(T, n, step01_of(step, bound), n_lds, 0, -1, true).plan;
+    for (uint32_t x = 0; x < kXcds; x++) {
+        n_segments[x] = plan.n_seg[x];
+        for (uint32_t i = 0; i < (uint32_t)kMaxSegs; i++) {
+            const EncodeSeg sg = i < plan.n_seg[x] ? plan.seg[x][i] : EncodeSeg{0u, 0u, 0u, 0u};
+            uint32_t* o = segments + (x * kMaxSegs + i) * 3;
+            o[0] = sg.level; o[1] = sg.tile0; o[2] = sg.tile1;
+        }
+    }
+    return 0;
+}
+int hm_grid_scatter_plan(uint32_t n, uint32_t P, float bound, float step, uint32_t n_levels, uint32_t base_resolution,
+                         float per_level_scale, uint32_t log2_hashmap_size, size_t workspace_bytes,
+                         unsigned long long* out) {
+    if (!valid_levels(n_levels) || !valid_stencil(P, P, nullptr) || n == 0 || out == nullptr) return 1;
+    GridTable T;
+    build_grid_table(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size);
+    ScatterPlan sp = plan_scatter(T, n, P, bound, step, false, workspace_bytes);
+    BinPlan& p = sp.plan;
+    plan_reduce_splits(p, T, reduce_base_split(sp.n_slice * P), sp.merge_levels);
+    out[0] = sp.n_slice; out[1] = bin_workspace_bytes(p); out[2] = sp.merge_levels; out[3] = p.n_reduce_wgs;
+    out[4] = p.total_bytes; out[5] = p.total_counts;
+    for (uint32_t l = 0; l < n_levels; l++) {
+        unsigned long long* o = out + 6 + 7 * l;
+        o[0] = level_bins(T.level[l]); o[1] = p.level_cap[l]; o[2] = p.level_waves[l]; o[3] = (p.row_mask >> l) & 1u;
+        o[4] = p.level_split[l]; o[5] = p.level_wg0[l]; o[6] = p.level_cnt0[l];
+    }
+    return 0;
 }
 }

@@ -81,6 +81,6 @@ def test_product_library_reads_no_environment_and_has_no_dev_hooks():
     so = os.path.join(PKG, "csrc", "libmi3d.so")
     syms = subprocess.run(["nm", "-D", so], capture_output=True, text=True, check=True).stdout
     assert "getenv" not in syms and "mi3d_dev_" not in syms
-    for f in ("hashgrid.hip", "field.hip", "raymarching.hip"):
+    for f in ("hashgrid.hip", "field.hip", "raymarching.hip", "mi3d_grid_plan.h"):
         src = open(os.path.join(PKG, "csrc", f)).read()
         assert "getenv" not in src and "12345" not in src and "static bool" not in src, f

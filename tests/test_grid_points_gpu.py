@@ -384,6 +384,65 @@ def test_plane_kernels_are_bit_identical_to_the_row_kernel(cuda, oracle, bound, 
         assert torch.equal(got, want), (half, float((got.float() - want.float()).abs().max()))
 
 
+def test_plane_gather_is_right_whichever_counter_slot_a_launch_gets(cuda, oracle):
+    """The plane gather claims its tiles from one of 64 counter slots (csrc/hashgrid.hip EncodeSlotRing): a slot is handed
+    out once the event behind its last launch has completed, a launch that finds none deals its tiles statically, a launch
+    being captured never owns one.  70 launches - more than there are slots - alternating between two streams, then one
+    launch captured into a graph (a single stream: no parallel branches), replayed twice and followed by an eager launch:
+    every one of them bit-identical to the row kernel.  (What the test sees is the planes of every launch, not the slot it
+    took.)"""
+    from mi3d import _lib as L, grid_ops
+    rng = np.random.default_rng(31)
+    levels, base, log2, bound = 16, 16, 15, 1.0
+    cfg = oracle.GridConfig(bound=bound, n_levels=levels, base_resolution=base, log2_hashmap_size=log2)
+    kcfg = dict(n_levels=levels, base_resolution=base, per_level_scale=cfg.per_level_scale, log2_hashmap_size=log2)
+    n = 4096 + 37
+    x = _ray_like_points(rng, n, bound)
+    x[:64] = bound
+    x2 = (x + rng.normal(size=x.shape).astype(np.float32) * np.float32(0.01)).astype(np.float32)
+    offs, P0 = grid_ops.stencil_offsets(center=True, second=True)
+    P = offs.shape[0]
+    assert P == 13 and 0 < P0 < P
+    params = T(rng.uniform(-1, 1, cfg.n_params).astype(np.float32), cuda)
+    xd, x2d = T(x, cuda), T(x2, cuda)
+    rows = grid_ops.encode_points(params, xd, offs, kcfg, bound, x2d, P0)          # [P n, 2 L]: the row kernel, once
+    _, offs_p = grid_ops._offs_arg(offs)
+
+    def launch(planes):
+        with L.on(xd):
+            L.call("mi3d_grid_encode_points_planes", L.ptr(xd), L.ptr(x2d), n, offs_p, int(P0), P, float(bound),
+                   L.ptr(params), levels, base, cfg.per_level_scale, log2, 2 * 3 ** 0.5 / 1024 * bound, L.ptr(planes),
+                   0, L.stream(xd))
+
+    def same(planes):
+        return torch.equal(planes.permute(1, 0, 2).reshape(P * n, 2 * levels), rows)
+
+    outs = [torch.full((levels, P * n, 2), 7.0, device=cuda) for _ in range(70)]
+    streams = [torch.cuda.Stream(device=cuda), torch.cuda.Stream(device=cuda)]
+    torch.cuda.synchronize(cuda)
+    for i, planes in enumerate(outs):
+        with torch.cuda.stream(streams[i & 1]):
+            launch(planes)
+    torch.cuda.synchronize(cuda)
+    wrong = [i for i, planes in enumerate(outs) if not same(planes)]
+    assert wrong == [], wrong
+    del outs
+
+    planes = torch.full((levels, P * n, 2), 7.0, device=cuda)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+        launch(planes)
+    for replay in range(2):
+        planes.fill_(7.0)
+        graph.replay()
+        torch.cuda.synchronize(cuda)
+        assert same(planes), replay
+    planes.fill_(7.0)
+    launch(planes)
+    torch.cuda.synchronize(cuda)
+    assert same(planes)
+
+
 @pytest.mark.parametrize("log2", [10, 12])
 @pytest.mark.parametrize("half", [False, True])
 def test_binned_scatter_with_hash_tables_smaller_than_a_bin(cuda, oracle, half, log2):

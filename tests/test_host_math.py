@@ -17,9 +17,10 @@ HERE = os.path.join(ROOT, "tests", "host_math")
 def hm():
     so = os.path.join(HERE, "libhostmath.so")
     src = os.path.join(HERE, "host_math.cpp")
-    hdr = os.path.join(PKG, "csrc", "mi3d_common.h")
-    if not os.path.exists(so) or max(os.path.getmtime(src), os.path.getmtime(hdr)) > os.path.getmtime(so):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared",
+    hdrs = [os.path.join(PKG, "csrc", h) for h in ("mi3d_common.h", "mi3d_grid_plan.h", "mi3d_dev.h")]
+    if not os.path.exists(so) or max(os.path.getmtime(f) for f in [src] + hdrs) > os.path.getmtime(so):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-fno-fast-math",
+                               "-fPIC", "-shared",
                                "-I", os.path.join(PKG, "csrc"), src, "-o", so])
     return C.CDLL(so)
 
@@ -129,6 +130,21 @@ def test_row12_record_packing_and_the_x_pair_rule(hm):
         assert np.array_equal(e1, rule), size
         same_bin = (e0 >> 13) == (e1 >> 13)      # what the emit sends as ONE record (the others leave as two singles)
         assert 0.99 < same_bin.mean() <= 1.0
+
+
+def test_grid_planners_built_for_the_host_plan_what_the_library_plans(hm):
+    """csrc/mi3d_grid_plan.h is host code: built with plain g++ (no HIP header, -Wall -Wextra -Werror), its encode and
+    scatter planners return the very integers libmi3d.so's plan queries - and so its launches - return, over the whole
+    matrix of tests/plan_matrix.py."""
+    import plan_matrix
+    from mi3d import _lib
+    lib = _lib.lib()
+    for name, plans in (("encode", plan_matrix.encode_plans), ("scatter", plan_matrix.scatter_plans)):
+        host, product = plans(getattr(hm, f"hm_grid_{name}_plan")), plans(getattr(lib, f"mi3d_grid_{name}_plan"))
+        assert sorted(host) == sorted(product)
+        for k in host:
+            assert np.array_equal(host[k], product[k]), k
+        assert (host[f"{name}_rc"] == 0).all()
 
 
 def test_lds_tile_transposition_offsets(hm):

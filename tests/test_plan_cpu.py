@@ -1,6 +1,7 @@
 """Host-side planning of the two big field kernels, queried through the C ABI without a GPU: the gather's per-XCD
-segments (csrc/hashgrid.hip make_encode_plan) and the binned scatter's workspace / reduce layout (plan_for,
-plan_reduce_splits)."""
+segments (csrc/mi3d_grid_plan.h make_encode_plan) and the binned scatter's workspace / reduce layout (plan_for,
+plan_reduce_splits).  The queries and the launches of csrc/hashgrid.hip call the same planners (plan_encode,
+plan_scatter); tests/golden/grid_plans.npz holds what they returned before they shared them."""
 import ctypes as C
 import os
 import sys
@@ -107,7 +108,7 @@ def test_scatter_plan_small_pass_and_bad_arguments(lib):
 
 
 def test_level_routes_of_the_reference_configurations(lib, oracle):
-    """Which index route each level takes (csrc/hashgrid.hip level_fast) against the oracle's level table: a level is on
+    """Which index route each level takes (csrc/mi3d_grid_plan.h level_fast) against the oracle's level table: a level is on
     the dense route exactly when its res^3 entries fit its table (tcnn's rule for not hashing), on the masked-hash route
     when it is hashed into a power-of-two table, and raw positions (tcnn.Encoding's own entry points) never leave the
     general rule."""
@@ -127,3 +128,21 @@ def test_level_routes_of_the_reference_configurations(lib, oracle):
     k16 = (C.c_int32 * 16)()
     lib.call("mi3d_grid_level_routes", 16, 16, PLS, 19, 1, k16)
     assert list(k16) == [1] * 5 + [2] * 11      # the default grid: levels 0-4 dense, 5-15 hashed into 2^19 entries
+
+
+def test_plans_equal_the_recorded_ones(lib):
+    """Every integer the five planning queries return, and the return codes of their invalid-argument cases, over the
+    matrix of tests/plan_matrix.py: exactly what tests/golden/grid_plans.npz recorded (make_golden_plans.py) from the
+    library as it was before launches and queries shared one planner.  The plans are integers out of double arithmetic
+    on the host: equality is the bound."""
+    import plan_matrix
+    want = np.load(os.path.join(ROOT, "tests", "golden", "grid_plans.npz"))
+    got = plan_matrix.record(lib.lib())
+    assert sorted(got) == sorted(want.files)
+    assert list(got["invalid_case"]) == list(want["invalid_case"])
+    for k in want.files:
+        if k == "invalid_case":
+            continue
+        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, k
+        bad = np.argwhere(got[k] != want[k])
+        assert len(bad) == 0, (k, len(bad), bad[:4].tolist())
