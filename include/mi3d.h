@@ -34,8 +34,9 @@ extern "C" {
 
 /* the ABI version: 5 (4 = 3 + the compact-round inference loop of Part 1b; 5: that loop's ctl block is int32[16] with
  * the dropped-row count in [8], and its plan never passes max_steps; every other entry point is unchanged).  Part 8
- * (marching cubes), Part 9 (texture baking), Part 10 (GroupNorm), Part 12 (the Canny detector) and Part 1's
- * mi3d_composite_rays_train_backward_depth were added under 5: new symbols only, nothing existing changed. */
+ * (marching cubes), Part 9 (texture baking), Part 10 (GroupNorm), Part 12 (the Canny detector), Part 1's
+ * mi3d_composite_rays_train_backward_depth and the hash grid's input gradients (mi3d_hashgrid_backward_input of Part 2,
+ * mi3d_grid_points_backward_input of Part 3) were added under 5: new symbols only, nothing existing changed. */
 int mi3d_abi_version(void);
 const char *mi3d_last_error_string(int err);
 
@@ -188,6 +189,21 @@ int mi3d_hashgrid_forward(const float *x, uint32_t n, const float *params, uint3
 int mi3d_hashgrid_backward(const float *x, uint32_t n, const float *dout, uint32_t n_levels,
                            uint32_t base_resolution, float per_level_scale, uint32_t log2_hashmap_size,
                            float *grad_params, void *stream);
+/* tcnn.Encoding.backward wrt the INPUT: dout [n, n_levels*2] rows -> grad_x [n,3] = dL/dx, WRITTEN (not accumulated).
+ * tiny-cuda-nn gives this to any caller whose x requires grad; the reference never asks, so the arithmetic is this
+ * project's own contract - PARITY UNPINNED, the standing of this whole Part.  Per level l with scale s_l let (c, f) be
+ * cell and fraction of every dimension as the forward computes them (p = fma(s_l, q, 0.5), c = floor(p), f = p - c),
+ * w(0) = 1 - f, w(1) = f, and v[.] the eight corner pairs the forward gathers.  For dimension d, with e, e' the other two:
+ *     dy[l,feat]/dq_d = s_l * sum over (j,k) in {0,1}^2 of w_e(j) w_e'(k) (v[d=1,j,k].feat - v[d=0,j,k].feat)
+ *     dL/dq_d         = sum over l, feat of dout[l,feat] * dy[l,feat]/dq_d
+ * - the derivative of the trilinear interpolant INSIDE its cell.  The interpolant is piecewise linear: on a cell face the
+ * result is the derivative of the cell floor picked (the one-sided derivative towards +), not a mean of the two.  First order
+ * only.  fp32 throughout, plain stores, no atomics, one fixed order of additions: two calls give the same bits.
+ * n == 0: nothing is launched, success; a null pointer (n > 0) or n_levels > MI3D_MAX_LEVELS: hipErrorInvalidValue.
+ * Added under ABI version 5: a new symbol only. */
+int mi3d_hashgrid_backward_input(const float *x, uint32_t n, const float *dout, const float *params, uint32_t n_levels,
+                                 uint32_t base_resolution, float per_level_scale, uint32_t log2_hashmap_size,
+                                 float *grad_x, void *stream);
 
 /* ------------------------------------------------------------------ Part 3: stencil-aware grid ops */
 
@@ -206,6 +222,19 @@ int mi3d_grid_encode_points(const float *x, const float *x2, uint32_t n, const i
                             const float *offsets_host, uint32_t P0, uint32_t P, float bound, const float *params,
                             uint32_t n_levels, uint32_t base_resolution, float per_level_scale,
                             uint32_t log2_hashmap_size, float *out, void *stream);
+/* dL/dx and dL/dx2 of mi3d_grid_encode_points: dout [P*n, n_levels*2] point-major rows ->
+ * grad_x [n,3] = sum over the points p < P0, grad_x2 [n,3] = sum over P0 <= p < P (NULL if and only if x2 is NULL; a buffer
+ * passed without x2 is left untouched), both WRITTEN.  Per point the arithmetic is mi3d_hashgrid_backward_input's (Part 2) at q = (pt + bound) / (2 bound), times
+ * dq/dpt = 1 / (2 bound) - a multiplication by the reciprocal where 2 bound is a power of two, a division otherwise, as the
+ * forward maps the point - and coordinate d of point p reaches its base only where |base_d + offsets[p]_d| <= bound,
+ * bounds INCLUDED: the rule of torch.clamp's backward.  No device-side count: the counted rows belong to the inference
+ * loop, which never differentiates.  Deterministic like the Part 2 call.  n == 0: nothing is launched, success; a null
+ * pointer, a bad stencil (P > MI3D_MAX_POINTS, P0 > P, points around a NULL x2) or x2 without grad_x2:
+ * hipErrorInvalidValue.  Added under ABI version 5: a new symbol only. */
+int mi3d_grid_points_backward_input(const float *x, const float *x2, uint32_t n, const float *offsets_host, uint32_t P0,
+                                    uint32_t P, float bound, const float *dout, const float *params, uint32_t n_levels,
+                                    uint32_t base_resolution, float per_level_scale, uint32_t log2_hashmap_size,
+                                    float *grad_x, float *grad_x2, void *stream);
 /* mi3d_grid_encode_points with level-major output planes [n_levels][P*n][2] (feature pair of level l, row r = p*n + i
  * at out_planes[(l*P*n + r)*2]) - the layout the MLP kernels take with x_plane_rows = P*n.  The (level, tile) work is
  * tied to XCDs so each XCD's L2 only ever holds the table of the level it is gathering from; `step` (the marching

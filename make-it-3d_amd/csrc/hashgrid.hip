@@ -1,4 +1,4 @@
-// Multiresolution hash-grid encoding, forward and parameter-gradient backward, for MI355X (gfx950).
+// Multiresolution hash-grid encoding, forward, parameter-gradient backward and input-gradient backward, for MI355X (gfx950).
 // Replaces the tiny-cuda-nn `Encoding` the reference instantiates at
 // /root/reference/nerf/network_tcnn.py:54-65 (Part 2 of include/mi3d.h) and adds the multi-point form the
 // fused field uses (P stencil points per sample, network_tcnn.py:115-128).
@@ -153,6 +153,111 @@ __global__ __launch_bounds__(kWave *kWaves) void k_grid_encode(PointSet ps, uint
             out[((size_t)p * n_rows + s0 + i) * F + f] = tile[i * stride + f];
         }
         __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------- backward, input positions
+// dL/dx of k_grid_encode (include/mi3d.h Part 2 states the arithmetic): the derivative of the trilinear interpolant inside
+// the cell grid_cell picked, so cell, fraction and entries are the forward's own.  The forward's mapping: lane = sample,
+// wave w walks levels w, w + 4, ... (level constants in SGPRs, the eight gathers of a level in flight before the
+// arithmetic); level outermost, so the stencil points of a sample - neighbours in space - gather from one level's table
+// back to back.  Every wave keeps the 3 (mode 1 with x2: 6) components of its levels in registers, the four partial sums
+// meet in LDS and wave 0 adds them in wave order and stores: plain stores, no atomics, one fixed order of additions -
+// two runs are bit-identical.  Rounding chain of one term, which tests/test_grid_grad_gpu.py's bound counts: two
+// (1 - f), their product, the corner difference, weight x difference, three additions of the four (j, k) terms, x scale,
+// x dout (10), the two features added (1), [mode 1: x 1 / (2 bound) (1)], ceil(n_levels / 4) x P additions into the
+// wave's sum, three across the waves.
+__global__ __launch_bounds__(kWave *kWaves) void k_grid_backward_input(PointSet ps, uint32_t n,
+                                                                        const float *__restrict__ dout,
+                                                                        const float2 *__restrict__ table, GridTable T,
+                                                                        float *__restrict__ grad_x,
+                                                                        float *__restrict__ grad_x2) {
+    static_assert(kWaves == 4, "the closing sum below adds four waves' partial sums");
+    __shared__ float part[kWaves][6][kWave];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+    const uint32_t F = T.n_levels * 2;
+    const uint32_t s0 = blockIdx.x * kTile, s = s0 + lane;
+    if (s0 >= n) return;
+    const bool valid = s < n;
+    float base[2][3];
+    load_bases(ps, s, valid, base);
+    float acc[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};  // around x, around x2
+
+    for (uint32_t l = wave; l < T.n_levels; l += kWaves) {
+        const GridLevel L = T.level[l];
+        const float2 *lvl = table + L.offset;
+        for (uint32_t p = 0; p < ps.P; ++p) {
+            const float4 o = ps.offs[p];
+            const bool second = p >= ps.P0;
+            if (valid) {
+                float q[3];
+                point_of(ps, base, p, o, q);
+                uint32_t cx, cy, cz;
+                float fx, fy, fz;
+                grid_cell(q[0], L.scale, cx, fx);
+                grid_cell(q[1], L.scale, cy, fy);
+                grid_cell(q[2], L.scale, cz, fz);
+                uint32_t e[8];
+#pragma unroll
+                for (uint32_t k = 0; k < 8; ++k) e[k] = grid_entry(L, cx + (k & 1u), cy + ((k >> 1) & 1u), cz + (k >> 2));
+                float2 v[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = lvl[e[k]];  // 8 independent 8-byte gathers in flight
+                const float *drow = dout + ((size_t)p * n + s) * F + 2 * l;  // point-major rows
+                const float d0 = drow[0], d1 = drow[1];
+                const float gx = 1.0f - fx, gy = 1.0f - fy, gz = 1.0f - fz;
+                // the weights of the two OTHER dimensions, corner k = x-bit | y-bit << 1 | z-bit << 2
+                const float wyz[4] = {gy * gz, fy * gz, gy * fz, fy * fz};  // x pairs (0,1) (2,3) (4,5) (6,7)
+                const float wxz[4] = {gx * gz, fx * gz, gx * fz, fx * fz};  // y pairs (0,2) (1,3) (4,6) (5,7)
+                const float wxy[4] = {gx * gy, fx * gy, gx * fy, fx * fy};  // z pairs (0,4) (1,5) (2,6) (3,7)
+                const float tx0 = wyz[0] * (v[1].x - v[0].x) + wyz[1] * (v[3].x - v[2].x) + wyz[2] * (v[5].x - v[4].x) +
+                                  wyz[3] * (v[7].x - v[6].x);
+                const float tx1 = wyz[0] * (v[1].y - v[0].y) + wyz[1] * (v[3].y - v[2].y) + wyz[2] * (v[5].y - v[4].y) +
+                                  wyz[3] * (v[7].y - v[6].y);
+                const float ty0 = wxz[0] * (v[2].x - v[0].x) + wxz[1] * (v[3].x - v[1].x) + wxz[2] * (v[6].x - v[4].x) +
+                                  wxz[3] * (v[7].x - v[5].x);
+                const float ty1 = wxz[0] * (v[2].y - v[0].y) + wxz[1] * (v[3].y - v[1].y) + wxz[2] * (v[6].y - v[4].y) +
+                                  wxz[3] * (v[7].y - v[5].y);
+                const float tz0 = wxy[0] * (v[4].x - v[0].x) + wxy[1] * (v[5].x - v[1].x) + wxy[2] * (v[6].x - v[2].x) +
+                                  wxy[3] * (v[7].x - v[3].x);
+                const float tz1 = wxy[0] * (v[4].y - v[0].y) + wxy[1] * (v[5].y - v[1].y) + wxy[2] * (v[6].y - v[2].y) +
+                                  wxy[3] * (v[7].y - v[3].y);
+                float g[3] = {d0 * (L.scale * tx0) + d1 * (L.scale * tx1), d0 * (L.scale * ty0) + d1 * (L.scale * ty1),
+                              d0 * (L.scale * tz0) + d1 * (L.scale * tz1)};
+                if (ps.mode != 0) {
+                    // the chain through point_of: q = (clamp(base + offs) + bound) / (2 bound); the clamp passes the
+                    // gradient where |base + offs| <= bound, bounds included (torch.clamp's backward)
+                    const float bo[3] = {(second ? base[1][0] : base[0][0]) + o.x, (second ? base[1][1] : base[0][1]) + o.y,
+                                         (second ? base[1][2] : base[0][2]) + o.z};
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {
+                        const float c = ps.pow2b ? g[d] * ps.inv2b : g[d] / (2.0f * ps.bound);
+                        g[d] = fabsf(bo[d]) <= ps.bound ? c : 0.f;
+                    }
+                }
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {  // (no register array indexed by the point: adding 0 is exact)
+                    acc[0][d] += second ? 0.f : g[d];
+                    acc[1][d] += second ? g[d] : 0.f;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        part[wave][d][lane] = acc[0][d];
+        part[wave][3 + d][lane] = acc[1][d];
+    }
+    __syncthreads();
+    if (wave == 0 && valid) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            grad_x[(size_t)s * 3 + d] = ((part[0][d][lane] + part[1][d][lane]) + part[2][d][lane]) + part[3][d][lane];
+            if (grad_x2 != nullptr)
+                grad_x2[(size_t)s * 3 + d] =
+                    ((part[0][3 + d][lane] + part[1][3 + d][lane]) + part[2][3 + d][lane]) + part[3][3 + d][lane];
+        }
     }
 }
 
@@ -1771,6 +1876,36 @@ int mi3d_grid_encode_points(const float *x, const float *x2, uint32_t n, const i
     const PointSet ps = make_points(x, x2, offsets_host, P0, P, bound, 1);
     hipLaunchKernelGGL(k_grid_encode, dim3((n + kTile - 1) / kTile), dim3(kWave * kWaves), 0, as_stream(stream), ps, n,
                        count, reinterpret_cast<const float2 *>(params), T, out);
+    return (int)hipGetLastError();
+}
+
+int mi3d_hashgrid_backward_input(const float *x, uint32_t n, const float *dout, const float *params, uint32_t n_levels,
+                                 uint32_t base_resolution, float per_level_scale, uint32_t log2_hashmap_size,
+                                 float *grad_x, void *stream) {
+    GridTable T;
+    if (!grid_table_for(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size)) return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    if (x == nullptr || dout == nullptr || params == nullptr || grad_x == nullptr) return (int)hipErrorInvalidValue;
+    const PointSet ps = make_points(x, nullptr, nullptr, 1, 1, 1.0f, 0);
+    hipLaunchKernelGGL(k_grid_backward_input, dim3((n + kTile - 1) / kTile), dim3(kWave * kWaves), 0, as_stream(stream), ps,
+                       n, dout, reinterpret_cast<const float2 *>(params), T, grad_x, (float *)nullptr);
+    return (int)hipGetLastError();
+}
+
+int mi3d_grid_points_backward_input(const float *x, const float *x2, uint32_t n, const float *offsets_host, uint32_t P0,
+                                    uint32_t P, float bound, const float *dout, const float *params, uint32_t n_levels,
+                                    uint32_t base_resolution, float per_level_scale, uint32_t log2_hashmap_size,
+                                    float *grad_x, float *grad_x2, void *stream) {
+    GridTable T;
+    if (!grid_table_for(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size) || !valid_stencil(P0, P, x2) ||
+        (x2 != nullptr && grad_x2 == nullptr))
+        return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    if (x == nullptr || offsets_host == nullptr || dout == nullptr || params == nullptr || grad_x == nullptr)
+        return (int)hipErrorInvalidValue;
+    const PointSet ps = make_points(x, x2, offsets_host, P0, P, bound, 1);
+    hipLaunchKernelGGL(k_grid_backward_input, dim3((n + kTile - 1) / kTile), dim3(kWave * kWaves), 0, as_stream(stream), ps,
+                       n, dout, reinterpret_cast<const float2 *>(params), T, grad_x, x2 != nullptr ? grad_x2 : nullptr);
     return (int)hipGetLastError();
 }
 

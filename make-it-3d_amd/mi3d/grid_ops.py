@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import torch
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from . import _lib as L
 
@@ -153,6 +154,11 @@ class _EncodePoints(Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, params, x, x2, offsets, P0, bound, cfg, step, count):
+        wants_dx = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        if wants_dx and count is not None:
+            raise L.Mi3dError("encode_points with a device-side count does not differentiate the positions: the counted "
+                              "rows belong to the inference loop")
+        shapes = (x.shape, None if x2 is None else x2.shape)
         x = L.dev_f32(x.contiguous().view(-1, 3), "x", 3)
         if x2 is not None:
             x2 = L.dev_f32(x2.contiguous().view(-1, 3), "x2", 3)
@@ -167,30 +173,45 @@ class _EncodePoints(Function):
                 "mi3d_grid_encode_points", L.ptr(x), L.ptr(x2), n, L.ptr(count), offs_p, int(P0), P, float(bound),
                 L.ptr(params), cfg["n_levels"], cfg["base_resolution"], cfg["per_level_scale"],
                 cfg["log2_hashmap_size"], L.ptr(out), L.stream(x)), n * P)
-        ctx.save_for_backward(x, x2 if x2 is not None else x, count if count is not None else x)
+        saved = (x, x2 if x2 is not None else x, count if count is not None else x)
+        ctx.save_for_backward(*saved, *((params,) if wants_dx else ()))  # the input gradient gathers from the table again
         ctx.meta = (offs, int(P0), float(bound), cfg, float(step), x2 is not None, count is not None, params.numel())
+        ctx.shapes = shapes
         return out
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
+    @once_differentiable
     def backward(ctx, dout):
-        x, x2, count = ctx.saved_tensors
+        x, x2, count = ctx.saved_tensors[:3]
         offs, P0, bound, cfg, step, has_x2, has_count, n_params = ctx.meta
         dout = L.dev_f32(dout.float().contiguous(), "dout")
-        grad = torch.zeros(n_params, dtype=torch.float32, device=x.device)
+        grid = (cfg["n_levels"], cfg["base_resolution"], cfg["per_level_scale"], cfg["log2_hashmap_size"])
         _, offs_p = _offs_arg(offs)
-        with L.on(x):
-            _timed("scatter_rows", lambda: L.call(
-                "mi3d_grid_scatter_points", L.ptr(x), L.ptr(x2 if has_x2 else None), x.shape[0],
-                L.ptr(count if has_count else None), offs_p, P0, offs.shape[0], bound, L.ptr(dout), cfg["n_levels"],
-                cfg["base_resolution"], cfg["per_level_scale"], cfg["log2_hashmap_size"], step, L.ptr(grad),
-                L.stream(x)), x.shape[0] * offs.shape[0])
-        return grad, None, None, None, None, None, None, None, None
+        grad = grad_x = grad_x2 = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:  # first order only (once_differentiable)
+            grad_x = torch.empty_like(x)
+            grad_x2 = torch.empty_like(x2) if has_x2 else None
+            with L.on(x):
+                _timed("input_grad_rows", lambda: L.call(
+                    "mi3d_grid_points_backward_input", L.ptr(x), L.ptr(x2 if has_x2 else None), x.shape[0], offs_p, P0,
+                    offs.shape[0], bound, L.ptr(dout), L.ptr(ctx.saved_tensors[3]), *grid, L.ptr(grad_x), L.ptr(grad_x2),
+                    L.stream(x)), x.shape[0] * offs.shape[0])
+            grad_x = grad_x.view(ctx.shapes[0]) if ctx.needs_input_grad[1] else None
+            grad_x2 = grad_x2.view(ctx.shapes[1]) if has_x2 and ctx.needs_input_grad[2] else None
+        if ctx.needs_input_grad[0]:
+            grad = torch.zeros(n_params, dtype=torch.float32, device=x.device)
+            with L.on(x):
+                _timed("scatter_rows", lambda: L.call(
+                    "mi3d_grid_scatter_points", L.ptr(x), L.ptr(x2 if has_x2 else None), x.shape[0],
+                    L.ptr(count if has_count else None), offs_p, P0, offs.shape[0], bound, L.ptr(dout), *grid, step,
+                    L.ptr(grad), L.stream(x)), x.shape[0] * offs.shape[0])
+        return grad, grad_x, grad_x2, None, None, None, None, None, None
 
 
 def encode_points(params, x, offsets, cfg, bound=1.0, x2=None, P0=None, step=0.0, count=None):
     """features [P*n, 2L] (point-major: row = point*n + sample) of clamp(base + offsets[p]) for every sample;
-    differentiable w.r.t. `params`."""
+    differentiable w.r.t. `params` and - first order, without `count` - w.r.t. `x` and `x2`."""
     P = np.asarray(offsets).reshape(-1, 3).shape[0]
     if P0 is None:
         P0 = P

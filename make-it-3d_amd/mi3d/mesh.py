@@ -10,7 +10,7 @@
                    at every texel's surface point, packed to 8-bit RGB on the device
   export           volume -> surface -> per-vertex albedo (-> texture) -> files; what `NeRFRenderer.export_mesh` calls
   write_obj        vertex-coloured OBJ (`v x y z r g b`) + the reference's `mat0` material; with UVs `v` / `vt` /
-                   `f v/vt` and `map_Kd`
+                   `f v/vt` and `map_Kd`; with normals `vn` lines and `f v//vn` / `f v/vt/vn`
   write_png        8-bit RGB PNG with the standard library alone
 
 `mcubes`, `xatlas` and `nvdiffrast` (the reference's extractor, unwrapper and rasteriser) are on no machine this project
@@ -219,12 +219,15 @@ def write_png(path, image):
     return path
 
 
-def write_obj(path, vertices, triangles, colors, name="mesh", uvs=None, uv_faces=None, texture=None):
+def write_obj(path, vertices, triangles, colors, name="mesh", uvs=None, uv_faces=None, texture=None, normals=None):
     """`<path>/<name>.obj` (lines `v x y z r g b`, `f a b c` one-based) and `<path>/<name>.mtl`.  NumPy arrays:
     vertices [nv, 3], triangles [nt, 3] (zero-based), colors [nv, 3] in [0, 1].  Returns the two file names.
     With `uvs` [nuv, 2], `uv_faces` [nt, 3] (zero-based rows of uvs) and `texture` (an image file name, as the MTL is to
     cite it) - all three or none - the lines are `v x y z`, `vt u v`, `f a/ta b/tb c/tc` instead and the MTL ends with
-    `map_Kd <texture>`; `colors` is not written then."""
+    `map_Kd <texture>`; `colors` is not written then.
+    With `normals` [nv, 3] (one per vertex) a line `vn x y z` per vertex follows the `v` / `vt` block and the faces cite
+    normal a for vertex a: `f a//a b//b c//c`, textured `f a/ta/a b/tb/b c/tc/c`.  Without it the files are what they
+    were before the argument existed."""
     vertices, colors = np.asarray(vertices, np.float32), np.asarray(colors, np.float32)
     triangles = np.asarray(triangles)
     if vertices.ndim != 2 or vertices.shape[1] != 3 or colors.shape != vertices.shape:
@@ -238,6 +241,10 @@ def write_obj(path, vertices, triangles, colors, name="mesh", uvs=None, uv_faces
         uvs, uv_faces = np.asarray(uvs, np.float32), np.asarray(uv_faces)
         if uvs.ndim != 2 or uvs.shape[1] != 2 or uv_faces.shape != triangles.shape:
             raise ValueError(f"uvs must be [nuv, 2] and uv_faces [nt, 3] (got {uvs.shape} and {uv_faces.shape})")
+    if normals is not None:
+        normals = np.asarray(normals, np.float32)
+        if normals.shape != vertices.shape:
+            raise ValueError(f"normals must be [nv, 3] like vertices {vertices.shape} (got {normals.shape})")
     os.makedirs(path, exist_ok=True)
     obj, mtl = os.path.join(path, f"{name}.obj"), os.path.join(path, f"{name}.mtl")
     with open(obj, "w") as fp:
@@ -248,18 +255,31 @@ def write_obj(path, vertices, triangles, colors, name="mesh", uvs=None, uv_faces
             _write_rows(fp, "vt %.9g %.9g\n", uvs.astype(np.float64))
         else:
             _write_rows(fp, "v %.9g %.9g %.9g %.6f %.6f %.6f\n", np.concatenate([vertices, colors], 1).astype(np.float64))
+        if normals is not None:
+            _write_rows(fp, "vn %.9g %.9g %.9g\n", normals.astype(np.float64))
         fp.write("usemtl mat0\n")
-        if textured:
-            both = np.stack([triangles.astype(np.int64) + 1, uv_faces.astype(np.int64) + 1], -1).reshape(-1, 6)
+        tri = triangles.astype(np.int64) + 1
+        if textured and normals is not None:
+            _write_rows(fp, "f %d/%d/%d %d/%d/%d %d/%d/%d\n", np.stack([tri, uv_faces.astype(np.int64) + 1, tri], -1).reshape(-1, 9))
+        elif textured:
+            both = np.stack([tri, uv_faces.astype(np.int64) + 1], -1).reshape(-1, 6)
             _write_rows(fp, "f %d/%d %d/%d %d/%d\n", both)
+        elif normals is not None:
+            _write_rows(fp, "f %d//%d %d//%d %d//%d\n", np.stack([tri, tri], -1).reshape(-1, 6))
         else:
-            _write_rows(fp, "f %d %d %d\n", triangles.astype(np.int64) + 1)
+            _write_rows(fp, "f %d %d %d\n", tri)
     with open(mtl, "w") as fp:
         fp.write(MTL + (f"map_Kd {texture}\n" if textured else ""))
     return obj, mtl
 
 
-def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1):
+def vertex_normals(model, vertices):
+    """model.analytic_normal(vertices): the unit normal of the density isosurface at every vertex, float32 [nv, 3] (the
+    field's own chunking)."""
+    return model.analytic_normal(vertices).float()
+
+
+def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False):
     """What NeRFRenderer.export_mesh does (see there).  `S` only sizes the reference's chunks and is ignored."""
     del S
     if model.aabb_train.device.type != "cuda":
@@ -283,11 +303,14 @@ def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1):
         albedo = vertex_albedo(model, vertices)
         if texture_size is not None:
             image, vt, _ = bake_texture(model, vertices, triangles, texture_size, ssaa)
+        vn = vertex_normals(model, vertices).cpu().numpy() if normals else None
     v, f, c = vertices.cpu().numpy(), triangles.cpu().numpy(), albedo.cpu().numpy()
+    last = () if vn is None else (vn,)
     if texture_size is None:
-        write_obj(path, v, f, c)
-        return v, f, c
+        write_obj(path, v, f, c, normals=vn)
+        return (v, f, c) + last
     vt, image = vt.cpu().numpy(), image.cpu().numpy()
-    write_obj(path, v, f, c, uvs=vt, uv_faces=np.arange(3 * len(f), dtype=np.int64).reshape(-1, 3), texture="albedo.png")
+    write_obj(path, v, f, c, uvs=vt, uv_faces=np.arange(3 * len(f), dtype=np.int64).reshape(-1, 3), texture="albedo.png",
+              normals=vn)
     write_png(os.path.join(path, "albedo.png"), image)
-    return v, f, c, vt, image
+    return (v, f, c, vt, image) + last

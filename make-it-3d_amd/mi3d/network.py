@@ -155,6 +155,38 @@ class NeRFNetwork(NeRFRenderer):
     def normal(self, x):
         return torch.nan_to_num(safe_normalize(self.finite_difference_normal(x)))
 
+    def density_gradient(self, x):
+        """sigma [n] and its analytic gradient d sigma / dx [n, 3] in world units at x in [-bound, bound]^3: ONE forward and
+        ONE backward per point through common_forward's chain - the hash grid's input gradient (include/mi3d.h Part 3), the
+        MLP's, the blob term and trunc_exp's clamped derivative - where the finite-difference stencil takes seven
+        forwards and blurs over epsilon.  First order only.  fp32 whatever autocast says, in chunks of
+        mesh.CHUNK, and usable under torch.no_grad(); the table and the MLP weights enter detached: no scatter runs and no
+        parameter's `.grad` is created or touched."""
+        from . import mesh
+        x = x.reshape(-1, 3).float()
+        if not (self.sigma_net.fused_ok(x) and self.encoder.cfg["n_levels"] * 2 == self.sigma_net.dim_in):
+            raise grid_ops.L.Mi3dError("density_gradient needs the model on the GPU and an MLP the matrix-core kernels cover")
+        n = x.shape[0]
+        sigma = torch.empty(n, dtype=torch.float32, device=x.device)
+        grad = torch.empty(n, 3, dtype=torch.float32, device=x.device)
+        table = self.encoder.params.detach()
+        weights = tuple(None if t is None else t.detach() for t in mlp_ops.layer_args(self.sigma_net.net))
+        with torch.enable_grad(), torch.autocast("cuda", enabled=False):
+            for s in range(0, n, mesh.CHUNK):
+                xc = x[s:s + mesh.CHUNK].detach().requires_grad_()
+                feat = grid_ops.encode_points(table, xc, self._CENTER, self.encoder.cfg, float(self.bound))
+                h = mlp_ops._FusedMLP.apply(feat, *weights, False)
+                sig = trunc_exp(h[..., 0] + self.gaussian(xc))
+                (g,) = torch.autograd.grad(sig.sum(), xc)
+                sigma[s:s + mesh.CHUNK] = sig.detach()
+                grad[s:s + mesh.CHUNK] = g
+        return sigma, grad
+
+    def analytic_normal(self, x):
+        """The smooth normal of the density isosurface through x, -grad sigma / |grad sigma| [n, 3], from density_gradient;
+        the sign and the clean-up (safe_normalize, nan_to_num) are normal()'s."""
+        return torch.nan_to_num(safe_normalize(-self.density_gradient(x)[1]))
+
     def field_stencil(self, x, x2=None, step=0.0):
         x = x.reshape(-1, 3).float()
         offs, P0 = grid_ops.stencil_offsets(center=True, second=x2 is not None)

@@ -117,7 +117,7 @@ class NeRFRenderer(nn.Module):
         self.local_step = 0
 
     @torch.no_grad()
-    def export_mesh(self, path, resolution=None, S=128, texture_size=None, ssaa=1):
+    def export_mesh(self, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False):
         """renderer.py:157-191 + the file writing of :300-328, reached through main.py's `--save_mesh`: sigma on the
         `resolution`^3 lattice of [-1, 1]^3 (default grid_size), marching cubes at min(mean_density, density_thresh)
         (density_thresh without cuda_ray) on the GPU (mi3d.mesh), `<path>/mesh.obj` + `mesh.mtl`.  By default
@@ -128,9 +128,12 @@ class NeRFRenderer(nn.Module):
         axis): `mesh.obj` with `v` / `vt` / `f v/vt`, `mesh.mtl` with `map_Kd albedo.png`, and the T x T `albedo.png`;
         it then returns (vertices, triangles, albedo, vt [3 nt, 2] float32, image [T, T, 3] uint8).  A mesh too large
         for T raises Mi3dError naming a size that fits, before anything is written.  `S` is accepted and ignored.  A CPU
-        model raises Mi3dError."""
+        model raises Mi3dError.  With `normals=True` the field's analytic normal at every vertex (`analytic_normal`:
+        -grad sigma / |grad sigma|, DESIGN.md 13) is written as `vn` lines, the faces become `f v//vn` (`f v/vt/vn` with a
+        texture), and the returned tuple gains the [nv,3] float32 normals as its last element; with `normals=False` files
+        and return value are what they were without the argument."""
         from . import mesh
-        return mesh.export(self, path, resolution, S, texture_size=texture_size, ssaa=ssaa)
+        return mesh.export(self, path, resolution, S, texture_size=texture_size, ssaa=ssaa, normals=normals)
 
     @torch.no_grad()
     def export_point_cloud(self, outputdir, poses, ref_rgb, fov, H, W, **kwargs):

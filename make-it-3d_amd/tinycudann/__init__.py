@@ -2,7 +2,8 @@
 (/root/reference/nerf/network_tcnn.py:10,54-65,107,197): `tcnn.Encoding(n_input_dims=3,
 encoding_config={"otype": "HashGrid", ...}, dtype=torch.float32)`, an nn.Module with ONE flat fp32
 parameter tensor named `params` (state_dict key `encoder.params`), `forward(x [n,3] in [0,1]) ->
-[n, n_levels*2]`, differentiable w.r.t. `params`.  Backed by csrc/hashgrid.hip (gfx950).
+[n, n_levels*2]`, differentiable w.r.t. `params` and - first order - w.r.t. `x` when it requires grad, as
+tiny-cuda-nn's own `Encoding` is.  Backed by csrc/hashgrid.hip (gfx950).
 
 tiny-cuda-nn itself is an un-vendored, un-pinned dependency of the reference: the arithmetic here
 follows its published grid.h (see oracle/hashgrid_ref.c) - PARITY UNPINNED.
@@ -13,6 +14,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from mi3d import _lib as L
 from mi3d.grid_ops import GridParameter
@@ -24,26 +26,38 @@ class _hashgrid(Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, x, params, cfg):
+        shape = x.shape
         x = L.dev_f32(x.contiguous().view(-1, 3), "x", 3)
         params = L.dev_f32(params, "params")
         n = x.shape[0]
         out = torch.empty(n, cfg["n_levels"] * 2, dtype=torch.float32, device=x.device)
         L.launch("mi3d_hashgrid_forward", x, L.ptr(x), n, L.ptr(params), cfg["n_levels"], cfg["base_resolution"],
                cfg["per_level_scale"], cfg["log2_hashmap_size"], L.ptr(out))
-        ctx.save_for_backward(x)
-        ctx.cfg, ctx.n_params = cfg, params.numel()
+        if ctx.needs_input_grad[0]:  # the input gradient gathers from the table again
+            ctx.save_for_backward(x, params)
+        else:
+            ctx.save_for_backward(x)
+        ctx.cfg, ctx.n_params, ctx.x_shape = cfg, params.numel(), shape
         return out
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
+    @once_differentiable
     def backward(ctx, dout):
-        (x,) = ctx.saved_tensors
+        x = ctx.saved_tensors[0]
         cfg = ctx.cfg
         dout = L.dev_f32(dout.float().contiguous(), "dout")
-        grad = torch.zeros(ctx.n_params, dtype=torch.float32, device=x.device)
-        L.launch("mi3d_hashgrid_backward", x, L.ptr(x), x.shape[0], L.ptr(dout), cfg["n_levels"], cfg["base_resolution"],
-               cfg["per_level_scale"], cfg["log2_hashmap_size"], L.ptr(grad))
-        return None, grad, None  # no gradient w.r.t. the input positions (the reference never asks for it)
+        grid = (cfg["n_levels"], cfg["base_resolution"], cfg["per_level_scale"], cfg["log2_hashmap_size"])
+        grad_x = grad = None
+        if ctx.needs_input_grad[0]:  # first order only: once_differentiable makes a second derivative raise
+            grad_x = torch.empty_like(x)
+            L.launch("mi3d_hashgrid_backward_input", x, L.ptr(x), x.shape[0], L.ptr(dout), L.ptr(ctx.saved_tensors[1]),
+                     *grid, L.ptr(grad_x))
+            grad_x = grad_x.view(ctx.x_shape)
+        if ctx.needs_input_grad[1]:
+            grad = torch.zeros(ctx.n_params, dtype=torch.float32, device=x.device)
+            L.launch("mi3d_hashgrid_backward", x, L.ptr(x), x.shape[0], L.ptr(dout), *grid, L.ptr(grad))
+        return grad_x, grad, None
 
 
 def grid_levels(n_levels, base_resolution, per_level_scale, log2_hashmap_size):
