@@ -1,21 +1,32 @@
-// The field's MLP on the MI355X matrix cores: Linear(32,64)-ReLU-Linear(64,64)-ReLU-Linear(64,4), forward and
-// backward (input gradient + all weight/bias gradients) in ONE kernel each, activations never leave registers.
-// Replaces the three nn.Linear / two ReLU launches per field evaluation of the reference's `sigma_net`
-// (/root/reference/nerf/network_tcnn.py:13-32,67,107) - Part 4 of include/mi3d.h.
+// The field's MLP on the MI355X matrix cores, forward and backward (input gradient + all weight / bias gradients) in ONE
+// kernel each, activations never leave registers.  Replaces the nn.Linear / ReLU launches per field evaluation of the
+// reference's `sigma_net` (nerf/network_tcnn.py:13-32,67,107) - Part 4 of include/mi3d.h.  One pair of kernel templates
+// covers every shape the reference's MLP class builds around this field (it takes num_layers and hidden_dim): dim_in even
+// and <= 32 (padded to one K-block with zero weights), dim_hidden 32 or 64, 2 or 3 layers, dim_out 4.  The product's is
+// Linear(32,64)-ReLU-Linear(64,64)-ReLU-Linear(64,4); BASELINE config 1 is Linear(8,32)-ReLU-Linear(32,4).
 //
 // Dataflow (wave64, v_mfma_f32_32x32x16_f16 or, in exact-fp32 mode, v_mfma_f32_32x32x2_f32).  One wave owns a
 // TILE of 32 rows (field evaluations).  Every matrix product is D = A.B with a 32x32 output tile whose lane l holds
 // column (l & 31) and, in register q, row rowmap(q, l >> 5) = (q & 3) + 8 (q >> 2) + 4 (l >> 5).  A "K-block" is 32
 // contraction indices held as 16 values per lane: value q of lane-half h stands for index kmap(q, h).  Two facts
-// make the whole network chain through registers with no LDS round trip and no cross-lane traffic:
+// make the whole network chain through registers with no cross-lane traffic:
 //   (1) the hardware pairs A and B by K-SLOT, so any kmap works as long as both operands use it - in particular
 //       kmap = rowmap: the accumulators of one layer ARE the next layer's operand (after bias/ReLU/convert);
 //   (2) A and B fragments have the same lane layout (lane = row of A / column of B), so an activation tile held
 //       as "lane = sample, values = features" can be the B operand (output: lane = sample, rows = out features,
 //       "orientation 1") or the A operand (output: lane = out feature, rows = samples, "orientation 2").
-// Orientation 2 is what the weight gradients need (contraction over samples), so the backward kernel runs the
-// cheap 32-wide layers in both orientations instead of transposing tiles through LDS: 34 K-block products per tile
-// (64 MFMAs in fp16 mode, 2048 matrix-pipe cycles per 32 samples) - the kernel stays bound by streaming its rows.
+// The forward and the input gradient run in orientation 1.  The weight gradients contract over samples and need their
+// operands as "lane = feature, values = samples": the backward TRANSPOSES its orientation-1 tiles instead of recomputing
+// the layers in orientation 2 - binary16 tiles through the wave's own LDS (ds_read_b64_tr_b16, csrc/lds_transpose.h:
+// 4 writes + 4 transposing reads per lane, bit moves, nothing on the matrix core), exact-fp32 tiles as a product with an
+// identity block (exact: one non-zero product per output; the transposing read moves 16-bit values).  Per tile of the
+// product's shape that is 42 MFMAs and ~500 instructions in binary16; how it got there, round by round: DESIGN.md A.6, A.7.
+//
+// Registers: hipcc puts every MFMA result into the accumulator file as soon as a kernel may use more than 256 registers,
+// and VALU cannot read AGPRs, so each of the 16 values of every product then pays a move before its convert.  The kernels
+// are therefore held to TWO waves per SIMD (<= 256 registers): every MFMA takes its VGPR form, there is no accumulator
+// file, and the second wave fills the issue slots the first one leaves under its matrix products.  The one exception is
+// bwd_waves_per_simd() below.
 //
 // Weights live in LDS as ready-made operand blocks (one 16-byte vector per lane per read, conflict-free), built
 // once per workgroup from the fp32 master weights; fp16 mode rounds weights, biases and inter-layer activations to
@@ -25,22 +36,17 @@
 // workgroup in LDS and leave with one atomic per element per workgroup.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/mi3d.h"
 #include "mi3d_dev.h"
 #include "lds_transpose.h"
-
-// 1: the backward turns its binary16 tiles round through LDS (ds_read_b64_tr_b16, csrc/lds_transpose.h); 0: on the matrix
-// core, as a product with an identity block (round 3)
-#ifndef MI3D_MLP_LDS_TRANSPOSE
-#define MI3D_MLP_LDS_TRANSPOSE 1
-#endif
 
 namespace {
 
 constexpr int kWave = 64;
 constexpr int kWavesPerWG = 4;
-constexpr int DIN = 32, HID = 64, DOUT = 4;
-constexpr int NTH = HID / 32;  // 32-wide tiles across the hidden width
+constexpr int DIN = 32, DOUT = 4;  // the widest input (one K-block) and the output width
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
@@ -57,7 +63,7 @@ __device__ __forceinline__ int rowmap(int q, int h) { return (q & 3) + 8 * (q >>
 struct F16 {
     using elem = _Float16;
     static constexpr int kUnits = 2;  // 16-byte vectors per lane per K-block (8 halfs each)
-    static constexpr bool kLdsTranspose = MI3D_MLP_LDS_TRANSPOSE != 0;
+    static constexpr bool kLdsTranspose = true;  // the backward turns its tiles round through LDS (csrc/lds_transpose.h)
     struct KB { half8 v[2]; };
     __device__ static __forceinline__ float round(float x) { return (float)(_Float16)x; }
     __device__ static __forceinline__ void set(KB &k, int q, float x) { k.v[q >> 3][q & 7] = (_Float16)x; }
@@ -70,12 +76,6 @@ struct F16 {
     __device__ static __forceinline__ void mma(f32x16 &acc, const KB &a, const KB &b) {
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.v[0], b.v[0], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.v[1], b.v[1], acc, 0, 0, 0);
-    }
-    // one K-block product = kSteps matrix instructions; issuing step s of several products before step s + 1 of any
-    // keeps consecutive MFMAs on different accumulators
-    [[maybe_unused]] static constexpr int kSteps = 2;
-    __device__ static __forceinline__ void mma_step(f32x16 &acc, const KB &a, const KB &b, int s) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.v[s], b.v[s], acc, 0, 0, 0);
     }
     // only values q < 8 of both operands are non-zero
     __device__ static __forceinline__ void mma_lo(f32x16 &acc, const KB &a, const KB &b) {
@@ -168,18 +168,9 @@ struct F32 {
     struct KB { float v[16]; };
     __device__ static __forceinline__ float round(float x) { return x; }
     __device__ static __forceinline__ void set(KB &k, int q, float x) { k.v[q] = x; }
-    __device__ static __forceinline__ void set_pair_bits(KB &k, int j, uint32_t bits) {  // (binary16 planes: F16 mode only)
-        const half2v hv = __builtin_bit_cast(half2v, bits);
-        k.v[2 * j] = (float)hv[0];
-        k.v[2 * j + 1] = (float)hv[1];
-    }
     __device__ static __forceinline__ void mma(f32x16 &acc, const KB &a, const KB &b) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[q], b.v[q], acc, 0, 0, 0);
-    }
-    static constexpr int kSteps = 16;
-    __device__ static __forceinline__ void mma_step(f32x16 &acc, const KB &a, const KB &b, int s) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[s], b.v[s], acc, 0, 0, 0);
     }
     __device__ static __forceinline__ void mma_lo(f32x16 &acc, const KB &a, const KB &b) {
 #pragma unroll
@@ -222,119 +213,24 @@ struct F32 {
 
 template <class P> constexpr int block_bytes() { return P::kUnits * kWave * 16; }
 
-// ---------------------------------------------------------------- operand blocks in LDS
-// Block list (N = the dimension lanes run over, K = the contraction dimension; kind D: kmap = rowmap, kind X:
-// kmap(q, h) = 16 h + q, the layout rows are loaded from memory in):
-enum : int {
-    B_W1 = 0,              // [tn]      N = hidden-1 feature, K = input feature (X)      Wm[N][K] = W1[N][K]
-    B_W2 = B_W1 + NTH,     // [tn][tk]  N = hidden-2 feature, K = hidden-1 feature (D)   W2[N][K]
-    B_W3 = B_W2 + NTH * NTH,   // [tk]  N = output (4, zero padded), K = hidden-2 (D)    W3[N][K]
-    B_W3T = B_W3 + NTH,    // [tn]      N = hidden-2 feature, K = output index (X, < 4)  W3[K][N]
-    B_W2T = B_W3T + NTH,   // [tn][tk]  N = hidden-1 feature, K = hidden-2 feature (D)   W2[K][N]
-    B_W1T = B_W2T + NTH * NTH, // [tk]  N = input feature, K = hidden-1 feature (D)      W1[K][N]
-    B_ID = B_W1T + NTH,    //           N = index j, K = index k (X): (j == k) - as the B operand of a tile held
-                           //           "lane = sample" it hands back the tile "lane = index" (a transpose on the matrix core)
-    B_ALL_COUNT = B_ID + 1,
-};
-
 struct Weights {
     const float *W1, *b1, *W2, *b2, *W3, *b3;
 };
-
-template <class P>
-__device__ void build_blocks(char *lds, float *bias /* [HID + HID + 32] */, const Weights &w, int n_blocks) {
-    using T = typename P::elem;
-    for (int e = threadIdx.x; e < n_blocks * kWave * 16; e += blockDim.x) {
-        const int blk = e / (kWave * 16), r = e % (kWave * 16), lane = r / 16, q = r % 16;
-        const int nl = lane & 31, h = lane >> 5;
-        const int kd = rowmap(q, h), kx = 16 * h + q;
-        float v = 0.f;
-        if (blk < B_W2) {
-            const int tn = blk - B_W1;
-            v = w.W1[(32 * tn + nl) * DIN + kx];
-        } else if (blk < B_W3) {
-            const int tn = (blk - B_W2) / NTH, tk = (blk - B_W2) % NTH;
-            v = w.W2[(32 * tn + nl) * HID + 32 * tk + kd];
-        } else if (blk < B_W3T) {
-            const int tk = blk - B_W3;
-            v = nl < DOUT ? w.W3[nl * HID + 32 * tk + kd] : 0.f;
-        } else if (blk < B_W2T) {
-            const int tn = blk - B_W3T;
-            v = kx < DOUT ? w.W3[kx * HID + 32 * tn + nl] : 0.f;
-        } else if (blk < B_W1T) {
-            const int tn = (blk - B_W2T) / NTH, tk = (blk - B_W2T) % NTH;
-            v = w.W2[(32 * tk + kd) * HID + 32 * tn + nl];
-        } else if (blk < B_ID) {
-            const int tk = blk - B_W1T;
-            v = w.W1[(32 * tk + kd) * DIN + nl];
-        } else {
-            v = nl == kx ? 1.f : 0.f;
-        }
-        // value q of lane sits in 16-byte unit q / per_unit
-        constexpr int per_unit = 16 / (int)sizeof(T);
-        T *dst = reinterpret_cast<T *>(lds + (size_t)blk * block_bytes<P>() + ((q / per_unit) * kWave + lane) * 16);
-        dst[q % per_unit] = (T)v;
-    }
-    for (int e = threadIdx.x; e < HID + HID + 32; e += blockDim.x) {
-        float v = 0.f;
-        if (e < HID) v = w.b1[e];
-        else if (e < 2 * HID) v = w.b2[e - HID];
-        else if (e - 2 * HID < DOUT) v = w.b3[e - 2 * HID];
-        bias[e] = P::round(v);
-    }
-}
+struct Grads {
+    float *dW1, *db1, *dW2, *db2, *dW3, *db3;
+};
 
 // ---------------------------------------------------------------- tile pieces
-// rows of the tile as a K-block (kind X): lane (p, h) holds features 16 h .. 16 h + 15 of row row0 + p.
-// x is either [n, DIN] rows or (plane_rows != 0) level-major planes [DIN/2][plane_rows][2]: feature pair (2l, 2l+1) of
-// row r at x[(l plane_rows + r) 2]; plane_rows >= n lets a caller process a prefix of the rows of wider planes.
-// The 16 floats are fetched raw (so the backward can have the next tile's in flight while it computes) and turned into
-// the precision's K-block afterwards.
-// Rows past n are read from row n - 1 instead of being predicated off (no exec-mask branches around the loads, so all
-// of them are in flight together); their products are harmless: every weight-gradient term carries a factor dout,
-// which IS zeroed for those rows, and their outputs are never stored.
-// planes_half: the planes hold binary16 pairs (4 bytes per (level, row)) - see plane layouts in include/mi3d.h.
-__device__ __forceinline__ void load_rows_raw(const float *__restrict__ x, size_t row, size_t n, int h,
-                                              size_t plane_rows, float (&raw)[16], int planes_half = 0) {
-    row = row < n ? row : n - 1;
-    if (plane_rows != 0 && planes_half) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {  // 32 consecutive rows of one plane per load: 128 contiguous bytes per lane-half
-            const uint32_t u = reinterpret_cast<const uint32_t *>(x)[(size_t)(8 * h + j) * plane_rows + row];
-            raw[2 * j] = (float)__builtin_bit_cast(_Float16, (unsigned short)(u & 0xFFFFu));
-            raw[2 * j + 1] = (float)__builtin_bit_cast(_Float16, (unsigned short)(u >> 16));
-        }
-    } else if (plane_rows == 0) {
-        const f32x4 *src = reinterpret_cast<const f32x4 *>(x + row * DIN + 16 * h);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const f32x4 t = src[c];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) raw[4 * c + i] = t[i];
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {  // 32 consecutive rows of one plane per load: 256 contiguous bytes per lane-half
-            const f32x2 t = *reinterpret_cast<const f32x2 *>(x + ((size_t)(8 * h + j) * plane_rows + row) * 2);
-            raw[2 * j] = t[0];
-            raw[2 * j + 1] = t[1];
-        }
-    }
-}
+// fetched values -> the precision's K-block.  The loads (load_rows_raw_g / load_rows_half_g below) are issued one tile
+// ahead and converted at the use, so the backward has the next tile's rows in flight while it computes.
 template <class P> __device__ __forceinline__ typename P::KB rows_kb(const float (&raw)[16]) {
     typename P::KB k;
 #pragma unroll
     for (int q = 0; q < 16; ++q) P::set(k, q, raw[q]);
     return k;
 }
-// binary16 planes: the 8 dwords a lane fetches ARE its K-block (pair j = features 2j, 2j+1 of this lane-half) - the
-// backward keeps them as bit patterns while they are in flight and re-interprets them, no conversion either way
-[[maybe_unused]] __device__ __forceinline__ void load_rows_half(const float *__restrict__ x, size_t row, size_t n, int h,
-                                               size_t plane_rows, uint32_t (&u)[8]) {
-    row = row < n ? row : n - 1;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) u[j] = reinterpret_cast<const uint32_t *>(x)[(size_t)(8 * h + j) * plane_rows + row];
-}
+// binary16 planes: the 8 dwords a lane fetches ARE its K-block (pair j = features 2j, 2j+1 of this lane-half) - they stay
+// bit patterns while they are in flight and are re-interpreted, no conversion either way
 template <class P> __device__ __forceinline__ typename P::KB rows_kb_half(const uint32_t (&u)[8]) {
     typename P::KB k;
 #pragma unroll
@@ -360,444 +256,30 @@ __device__ __forceinline__ f32x16 splat(float v) {
     for (int q = 0; q < 16; ++q) a[q] = v;
     return a;
 }
-// bias along the ROWS of the tile (orientation 1: rows = features)
-__device__ __forceinline__ f32x16 bias_rows(const float *bias, int h) {
-    f32x16 a;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) a[q] = bias[rowmap(q, h)];
-    return a;
-}
-// ---------------------------------------------------------------- backward
-struct Grads {
-    float *dW1, *db1, *dW2, *db2, *dW3, *db3;
-};
 
-// U = tiles (of 32 rows) a wave works on at once, WPS = waves per SIMD the register allocation is held to.
-//
-// One wave per SIMD (the weight-gradient tiles alone are 128 registers), so nothing hides a latency but the wave's own
-// independent work.  Round 2 measured where the time went (tools/kbench.py): prefetching the next tile's rows gained
-// 1 ms of 20, the other 18 are the dependency chain product -> convert / mask -> next product, ~250 cycles per product
-// against 64 on the matrix pipe.  So the kernel is written in STAGES over U = 2 tiles x NTH = 2 output tiles: every
-// stage first issues the matrix products of all its (tile, output-tile) pairs step by step - consecutive MFMAs go to
-// different accumulators - and only then converts them, which gives the in-order wave four independent chains to
-// overlap (the packed converts of one accumulator run under the MFMAs of the next).
-template <class P, int U, int WPS, bool HP>
-__global__ __launch_bounds__(kWave *kWavesPerWG, WPS) void k_mlp_backward(const float *x, uint32_t x_planes,
-                                                                           int /*planes_half: HP*/, const float *__restrict__ dout,
-                                                                           uint32_t n, Weights w, float *dx,
-                                                                           uint32_t dx_planes, Grads g) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    float *bias = reinterpret_cast<float *>(lds + (size_t)B_ALL_COUNT * block_bytes<P>());
-    build_blocks<P>(lds, bias, w, B_ALL_COUNT);
-    __syncthreads();
-    const int lane = threadIdx.x & (kWave - 1), p = lane & 31, h = lane >> 5;
-    const uint32_t wave = blockIdx.x * kWavesPerWG + threadIdx.x / kWave, n_waves = gridDim.x * kWavesPerWG;
-    const uint32_t n_tiles = (n + 31) / 32;
-    using KB = typename P::KB;
-    // the lane offset is laundered through an empty asm so every use is a fresh LDS read: hipcc would otherwise
-    // hoist all (loop-invariant) operand blocks into registers and spill the accumulators
-    auto blk = [&](int b) {
-        int l = lane;
-        asm volatile("" : "+v"(l));
-        return P::load_block(lds + (size_t)b * block_bytes<P>(), l);
-    };
-
-    // weight-gradient tiles: lane = column (input-side feature), register q = row rowmap(q, h) (output-side feature)
-    f32x16 gW2[NTH][NTH], gW1[NTH], gW3[NTH];
-    float gb1[NTH], gb2[NTH], gb3 = 0.f;
-#pragma unroll
-    for (int a = 0; a < NTH; ++a) {
-        gW1[a] = splat(0.f); gW3[a] = splat(0.f); gb1[a] = 0.f; gb2[a] = 0.f;
-#pragma unroll
-        for (int b = 0; b < NTH; ++b) gW2[a][b] = splat(0.f);
-    }
-
-    // the rows of the NEXT group of tiles are requested before the current group's products start and are consumed one
-    // iteration later; tile u of a group is `u * n_waves` tiles further on, so every wave instruction still reads 32
-    // consecutive rows
-    float raw[HP ? 1 : U][16];
-    uint32_t rawh[HP ? U : 1][8];
-    f32x4 dor[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const size_t r0 = ((size_t)wave + (size_t)u * n_waves) * 32 + p;
-        if constexpr (HP) load_rows_half(x, r0, n, h, x_planes, rawh[u]);
-        else load_rows_raw(x, r0, n, h, x_planes, raw[u]);
-        dor[u] = load_dout_raw(dout, r0, n);
-    }
-    for (uint32_t tile = wave; tile < n_tiles; tile += U * n_waves) {
-        size_t row[U];
-        bool valid[U];
-        KB X[U], dO[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            row[u] = ((size_t)tile + (size_t)u * n_waves) * 32 + p;
-            valid[u] = row[u] < n;
-            if constexpr (HP) X[u] = rows_kb_half<P>(rawh[u]);
-            else X[u] = rows_kb<P>(raw[u]);
-            dO[u] = dout_kb<P>(dor[u], valid[u] && h == 0);
-        }
-        if (tile + U * n_waves < n_tiles) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const size_t rn = ((size_t)tile + (size_t)(U + u) * n_waves) * 32 + p;
-                if constexpr (HP) load_rows_half(x, rn, n, h, x_planes, rawh[u]);
-                else load_rows_raw(x, rn, n, h, x_planes, raw[u]);
-                dor[u] = load_dout_raw(dout, rn, n);
-            }
-        }
-
-        // ---- orientation 1 (lane = sample): recompute the activations (they double as their own ReLU masks)
-        KB H1[U][NTH], H2[U][NTH], dH2[U][NTH], dH1[U][NTH];
-        {
-            f32x16 acc[U][NTH];
-#pragma unroll
-            for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                for (int u = 0; u < U; ++u) acc[u][t] = bias_rows(bias + 32 * t, h);
-            {
-                KB Wb[NTH];
-#pragma unroll
-                for (int t = 0; t < NTH; ++t) Wb[t] = blk(B_W1 + t);
-#pragma unroll
-                for (int st = 0; st < P::kSteps; ++st)
-#pragma unroll
-                    for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                        for (int u = 0; u < U; ++u) P::mma_step(acc[u][t], Wb[t], X[u], st);
-            }
-#pragma unroll
-            for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                for (int u = 0; u < U; ++u) H1[u][t] = P::relu(acc[u][t]);
-        }
-        {
-            f32x16 acc[U][NTH];
-#pragma unroll
-            for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                for (int u = 0; u < U; ++u) acc[u][t] = bias_rows(bias + HID + 32 * t, h);
-#pragma unroll
-            for (int tk = 0; tk < NTH; ++tk) {
-                KB Wb[NTH];
-#pragma unroll
-                for (int t = 0; t < NTH; ++t) Wb[t] = blk(B_W2 + t * NTH + tk);
-#pragma unroll
-                for (int st = 0; st < P::kSteps; ++st)
-#pragma unroll
-                    for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                        for (int u = 0; u < U; ++u) P::mma_step(acc[u][t], Wb[t], H1[u][tk], st);
-            }
-#pragma unroll
-            for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                for (int u = 0; u < U; ++u) H2[u][t] = P::relu(acc[u][t]);
-        }
-        // ---- orientation 1: input-side gradients  dH2 = W3^T dO, dH1 = W2^T dH2, dX = W1^T dH1
-        {
-            f32x16 acc[U][NTH];
-            KB Wb[NTH];
-#pragma unroll
-            for (int t = 0; t < NTH; ++t) Wb[t] = blk(B_W3T + t);
-#pragma unroll
-            for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                for (int u = 0; u < U; ++u) { acc[u][t] = splat(0.f); P::mma_lo(acc[u][t], Wb[t], dO[u]); }
-#pragma unroll
-            for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                for (int u = 0; u < U; ++u) dH2[u][t] = P::masked(acc[u][t], H2[u][t]);
-        }
-        {
-            f32x16 acc[U][NTH];
-#pragma unroll
-            for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                for (int u = 0; u < U; ++u) acc[u][t] = splat(0.f);
-#pragma unroll
-            for (int tk = 0; tk < NTH; ++tk) {
-                KB Wb[NTH];
-#pragma unroll
-                for (int t = 0; t < NTH; ++t) Wb[t] = blk(B_W2T + t * NTH + tk);
-#pragma unroll
-                for (int st = 0; st < P::kSteps; ++st)
-#pragma unroll
-                    for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                        for (int u = 0; u < U; ++u) P::mma_step(acc[u][t], Wb[t], dH2[u][tk], st);
-            }
-#pragma unroll
-            for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                for (int u = 0; u < U; ++u) dH1[u][t] = P::masked(acc[u][t], H1[u][t]);
-        }
-        {
-            f32x16 acc[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) acc[u] = splat(0.f);
-#pragma unroll
-            for (int tk = 0; tk < NTH; ++tk) {
-                const KB Wb = blk(B_W1T + tk);
-#pragma unroll
-                for (int st = 0; st < P::kSteps; ++st)
-#pragma unroll
-                    for (int u = 0; u < U; ++u) P::mma_step(acc[u], Wb, dH1[u][tk], st);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (valid[u] && !dx_planes) {  // register q = input feature rowmap(q, h): four runs of four features
-                    float *dst = dx + row[u] * DIN + 4 * h;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        f32x4 o = {acc[u][4 * c], acc[u][4 * c + 1], acc[u][4 * c + 2], acc[u][4 * c + 3]};
-                        __builtin_nontemporal_store(o, reinterpret_cast<f32x4 *>(dst + 8 * c));
-                    }
-                } else if (valid[u] && HP) {
-                    // binary16 planes: one 4-byte store per (level, row); this IS the rounding torch.autocast gives the
-                    // input gradient of the first nn.Linear (a binary16 GEMM output)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const size_t lvl = 4 * c + 2 * h;
-                        const half2v a = __builtin_convertvector((f32x2){acc[u][4 * c], acc[u][4 * c + 1]}, half2v);
-                        const half2v b = __builtin_convertvector((f32x2){acc[u][4 * c + 2], acc[u][4 * c + 3]}, half2v);
-                        reinterpret_cast<uint32_t *>(dx)[lvl * dx_planes + row[u]] = __builtin_bit_cast(uint32_t, a);
-                        reinterpret_cast<uint32_t *>(dx)[(lvl + 1) * dx_planes + row[u]] = __builtin_bit_cast(uint32_t, b);
-                    }
-                } else if (valid[u]) {
-                    // level-major planes [DIN/2][dx_planes][2] (what the binned scatter reads): features (2l, 2l+1) of
-                    // this row are one 8-byte store; lane-half h owns levels 4c + 2h and 4c + 2h + 1, 32 consecutive
-                    // rows per store
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        f32x2 a = {acc[u][4 * c], acc[u][4 * c + 1]}, b = {acc[u][4 * c + 2], acc[u][4 * c + 3]};
-                        const size_t lvl = 4 * c + 2 * h;
-                        __builtin_nontemporal_store(a, reinterpret_cast<f32x2 *>(dx + (lvl * dx_planes + row[u]) * 2));
-                        __builtin_nontemporal_store(b, reinterpret_cast<f32x2 *>(dx + ((lvl + 1) * dx_planes + row[u]) * 2));
-                    }
-                }
-            }
-        }
-
-        // ---- orientation 2 (lane = feature, registers = the tile's 32 samples): operands of the weight gradients.
-        // (Stages are cut so that at most one set of U x NTH accumulators is live next to the 128 gradient registers.)
-        KB H1p[U][NTH];
-        {   // hidden-1 activations
-            f32x16 acc[U][NTH];
-#pragma unroll
-            for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                for (int u = 0; u < U; ++u) acc[u][t] = splat(bias[32 * t + p]);
-            KB Wb[NTH];
-#pragma unroll
-            for (int t = 0; t < NTH; ++t) Wb[t] = blk(B_W1 + t);
-#pragma unroll
-            for (int st = 0; st < P::kSteps; ++st)
-#pragma unroll
-                for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                    for (int u = 0; u < U; ++u) P::mma_step(acc[u][t], X[u], Wb[t], st);
-#pragma unroll
-            for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                for (int u = 0; u < U; ++u) H1p[u][t] = P::relu(acc[u][t]);
-        }
-        KB dH2p[U][NTH];
-        {
-            KB H2p[U][NTH], dOp[U];
-            {   // hidden-2 activations (the mask, and the operand of dW3)
-                f32x16 acc[U][NTH];
-#pragma unroll
-                for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                    for (int u = 0; u < U; ++u) acc[u][t] = splat(bias[HID + 32 * t + p]);
-#pragma unroll
-                for (int tk = 0; tk < NTH; ++tk) {
-                    KB Wb[NTH];
-#pragma unroll
-                    for (int t = 0; t < NTH; ++t) Wb[t] = blk(B_W2 + t * NTH + tk);
-#pragma unroll
-                    for (int st = 0; st < P::kSteps; ++st)
-#pragma unroll
-                        for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                            for (int u = 0; u < U; ++u) P::mma_step(acc[u][t], H1[u][tk], Wb[t], st);
-                }
-#pragma unroll
-                for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                    for (int u = 0; u < U; ++u) H2p[u][t] = P::relu(acc[u][t]);
-            }
-            {   // dO with lane = output index, values = samples: dO (lane = sample) times the identity block hands it
-                // back transposed (no gather loads); its sum over the samples is db3
-                const KB Id = blk(B_ID);
-                f32x16 tO[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) { tO[u] = splat(0.f); P::mma_lo(tO[u], dO[u], Id); }
-#pragma unroll
-                for (int u = 0; u < U; ++u) { dOp[u] = P::cast(tO[u]); gb3 += P::sum(dOp[u]); }
-            }
-            // dW3[o][f] += sum_s dO[s][o] H2[s][f]
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int st = 0; st < P::kSteps; ++st)
-#pragma unroll
-                    for (int t = 0; t < NTH; ++t) P::mma_step(gW3[t], dOp[u], H2p[u][t], st);
-            {   // gradient wrt hidden-2
-                f32x16 d[U][NTH];
-                KB Wb[NTH];
-#pragma unroll
-                for (int t = 0; t < NTH; ++t) Wb[t] = blk(B_W3T + t);
-#pragma unroll
-                for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                    for (int u = 0; u < U; ++u) { d[u][t] = splat(0.f); P::mma_lo(d[u][t], dO[u], Wb[t]); }
-#pragma unroll
-                for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        dH2p[u][t] = P::masked(d[u][t], H2p[u][t]);
-                        gb2[t] += P::sum(dH2p[u][t]);
-                    }
-            }
-        }
-        // dW2[i][j] += sum_s dH2[s][i] H1[s][j]
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int st = 0; st < P::kSteps; ++st)
-#pragma unroll
-                for (int ti = 0; ti < NTH; ++ti)
-#pragma unroll
-                    for (int tj = 0; tj < NTH; ++tj) P::mma_step(gW2[ti][tj], dH2p[u][ti], H1p[u][tj], st);
-        {   // the gradient wrt hidden-1 in orientation 2, the input rows with lane = input feature (X times the
-            // identity block), and dW1[i][j] += sum_s dH1[s][i] X[s][j]
-            KB dH1p[U][NTH], Xp[U];
-            {
-                f32x16 d[U][NTH];
-#pragma unroll
-                for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                    for (int u = 0; u < U; ++u) d[u][t] = splat(0.f);
-#pragma unroll
-                for (int tk = 0; tk < NTH; ++tk) {
-                    KB Wb[NTH];
-#pragma unroll
-                    for (int t = 0; t < NTH; ++t) Wb[t] = blk(B_W2T + t * NTH + tk);
-#pragma unroll
-                    for (int st = 0; st < P::kSteps; ++st)
-#pragma unroll
-                        for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                            for (int u = 0; u < U; ++u) P::mma_step(d[u][t], dH2[u][tk], Wb[t], st);
-                }
-#pragma unroll
-                for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        dH1p[u][t] = P::masked(d[u][t], H1p[u][t]);
-                        gb1[t] += P::sum(dH1p[u][t]);
-                    }
-            }
-            {
-                const KB Id = blk(B_ID);
-                f32x16 tX[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) tX[u] = splat(0.f);
-#pragma unroll
-                for (int st = 0; st < P::kSteps; ++st)
-#pragma unroll
-                    for (int u = 0; u < U; ++u) P::mma_step(tX[u], X[u], Id, st);
-#pragma unroll
-                for (int u = 0; u < U; ++u) Xp[u] = P::cast(tX[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int st = 0; st < P::kSteps; ++st)
-#pragma unroll
-                    for (int t = 0; t < NTH; ++t) P::mma_step(gW1[t], dH1p[u][t], Xp[u], st);
-        }
-    }
-
-    // ---- reduce the weight gradients across the workgroup in LDS, then one atomic per element per workgroup
-    __syncthreads();
-    float *red = reinterpret_cast<float *>(lds);
-    constexpr int OFF_W1 = 0, OFF_B1 = OFF_W1 + HID * DIN, OFF_W2 = OFF_B1 + HID, OFF_B2 = OFF_W2 + HID * HID,
-                  OFF_W3 = OFF_B2 + HID, OFF_B3 = OFF_W3 + DOUT * HID, TOTAL = OFF_B3 + DOUT;
-    for (int e = threadIdx.x; e < TOTAL; e += blockDim.x) red[e] = 0.f;
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const int r = rowmap(q, h);
-#pragma unroll
-        for (int ti = 0; ti < NTH; ++ti) {
-            atomicAdd(&red[OFF_W1 + (32 * ti + r) * DIN + p], gW1[ti][q]);
-#pragma unroll
-            for (int tj = 0; tj < NTH; ++tj) atomicAdd(&red[OFF_W2 + (32 * ti + r) * HID + 32 * tj + p], gW2[ti][tj][q]);
-            if (r < DOUT) atomicAdd(&red[OFF_W3 + r * HID + 32 * ti + p], gW3[ti][q]);
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < NTH; ++t) {
-        atomicAdd(&red[OFF_B1 + 32 * t + p], gb1[t]);
-        atomicAdd(&red[OFF_B2 + 32 * t + p], gb2[t]);
-    }
-    if (p < DOUT) atomicAdd(&red[OFF_B3 + p], gb3);
-    __syncthreads();
-    for (int e = threadIdx.x; e < TOTAL; e += blockDim.x) {
-        const float v = red[e];
-        float *dst = e < OFF_B1 ? g.dW1 + (e - OFF_W1)
-                   : e < OFF_W2 ? g.db1 + (e - OFF_B1)
-                   : e < OFF_B2 ? g.dW2 + (e - OFF_W2)
-                   : e < OFF_W3 ? g.db2 + (e - OFF_B2)
-                   : e < OFF_B3 ? g.dW3 + (e - OFF_W3)
-                                : g.db3 + (e - OFF_B3);
-        if (v != 0.f) unsafeAtomicAdd(dst, v);
-    }
-}
-
-// ================================================================ generic kernels (round 3)
-// The same dataflow for every shape the reference's MLP class builds around this field (network_tcnn.py:13-32,67 takes
-// num_layers and hidden_dim; BASELINE config 1 is Linear(8,32)-ReLU-Linear(32,4)): dim_in even and <= 32 (padded to one
-// K-block with zero weights), dim_hidden 32 or 64, 2 or 3 layers, dim_out 4 - and a different register plan.
-//
-// What round 2's profile showed (rocprofv3 + the ISA of k_mlp_backward): 12.0 ms for 141 M rows whatever the staging -
-// one tile at a time, two, prefetch or not - because the kernel was bound by INSTRUCTION ISSUE of its single wave per
-// SIMD: 1175 instructions per 32-row tile, 40 % of them v_accvgpr_read / _mov.  hipcc puts every MFMA result into the
-// accumulator file as soon as a kernel may use more than 256 registers (one wave per SIMD), and VALU cannot read AGPRs,
-// so each of the 16 values of every product paid a move before its convert.  Here the kernels are held to TWO waves
-// per SIMD (<= 256 registers, __launch_bounds__(256, 2)): the compiler then selects the VGPR form of every MFMA and
-// there is no accumulator file at all, the second wave fills the issue slots the first one leaves under its matrix
-// products, and the operands of the weight gradients (which need "lane = feature, registers = samples") come from
-// TRANSPOSING the orientation-1 tiles on the matrix core (a product with an identity block: 2 MFMAs and 8 converts per
-// K-block) instead of recomputing the layers in the second orientation (4 MFMAs, 16-32 converts / masks and a bias
-// splat per K-block): 61 MFMAs and 676 instructions per tile.
-//
-// Round 4: binary16 tiles are turned round through the wave's own LDS instead (ds_read_b64_tr_b16, csrc/lds_transpose.h:
-// 4 writes + 4 transposing reads per lane, nothing on the matrix core, no converts) - the kernel was issue-bound, and 20
-// of its 61 MFMAs moved bits.  43 MFMAs and ~500 instructions per tile with the instruction diet described at the
-// functions below (whole-register sums / masks, an instance of its own for the full input width, the next tile's rows
-// requested after this tile's last use of its own): 9.2-9.5 -> 8.3 ms for 141 M rows in one process
-// (tools/mlp_ab.py, profiles/mlp_ab_r04_final.json), every output of every instance bit-identical in the input
-// gradient.  The exact-fp32 kernels keep the identity product.
+// ---------------------------------------------------------------- operand blocks in LDS
+// One block is a 32 x 32 operand: lane (nl, h) holds, for index nl of N (the dimension lanes run over), the 16 values q
+// of its lane-half's indices of K (the contraction dimension).  K comes in two layouts: kind D, kmap = rowmap (what a
+// product leaves in its accumulators), and kind X, kmap(q, h) = 16 h + q (the layout rows are loaded from memory in).
+// NTH = hidden / 32 tiles across the hidden width; tn / tk = the tile of N / of K.
 template <int NTH, int LAYERS> struct Blk {
-    static constexpr int W1 = 0;                                      // [tn]      as B_W1
-    static constexpr int W2 = W1 + NTH;                               // [tn][tk]  as B_W2 (three layers only)
-    static constexpr int W3 = W2 + (LAYERS == 3 ? NTH * NTH : 0);     // [tk]      the LAST layer (4 outputs)
+    static constexpr int W1 = 0;                                      // [tn]      N = hidden-1 feature, K = input feature (X)      W1[N][K]
+    static constexpr int W2 = W1 + NTH;                               // [tn][tk]  N = hidden-2 feature, K = hidden-1 feature (D)   W2[N][K] (three layers only)
+    static constexpr int W3 = W2 + (LAYERS == 3 ? NTH * NTH : 0);     // [tk]      the LAST layer: N = output (4, zero padded), K = last hidden (D)
     static constexpr int FWD_COUNT = W3 + NTH;
-    static constexpr int W3T = FWD_COUNT;                             // [tn]
-    static constexpr int W2T = W3T + NTH;                             // [tn][tk]
-    static constexpr int W1T = W2T + (LAYERS == 3 ? NTH * NTH : 0);   // [tk]
-    static constexpr int IDX = W1T + NTH;                             // identity, K kind X (transposes X and dO)
-    static constexpr int IDD = IDX + 1;                               // identity, K kind D (transposes layer outputs)
+    static constexpr int W3T = FWD_COUNT;                             // [tn]      N = last hidden feature, K = output index (X, < 4)   W3[K][N]
+    static constexpr int W2T = W3T + NTH;                             // [tn][tk]  N = hidden-1 feature, K = hidden-2 feature (D)   W2[K][N]
+    static constexpr int W1T = W2T + (LAYERS == 3 ? NTH * NTH : 0);   // [tk]      N = input feature, K = hidden-1 feature (D)      W1[K][N]
+    // identity blocks, (N == K): as the B operand of a tile held "lane = sample" they hand back the tile "lane = index" (a
+    // transpose on the matrix core; exact fp32 only, binary16 tiles go through LDS)
+    static constexpr int IDX = W1T + NTH;                             // K kind X (transposes X and dO)
+    static constexpr int IDD = IDX + 1;                               // K kind D (transposes layer outputs)
     static constexpr int ALL_COUNT = IDD + 1;
     static constexpr int BIAS_TILES = 2 * NTH + 1;                    // b1[t], b2[t], b_last: [h][16] floats each
 };
 
-// Operand blocks (layouts as build_blocks above) for hidden width 32 NTH and input width din <= 32, plus the biases as
-// ready-made accumulator tiles: tile i, lane-half h, register q = bias of row rowmap(q, h) - one broadcast 64-byte read
+// The operand blocks for hidden width 32 NTH and input width din <= 32 (features past din: zero weights), plus the biases
+// as ready-made accumulator tiles: tile i, lane-half h, register q = bias of row rowmap(q, h) - one broadcast 64-byte read
 // per lane initialises an accumulator.
 template <class P, int NTH, int LAYERS>
 __device__ void build_blocks_g(char *lds, float *biasT, const Weights &w, int din, int n_blocks) {
@@ -856,8 +338,15 @@ __device__ __forceinline__ f32x16 bias_tile(const float *biasT, int tile, int h)
     return a;
 }
 
-// Rows of a tile for input width din <= 32.  Planes / features past din are read from the last valid one instead of
-// being predicated off (their weights are zero, so whatever finite value they carry contributes nothing).
+// Rows of a tile as a K-block (kind X): lane (p, h) holds features 16 h .. 16 h + 15 of row row0 + p, for input width
+// din <= 32.  x is either [n, din] rows or (plane_rows != 0) level-major planes [din/2][plane_rows][2]: feature pair
+// (2l, 2l+1) of row r at x[(l plane_rows + r) 2] - 32 consecutive rows of one plane per load; plane_rows >= n lets a caller
+// process a prefix of the rows of wider planes.  Binary16 planes hold 4 bytes per (level, row) - plane layouts in
+// include/mi3d.h.
+// Rows past n are read from row n - 1 instead of being predicated off (no exec-mask branches around the loads, so all
+// of them are in flight together); their products are harmless: every weight-gradient term carries a factor dout,
+// which IS zeroed for those rows, and their outputs are never stored.  Planes / features past din are read from the last
+// valid one in the same way (their weights are zero, so whatever finite value they carry contributes nothing).
 template <bool FULL = false>
 __device__ __forceinline__ void load_rows_half_g(const float *__restrict__ x, size_t row, size_t n, int h,
                                                  size_t plane_rows, uint32_t last_plane, uint32_t (&u)[8]) {
@@ -917,7 +406,9 @@ __global__ __launch_bounds__(kWave *kWavesPerWG, 2) void k_mlp_fwd_g(const float
     const int lane = threadIdx.x & (kWave - 1), p = lane & 31, h = lane >> 5;
     const uint32_t wave = blockIdx.x * kWavesPerWG + threadIdx.x / kWave, n_waves = gridDim.x * kWavesPerWG;
     const uint32_t n_tiles = (n + 31) / 32;
-    auto blk = [&](int b) {  // fresh LDS read at every use (see k_mlp_backward)
+    // the lane offset is laundered through an empty asm so every use is a fresh LDS read: hipcc would otherwise hoist all
+    // (loop-invariant) operand blocks into registers and spill the accumulators
+    auto blk = [&](int b) {
         int l = lane;
         asm volatile("" : "+v"(l));
         return P::load_block(lds + (size_t)b * block_bytes<P>(), l);
@@ -980,11 +471,18 @@ __global__ __launch_bounds__(kWave *kWavesPerWG, 2) void k_mlp_fwd_g(const float
 
 // x and dx carry no __restrict__ in the backward kernels: mi3d.h lets dx BE x (same layout), and the product calls it so.
 // (Register counts and scratch of every instance are the same with and without the qualifier - hipcc 7.2, gfx950.)
+//
+// Waves per SIMD the backward's register allocation is held to: two (see the head of the file), except for exact fp32 at
+// hidden 64 x 3 layers.  Its K-blocks are 16 registers (8 in binary16) and its weight-gradient tiles alone 128 of the 256
+// registers two waves leave each other - hipcc then spills 716 bytes per lane.  Held to one wave it takes 255 VGPRs + 256
+// AGPRs and no scratch, and the accumulator-file moves cost less than the spills did (measured: DESIGN.md A.6).
+template <class P, int NTH, int LAYERS> constexpr int bwd_waves_per_simd() {
+    return std::is_same<P, F32>::value && NTH == 2 && LAYERS == 3 ? 1 : 2;
+}
 template <class P, int NTH, int LAYERS, bool HP, bool FULL>   // FULL: dim_in = 32 (plane indices and store guards constant)
-__global__ __launch_bounds__(kWave *kWavesPerWG, 2) void k_mlp_bwd_g(const float *x, uint32_t x_planes,
-                                                                        const float *__restrict__ dout, uint32_t n,
-                                                                        uint32_t din, Weights w, float *dx,
-                                                                        uint32_t dx_planes, Grads g) {
+__global__ __launch_bounds__(kWave *kWavesPerWG, (bwd_waves_per_simd<P, NTH, LAYERS>())) void k_mlp_bwd_g(
+    const float *x, uint32_t x_planes, const float *__restrict__ dout, uint32_t n, uint32_t din, Weights w, float *dx,
+    uint32_t dx_planes, Grads g) {
     using B = Blk<NTH, LAYERS>;
     using KB = typename P::KB;
     constexpr int H = 32 * NTH;
@@ -1047,7 +545,7 @@ __global__ __launch_bounds__(kWave *kWavesPerWG, 2) void k_mlp_bwd_g(const float
     f32x4 dor;
     {
         const size_t r0 = (size_t)wave * 32 + p;
-        if constexpr (HP) load_rows_half_g<FULL && P::kLdsTranspose>(x, r0, n, h, x_planes, last_plane, rawh);
+        if constexpr (HP) load_rows_half_g<FULL>(x, r0, n, h, x_planes, last_plane, rawh);
         else load_rows_raw_g(x, r0, n, h, x_planes, din, raw);
         dor = load_dout_raw(dout, r0, n);
     }
@@ -1067,12 +565,12 @@ __global__ __launch_bounds__(kWave *kWavesPerWG, 2) void k_mlp_bwd_g(const float
                 const size_t rn = ((size_t)tile + n_waves) * 32 + p;
                 // (LDS transposes: the eight 64-bit plane indices of the prefetch are formed here from the laundered lane
                 // half instead of living across the tile as lane constants - they were what spilled, 20 registers)
-                if constexpr (HP) load_rows_half_g<FULL && P::kLdsTranspose>(x, rn, n, P::kLdsTranspose ? ht : h, xp, last_plane, rawh);
+                if constexpr (HP) load_rows_half_g<FULL>(x, rn, n, ht, xp, last_plane, rawh);
                 else load_rows_raw_g(x, rn, n, P::kLdsTranspose ? ht : h, xp, din, raw);
                 dor = load_dout_raw(dout, rn, n);
             }
         };
-        constexpr bool late_prefetch = P::kLdsTranspose && HP;
+        constexpr bool late_prefetch = HP;
         if constexpr (!late_prefetch) prefetch();
         // ---- forward recompute, lane = sample (the activations double as their own ReLU masks).  The order below keeps
         // the live set small (it is what decides spills at 256 registers): every orientation-1 tile is transposed
@@ -1174,7 +672,7 @@ __global__ __launch_bounds__(kWave *kWavesPerWG, 2) void k_mlp_bwd_g(const float
                     pk[2 * c] = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){acc[4 * c], acc[4 * c + 1]}, half2v));
                     pk[2 * c + 1] = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){acc[4 * c + 2], acc[4 * c + 3]}, half2v));
                 }
-                if (FULL && P::kLdsTranspose) {
+                if (FULL) {
                     uint32_t *dst = dxh + (size_t)(2 * h) * dxp;   // one lane address; the planes a uniform stride apart
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
@@ -1403,9 +901,6 @@ HeadArgs make_head_args(const float *x, const float *x2, const float *offsets_ho
     return a;
 }
 
-template <class P> constexpr size_t lds_bytes(int n_blocks) {
-    return (size_t)n_blocks * block_bytes<P>() + (HID + HID + 32) * sizeof(float);
-}
 template <class P> constexpr size_t lds_bytes_g(int n_blocks, int bias_tiles, bool transposes = false) {
     return (size_t)n_blocks * block_bytes<P>() + (size_t)bias_tiles * 32 * sizeof(float) +
            (transposes && P::kLdsTranspose ? (size_t)kWavesPerWG * mi3d_tr::kTileBytes : 0u);
@@ -1435,8 +930,8 @@ void launch_bwd(dim3 grid, hipStream_t st, const float *x, uint32_t x_planes, co
                 const Weights &w, float *dx, uint32_t dx_planes, const Grads &g) {
     using B = Blk<NTH, LAYERS>;
     // (binary16 planes at the full input width get their own instance: constant plane indices, no store guards)
-    if (HP && P::kLdsTranspose && din == (uint32_t)DIN)
-        hipLaunchKernelGGL((k_mlp_bwd_g<P, NTH, LAYERS, HP, HP && P::kLdsTranspose>), grid, dim3(kWave * kWavesPerWG),
+    if (HP && din == (uint32_t)DIN)
+        hipLaunchKernelGGL((k_mlp_bwd_g<P, NTH, LAYERS, HP, HP>), grid, dim3(kWave * kWavesPerWG),
                            lds_bytes_g<P>(B::ALL_COUNT, B::BIAS_TILES, true), st, x, x_planes, dout, n, din, w, dx, dx_planes, g);
     else
         hipLaunchKernelGGL((k_mlp_bwd_g<P, NTH, LAYERS, HP, false>), grid, dim3(kWave * kWavesPerWG),
@@ -1508,16 +1003,12 @@ int mi3d_mlp_backward(const void *xv, uint32_t x_plane_rows, int planes_half, co
     const Weights w{W1, b1, W2, b2, W3, b3};
     const Grads g{dW1, db1, dW2, db2, dW3, db3};
     const int nth = (int)dim_hidden / 32;
-    const dim3 grid(grid_for(n, MI3D_TUNE(MI3D_T_MLP_WGS_PER_CU, 2))), block(kWave * kWavesPerWG);
+    const dim3 grid(grid_for(n, MI3D_TUNE(MI3D_T_MLP_WGS_PER_CU, 2)));
     hipStream_t st = as_stream(stream);
-    const bool classic = nth == 2 && layers == 3 && dim_in == (uint32_t)DIN;
     if (half_mode && planes_half)
         MI3D_MLP_DISPATCH(launch_bwd, F16, true, nth, layers, grid, st, x, x_plane_rows, dout, n, dim_in, w, dx, dx_plane_rows, g);
     else if (half_mode)
         MI3D_MLP_DISPATCH(launch_bwd, F16, false, nth, layers, grid, st, x, x_plane_rows, dout, n, dim_in, w, dx, dx_plane_rows, g);
-    else if (classic)   // exact fp32 at full width: 16-register K-blocks do not fit two waves per SIMD - one wave, one tile
-        hipLaunchKernelGGL((k_mlp_backward<F32, 1, 1, false>), grid, block, lds_bytes<F32>(B_ALL_COUNT), st, x, x_plane_rows, 0,
-                           dout, n, w, dx, dx_plane_rows, g);
     else
         MI3D_MLP_DISPATCH(launch_bwd, F32, false, nth, layers, grid, st, x, x_plane_rows, dout, n, dim_in, w, dx, dx_plane_rows, g);
     return (int)hipGetLastError();

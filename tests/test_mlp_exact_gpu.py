@@ -67,8 +67,7 @@ k_mlp_fwd_g<F16,2,3,1>      half, planes16 hidden 64  3 layers
 k_mlp_fwd_g<F16,2,2,1>      half, planes16 hidden 64  2 layers
 k_mlp_fwd_g<F16,1,3,1>      half, planes16 hidden 32  3 layers
 k_mlp_fwd_g<F16,1,2,1>      half, planes16 hidden 32  2 layers
-k_mlp_backward<F32,1,1,0>   fp32           32 -> 64 -> 64 -> 4 (the classic kernel: one wave per SIMD)
-k_mlp_bwd_g<F32,2,3,0,0>    fp32           hidden 64  3 layers  dim_in < 32
+k_mlp_bwd_g<F32,2,3,0,0>    fp32           hidden 64  3 layers  every dim_in (one wave per SIMD)
 k_mlp_bwd_g<F32,2,2,0,0>    fp32           hidden 64  2 layers
 k_mlp_bwd_g<F32,1,3,0,0>    fp32           hidden 32  3 layers
 k_mlp_bwd_g<F32,1,2,0,0>    fp32           hidden 32  2 layers
@@ -94,8 +93,6 @@ def instances_of(mode, din, hid, layers):
     half, _, hp = MODES[mode]
     pol, nth = ("F16" if half else "F32"), hid // 32
     fwd = f"k_mlp_fwd_g<{pol},{nth},{layers},{hp}>"
-    if not half and nth == 2 and layers == 3 and din == 32:
-        return fwd, "k_mlp_backward<F32,1,1,0>"
     return fwd, f"k_mlp_bwd_g<{pol},{nth},{layers},{hp},{int(bool(hp) and din == 32)}>"
 
 
@@ -106,7 +103,7 @@ def test_matrix_reaches_every_instance():
     reached = set()
     for mode, din, hid, layers in CASES:
         reached |= set(instances_of(mode, din, hid, layers))
-    assert reached == set(INSTANCE_NAMES) and len(INSTANCE_NAMES) == 29
+    assert reached == set(INSTANCE_NAMES) and len(INSTANCE_NAMES) == 28
     from mi3d import _lib as L
     for _, din, hid, layers in CASES:
         assert L.lib().mi3d_mlp_supported(din, hid, 4, layers) == 1

@@ -1,9 +1,10 @@
 """A/B of the MLP backward across several builds of the library IN ONE PROCESS (all loaded with ctypes, same inputs,
 same box): equality of everything the kernel writes, for every template instance, and timings at the headline size.
 
-    python tools/build_dev.py tools/bin/libmi3d_dev_tr0.so -DMI3D_MLP_LDS_TRANSPOSE=0      # round 3's form: the reference
-    python tools/build_dev.py tools/bin/libmi3d_dev_tr1.so -DMI3D_MLP_LDS_TRANSPOSE=1      # the product's form
-    python tools/mlp_ab.py --libs tools/bin/libmi3d_dev_tr0.so,tools/bin/libmi3d_dev_tr1.so --out mlp_ab.json
+    # a product build of the parent commit (made in a checkout of it, the library copied over) against this tree's:
+    (cd make-it-3d_amd && python -c "import build; build.build(out='../tools/bin/libmi3d_parent.so')")   # the reference
+    (cd make-it-3d_amd && python -c "import build; build.build(out='../tools/bin/libmi3d_tree.so')")
+    python tools/mlp_ab.py --libs tools/bin/libmi3d_parent.so,tools/bin/libmi3d_tree.so --out mlp_ab.json
 
 The input gradient planes must be EQUAL as numbers to the first library's (a transposition moves values; -0.0 against
 +0.0 is the one difference the two ways of turning a tile may leave, and the scatter skips both); the weight gradients
@@ -116,6 +117,9 @@ def main():
                     case(rows, din, hid, layers, half_planes, half_mode, False)
     case(a.rows, 32, 64, 3, True, True, True)   # the headline: 13 points x 10.9 M samples, binary16 planes
     case(a.rows // 13, 32, 64, 3, True, True, True)   # the point-0 pass
+    # exact fp32, fp32 planes (at the headline's row count they would be 18 GB each): the one-wave instance, full and half width
+    case(a.rows // 13, 32, 64, 3, False, False, True)
+    case(a.rows // 13, 16, 64, 3, False, False, True)
     res["ok"] = ok
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
     json.dump(res, open(a.out, "w"), indent=1)
