@@ -36,7 +36,8 @@ extern "C" {
  * the dropped-row count in [8], and its plan never passes max_steps; every other entry point is unchanged).  Part 8
  * (marching cubes), Part 9 (texture baking), Part 10 (GroupNorm), Part 12 (the Canny detector), Part 1's
  * mi3d_composite_rays_train_backward_depth and the hash grid's input gradients (mi3d_hashgrid_backward_input of Part 2,
- * mi3d_grid_points_backward_input of Part 3) were added under 5: new symbols only, nothing existing changed. */
+ * mi3d_grid_points_backward_input of Part 3) and their second-order passes (mi3d_hashgrid_backward_input_backward,
+ * mi3d_grid_points_backward_input_backward) were added under 5: new symbols only, nothing existing changed. */
 int mi3d_abi_version(void);
 const char *mi3d_last_error_string(int err);
 
@@ -197,13 +198,38 @@ int mi3d_hashgrid_backward(const float *x, uint32_t n, const float *dout, uint32
  *     dy[l,feat]/dq_d = s_l * sum over (j,k) in {0,1}^2 of w_e(j) w_e'(k) (v[d=1,j,k].feat - v[d=0,j,k].feat)
  *     dL/dq_d         = sum over l, feat of dout[l,feat] * dy[l,feat]/dq_d
  * - the derivative of the trilinear interpolant INSIDE its cell.  The interpolant is piecewise linear: on a cell face the
- * result is the derivative of the cell floor picked (the one-sided derivative towards +), not a mean of the two.  First order
- * only.  fp32 throughout, plain stores, no atomics, one fixed order of additions: two calls give the same bits.
+ * result is the derivative of the cell floor picked (the one-sided derivative towards +), not a mean of the two.  This call is
+ * the first order; its own derivative is mi3d_hashgrid_backward_input_backward below.  fp32 throughout, plain stores,
+ * no atomics, one fixed order of additions: two calls give the same bits.
  * n == 0: nothing is launched, success; a null pointer (n > 0) or n_levels > MI3D_MAX_LEVELS: hipErrorInvalidValue.
  * Added under ABI version 5: a new symbol only. */
 int mi3d_hashgrid_backward_input(const float *x, uint32_t n, const float *dout, const float *params, uint32_t n_levels,
                                  uint32_t base_resolution, float per_level_scale, uint32_t log2_hashmap_size,
                                  float *grad_x, void *stream);
+/* The SECOND-ORDER pass: the backward of mi3d_hashgrid_backward_input, for losses that contain the input gradient (an
+ * eikonal term, losses on analytic normals).  tiny-cuda-nn's grid has it as backward_backward_input; the arithmetic is this
+ * project's own contract - PARITY UNPINNED.  g = grad_x of the call above is linear in dout and in the table and, inside
+ * a cell, bilinear in the fractions.  Given r [n,3] = dL/dg, with the notation above, sigma(0) = -1, sigma(1) = +1, the
+ * corners k = bx | by << 1 | bz << 2 and, per level, rho_d = r_d s_l, let
+ *     T_{d,c}    = sum_k sigma(b_d) w_e(b_e) w_e'(b_e') v[k].c          (g_d = sum_l sum_c dout[l,c] s_l T_{d,c})
+ *     M_{d,d',c} = sum_k sigma(b_d) sigma(b_d') w_e(b_e) v[k].c         (e the remaining dimension)
+ * Three outputs, each computed only if its pointer is not NULL:
+ *     grad_dout [n, n_levels*2] WRITTEN       grad_dout[l,c] = sum_d rho_d T_{d,c}
+ *     grad_x    [n,3]           WRITTEN       grad_q_d' = sum_l s_l sum_c dout[l,c] sum_{d != d'} rho_d M_{d,d',c}
+ *     grad_params [entries*2]   ACCUMULATED   grad_params[entry(k), c] += dout[l,c] kappa_k,
+ *                                             kappa_k = rho_x sigma(bx) w_y w_z + rho_y w_x sigma(by) w_z + rho_z w_x w_y sigma(bz)
+ * grad_x holds the mixed second derivatives of the trilinear interpolant inside its cell; the pure ones are zero.  The
+ * two row outputs come from one kernel, launched only if one of them is asked for: plain stores, one fixed order of
+ * additions, the same bits from call to call and whichever other outputs are asked for.  grad_params comes from a second
+ * kernel, launched only if asked for: the pointwise scatter with the trilinear weight replaced by kappa_k, float atomics
+ * (the caller zeroes; the order of the additions is free); a point whose dout pair is zero or whose three rho are zero
+ * adds nothing.  It is sized for the <= ~1e7 points a second-order loss is taken on.  n == 0: nothing is launched,
+ * success; a null input (n > 0), all three outputs NULL or n_levels > MI3D_MAX_LEVELS: hipErrorInvalidValue.
+ * Added under ABI version 5: a new symbol only. */
+int mi3d_hashgrid_backward_input_backward(const float *x, uint32_t n, const float *dout, const float *params,
+                                          const float *r, uint32_t n_levels, uint32_t base_resolution,
+                                          float per_level_scale, uint32_t log2_hashmap_size, float *grad_dout,
+                                          float *grad_x, float *grad_params, void *stream);
 
 /* ------------------------------------------------------------------ Part 3: stencil-aware grid ops */
 
@@ -235,6 +261,22 @@ int mi3d_grid_points_backward_input(const float *x, const float *x2, uint32_t n,
                                     uint32_t P, float bound, const float *dout, const float *params, uint32_t n_levels,
                                     uint32_t base_resolution, float per_level_scale, uint32_t log2_hashmap_size,
                                     float *grad_x, float *grad_x2, void *stream);
+/* The second-order pass of mi3d_grid_points_backward_input: r [n,3] = dL/dgrad_x, r2 [n,3] = dL/dgrad_x2 (not NULL
+ * exactly when x2 is not NULL).  Per point p the arithmetic is mi3d_hashgrid_backward_input_backward's (Part 2) at
+ * q = (pt + bound) / (2 bound) with rho_d = r_d m_d / (2 bound) s_l - r of the point's base, m_d = 1 where
+ * |base_d + offsets[p]_d| <= bound (bounds included) and 0 otherwise, the factor 1 / (2 bound) applied as the first-order
+ * call applies it - and grad_q_d' is multiplied by m_d' / (2 bound) again on its way to the base.  grad_dout [P*n,
+ * n_levels*2] point-major rows, WRITTEN; grad_x [n,3] = the sum over the points p < P0 and grad_x2 [n,3] = the sum over
+ * P0 <= p < P, WRITTEN (grad_x2 is passed exactly when both x2 and grad_x are: the two come from one sum); grad_params
+ * ACCUMULATED.  Each output is computed only if its pointer is not NULL, by the two kernels of the Part 2 call.  No
+ * device-side count.  n == 0: nothing is launched, success; a null input, all outputs NULL, a bad stencil, r2 without x2
+ * or x2 without r2, grad_x2 without x2 or without grad_x, x2 and grad_x without grad_x2: hipErrorInvalidValue.
+ * Added under ABI version 5: a new symbol only. */
+int mi3d_grid_points_backward_input_backward(const float *x, const float *x2, uint32_t n, const float *offsets_host,
+                                             uint32_t P0, uint32_t P, float bound, const float *dout, const float *params,
+                                             const float *r, const float *r2, uint32_t n_levels, uint32_t base_resolution,
+                                             float per_level_scale, uint32_t log2_hashmap_size, float *grad_dout,
+                                             float *grad_x, float *grad_x2, float *grad_params, void *stream);
 /* mi3d_grid_encode_points with level-major output planes [n_levels][P*n][2] (feature pair of level l, row r = p*n + i
  * at out_planes[(l*P*n + r)*2]) - the layout the MLP kernels take with x_plane_rows = P*n.  The (level, tile) work is
  * tied to XCDs so each XCD's L2 only ever holds the table of the level it is gathering from; `step` (the marching

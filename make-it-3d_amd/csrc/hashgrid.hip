@@ -1,4 +1,5 @@
-// Multiresolution hash-grid encoding, forward, parameter-gradient backward and input-gradient backward, for MI355X (gfx950).
+// Multiresolution hash-grid encoding, forward, parameter-gradient backward, input-gradient backward and the second-order
+// pass behind the input gradient, for MI355X (gfx950).
 // Replaces the tiny-cuda-nn `Encoding` the reference instantiates at
 // /root/reference/nerf/network_tcnn.py:54-65 (Part 2 of include/mi3d.h) and adds the multi-point form the
 // fused field uses (P stencil points per sample, network_tcnn.py:115-128).
@@ -244,6 +245,153 @@ __global__ __launch_bounds__(kWave *kWaves) void k_grid_backward_input(PointSet 
             }
         }
     }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        part[wave][d][lane] = acc[0][d];
+        part[wave][3 + d][lane] = acc[1][d];
+    }
+    __syncthreads();
+    if (wave == 0 && valid) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            grad_x[(size_t)s * 3 + d] = ((part[0][d][lane] + part[1][d][lane]) + part[2][d][lane]) + part[3][d][lane];
+            if (grad_x2 != nullptr)
+                grad_x2[(size_t)s * 3 + d] =
+                    ((part[0][3 + d][lane] + part[1][3 + d][lane]) + part[2][3 + d][lane]) + part[3][3 + d][lane];
+        }
+    }
+}
+
+// ---------------------------------------------------------------- second order: backward of the input gradient, rows
+// g = k_grid_backward_input(x, dout, table) is linear in dout and in the table and, inside a cell, bilinear in the
+// fractions; given r = dL/dg (mode 1: r2 for the points around x2) this kernel writes the two outputs that are rows
+// (include/mi3d.h Part 2 states the arithmetic):
+//     grad_dout[l, c] = sum_d rho_d T_{d,c}                                   T: the first-order kernel's sums
+//     grad_q_d'       = s sum_c dout[l, c] sum_{d != d'} rho_d M_{d,d',c}     M: the mixed second derivatives in the cell
+// with rho_d = r_d s (mode 1: r_d m_d / (2 bound) s, m_d the clamp's pass mask).  The pure second derivatives of a
+// trilinear interpolant are zero.  The mapping is k_grid_backward_input's: lane = sample, wave w walks levels w, w + 4,
+// ..., the eight gathers of a level in flight before the arithmetic.  The (row, level) pair of grad_dout belongs to ONE
+// wave, which stores it as one 8-byte pair; the grad_x partial sums meet in LDS and wave 0 adds them in wave order: plain
+// stores, one fixed order of additions - two runs are bit-identical, and an output that is not asked for (a null
+// pointer) is skipped without changing the arithmetic of the other.
+// Rounding chains of one term, which tests/test_grid_grad2_gpu.py's bounds count (a fused multiply-add only removes one):
+//   rho        r x scale (1); mode 1: r x 1 / (2 bound) or r / (2 bound) first (2)
+//   grad_dout  T as in the first-order kernel - two (1 - f), their product, the corner difference, weight x difference,
+//              three additions of the four (j, k) terms (8) - rho (1; mode 1: 2), rho x T (1), two additions of the three
+//              dimensions (2): 12, mode 1: 13
+//   grad_x     (1 - f) (1), the corner difference (1), the difference of two differences (1), weight x that (1), the two
+//              terms added (1) - M (5) - rho (1; mode 1: 2), rho x M (1), the two other dimensions added (1), x dout (1),
+//              the two features added (1), x scale (1): 11; mode 1: 12 and x 1 / (2 bound) (1): 13; then
+//              ceil(n_levels / 4) x P additions into the wave's sum and three across the waves.
+__global__ __launch_bounds__(kWave *kWaves) void k_grid_backward_input_backward_rows(
+    PointSet ps, uint32_t n, const float *__restrict__ dout, const float *__restrict__ r, const float *__restrict__ r2,
+    const float2 *__restrict__ table, GridTable T, float *__restrict__ grad_dout, float *__restrict__ grad_x,
+    float *__restrict__ grad_x2) {
+    static_assert(kWaves == 4, "the closing sum below adds four waves' partial sums");
+    __shared__ float part[kWaves][6][kWave];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+    const uint32_t F = T.n_levels * 2;
+    const uint32_t s0 = blockIdx.x * kTile, s = s0 + lane;
+    if (s0 >= n) return;
+    const bool valid = s < n;
+    float base[2][3], rr[2][3];
+    load_bases(ps, s, valid, base);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        rr[0][d] = valid ? r[(size_t)s * 3 + d] : 0.f;
+        rr[1][d] = (valid && r2 != nullptr) ? r2[(size_t)s * 3 + d] : 0.f;
+    }
+    float acc[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};  // around x, around x2
+
+    for (uint32_t l = wave; l < T.n_levels; l += kWaves) {
+        const GridLevel L = T.level[l];
+        const float2 *lvl = table + L.offset;
+        for (uint32_t p = 0; p < ps.P; ++p) {
+            const float4 o = ps.offs[p];
+            const bool second = p >= ps.P0;
+            if (valid) {
+                float q[3];
+                point_of(ps, base, p, o, q);
+                uint32_t cx, cy, cz;
+                float fx, fy, fz;
+                grid_cell(q[0], L.scale, cx, fx);
+                grid_cell(q[1], L.scale, cy, fy);
+                grid_cell(q[2], L.scale, cz, fz);
+                uint32_t e[8];
+#pragma unroll
+                for (uint32_t k = 0; k < 8; ++k) e[k] = grid_entry(L, cx + (k & 1u), cy + ((k >> 1) & 1u), cz + (k >> 2));
+                float2 v[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = lvl[e[k]];  // 8 independent 8-byte gathers in flight
+                const size_t row = ((size_t)p * n + s) * F + 2 * l;  // point-major rows
+                // rho and, in mode 1, the pass mask of the clamp (k_grid_backward_input's rule: bounds included)
+                float rho[3];
+                bool pass[3] = {true, true, true};
+#pragma unroll
+                for (int d = 0; d < 3; ++d) rho[d] = second ? rr[1][d] : rr[0][d];
+                if (ps.mode != 0) {
+                    const float bo[3] = {(second ? base[1][0] : base[0][0]) + o.x, (second ? base[1][1] : base[0][1]) + o.y,
+                                         (second ? base[1][2] : base[0][2]) + o.z};
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {
+                        pass[d] = fabsf(bo[d]) <= ps.bound;
+                        const float c = ps.pow2b ? rho[d] * ps.inv2b : rho[d] / (2.0f * ps.bound);
+                        rho[d] = pass[d] ? c : 0.f;
+                    }
+                }
+#pragma unroll
+                for (int d = 0; d < 3; ++d) rho[d] *= L.scale;
+                const float gx = 1.0f - fx, gy = 1.0f - fy, gz = 1.0f - fz;
+                if (grad_dout != nullptr) {
+                    // T: the first-order kernel's sums, corner k = x-bit | y-bit << 1 | z-bit << 2
+                    const float wyz[4] = {gy * gz, fy * gz, gy * fz, fy * fz};  // x pairs (0,1) (2,3) (4,5) (6,7)
+                    const float wxz[4] = {gx * gz, fx * gz, gx * fz, fx * fz};  // y pairs (0,2) (1,3) (4,6) (5,7)
+                    const float wxy[4] = {gx * gy, fx * gy, gx * fy, fx * fy};  // z pairs (0,4) (1,5) (2,6) (3,7)
+                    const float tx0 = wyz[0] * (v[1].x - v[0].x) + wyz[1] * (v[3].x - v[2].x) + wyz[2] * (v[5].x - v[4].x) +
+                                      wyz[3] * (v[7].x - v[6].x);
+                    const float tx1 = wyz[0] * (v[1].y - v[0].y) + wyz[1] * (v[3].y - v[2].y) + wyz[2] * (v[5].y - v[4].y) +
+                                      wyz[3] * (v[7].y - v[6].y);
+                    const float ty0 = wxz[0] * (v[2].x - v[0].x) + wxz[1] * (v[3].x - v[1].x) + wxz[2] * (v[6].x - v[4].x) +
+                                      wxz[3] * (v[7].x - v[5].x);
+                    const float ty1 = wxz[0] * (v[2].y - v[0].y) + wxz[1] * (v[3].y - v[1].y) + wxz[2] * (v[6].y - v[4].y) +
+                                      wxz[3] * (v[7].y - v[5].y);
+                    const float tz0 = wxy[0] * (v[4].x - v[0].x) + wxy[1] * (v[5].x - v[1].x) + wxy[2] * (v[6].x - v[2].x) +
+                                      wxy[3] * (v[7].x - v[3].x);
+                    const float tz1 = wxy[0] * (v[4].y - v[0].y) + wxy[1] * (v[5].y - v[1].y) + wxy[2] * (v[6].y - v[2].y) +
+                                      wxy[3] * (v[7].y - v[3].y);
+                    f32x2_native out = {rho[0] * tx0 + rho[1] * ty0 + rho[2] * tz0, rho[0] * tx1 + rho[1] * ty1 + rho[2] * tz1};
+                    *reinterpret_cast<f32x2_native *>(grad_dout + row) = out;  // (F and 2 l are even: 8-byte aligned)
+                }
+                if (grad_x != nullptr) {
+                    const float d0 = dout[row], d1 = dout[row + 1];
+                    // M: the mixed second derivatives, weighted over the remaining dimension
+                    const float mxy0 = gz * ((v[3].x - v[2].x) - (v[1].x - v[0].x)) + fz * ((v[7].x - v[6].x) - (v[5].x - v[4].x));
+                    const float mxy1 = gz * ((v[3].y - v[2].y) - (v[1].y - v[0].y)) + fz * ((v[7].y - v[6].y) - (v[5].y - v[4].y));
+                    const float mxz0 = gy * ((v[5].x - v[4].x) - (v[1].x - v[0].x)) + fy * ((v[7].x - v[6].x) - (v[3].x - v[2].x));
+                    const float mxz1 = gy * ((v[5].y - v[4].y) - (v[1].y - v[0].y)) + fy * ((v[7].y - v[6].y) - (v[3].y - v[2].y));
+                    const float myz0 = gx * ((v[6].x - v[4].x) - (v[2].x - v[0].x)) + fx * ((v[7].x - v[5].x) - (v[3].x - v[1].x));
+                    const float myz1 = gx * ((v[6].y - v[4].y) - (v[2].y - v[0].y)) + fx * ((v[7].y - v[5].y) - (v[3].y - v[1].y));
+                    float g[3] = {L.scale * (d0 * (rho[1] * mxy0 + rho[2] * mxz0) + d1 * (rho[1] * mxy1 + rho[2] * mxz1)),
+                                  L.scale * (d0 * (rho[0] * mxy0 + rho[2] * myz0) + d1 * (rho[0] * mxy1 + rho[2] * myz1)),
+                                  L.scale * (d0 * (rho[0] * mxz0 + rho[1] * myz0) + d1 * (rho[0] * mxz1 + rho[1] * myz1))};
+                    if (ps.mode != 0) {
+#pragma unroll
+                        for (int d = 0; d < 3; ++d) {
+                            const float c = ps.pow2b ? g[d] * ps.inv2b : g[d] / (2.0f * ps.bound);
+                            g[d] = pass[d] ? c : 0.f;
+                        }
+                    }
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {  // (no register array indexed by the point: adding 0 is exact)
+                        acc[0][d] += second ? 0.f : g[d];
+                        acc[1][d] += second ? g[d] : 0.f;
+                    }
+                }
+            }
+        }
+    }
+    if (grad_x == nullptr) return;  // (uniform over the workgroup: nobody waits at the barrier below)
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         part[wave][d][lane] = acc[0][d];
@@ -738,6 +886,90 @@ __global__ __launch_bounds__(kWave *kWaves) void k_scatter(PointSet ps, uint32_t
     }
 }
 
+// ---------------------------------------------------------------- second order: backward of the input gradient, table
+// The table's share of the second-order pass (include/mi3d.h Part 2): the input gradient is linear in the corner values,
+// so entry(k) of a point's cell receives dout[l, c] kappa_k with
+//     kappa_k = rho_x sigma(bx) w_y w_z + rho_y w_x sigma(by) w_z + rho_z w_x w_y sigma(bz)        sigma(0) = -1, sigma(1) = +1
+// - the pointwise scatter with the trilinear weight replaced by kappa_k.  k_scatter's quad mapping: lane (dx, f) of a quad
+// owns feature f of the four corners x + dx, so the 4 dwords of an x-neighbour pair leave in ONE request; atomic adds into
+// grad_table, which the caller zeroes.  A point whose dout pair is zero or whose three rho are zero (r == 0, a coordinate
+// the clamp stopped, padding) issues nothing.  No run merging and no bins: the pass is sized for the <= ~1e7 points a
+// second-order loss is taken on.  Rounding chain of one contribution: (1 - f) (1), the product of the two weights (1),
+// rho (1; mode 1: 2), rho x weights (1), two additions of the three terms (2), x dout (1): 7, mode 1: 8; the atomic
+// additions of an entry's N contributions come in any order (N - 1 more).
+__global__ __launch_bounds__(kWave *kWaves) void k_grid_backward_input_backward_table(
+    PointSet ps, uint32_t n, const float *__restrict__ dout, const float *__restrict__ r, const float *__restrict__ r2,
+    GridTable T, float *__restrict__ grad_table) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+    const uint32_t F = T.n_levels * 2;
+    const uint32_t s0 = blockIdx.x * kTile;
+    if (s0 >= n) return;
+    const uint32_t sub = lane & 3u, dx = sub >> 1, f = sub & 1u;
+
+    for (uint32_t g = 0; g < kTile / 16; ++g) {  // 16 samples per wave instruction
+        const uint32_t s = s0 + g * 16 + (lane >> 2);
+        const bool valid = s < n;
+        if (!__any(valid)) break;
+        float base[2][3], rr[2][3];
+        load_bases(ps, s, valid, base);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            rr[0][d] = valid ? r[(size_t)s * 3 + d] : 0.f;
+            rr[1][d] = (valid && r2 != nullptr) ? r2[(size_t)s * 3 + d] : 0.f;
+        }
+        for (uint32_t p = 0; p < ps.P; ++p) {
+            const float4 o = ps.offs[p];
+            const bool second = p >= ps.P0;
+            float q[3];
+            point_of(ps, base, p, o, q);
+            float rb[3];  // r, in mode 1 through the clamp's pass mask and x 1 / (2 bound): rho without the level's scale
+#pragma unroll
+            for (int d = 0; d < 3; ++d) rb[d] = second ? rr[1][d] : rr[0][d];
+            if (ps.mode != 0) {
+                const float bo[3] = {(second ? base[1][0] : base[0][0]) + o.x, (second ? base[1][1] : base[0][1]) + o.y,
+                                     (second ? base[1][2] : base[0][2]) + o.z};
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    const float c = ps.pow2b ? rb[d] * ps.inv2b : rb[d] / (2.0f * ps.bound);
+                    rb[d] = fabsf(bo[d]) <= ps.bound ? c : 0.f;
+                }
+            }
+            const bool live = valid && (rb[0] != 0.f || rb[1] != 0.f || rb[2] != 0.f);
+            if (!__any(live)) continue;
+            const size_t row = (size_t)p * n + s;  // point-major rows
+            const float *drow = dout + row * F + f;
+            for (uint32_t l = wave; l < T.n_levels; l += kWaves) {
+                const GridLevel L = T.level[l];
+                const float d = live ? drow[2 * l] : 0.f;
+                const float d_other = __shfl_xor(d, 1, 64);  // the quad's other feature (unconditional: all lanes)
+                const bool has = live && (d != 0.f || d_other != 0.f);
+                if (!__any(has)) continue;
+                uint32_t cx, cy, cz;
+                float fx, fy, fz;
+                grid_cell(q[0], L.scale, cx, fx);
+                grid_cell(q[1], L.scale, cy, fy);
+                grid_cell(q[2], L.scale, cz, fz);
+                const float gy = 1.0f - fy, gz = 1.0f - fz;
+                const float wx = dx ? fx : 1.0f - fx;
+                const float rx = dx ? rb[0] * L.scale : -(rb[0] * L.scale);  // sigma(bx) rho_x
+                const float ry = rb[1] * L.scale, rz = rb[2] * L.scale;
+                if (has) {
+                    float *lvl = grad_table + (size_t)L.offset * 2 + f;
+#pragma unroll
+                    for (uint32_t yz = 0; yz < 4; ++yz) {
+                        const float wy = (yz & 1u) ? fy : gy, wz = (yz >> 1) ? fz : gz;
+                        const float sy = (yz & 1u) ? ry : -ry, sz = (yz >> 1) ? rz : -rz;  // sigma(by) rho_y, sigma(bz) rho_z
+                        const float kappa = rx * (wy * wz) + sy * (wx * wz) + sz * (wx * wy);
+                        const uint32_t e = grid_entry(L, cx + dx, cy + (yz & 1u), cz + (yz >> 1));
+                        unsafeAtomicAdd(lvl + (size_t)e * 2, kappa * d);
+                    }
+                }
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------- backward, coarse levels ("runs" kernel)
 // Levels whose cells are longer than a marching step: consecutive samples of a ray (= consecutive lanes) sit in the
 // same cell for a whole RUN of lanes.  Lane = sample, so cell and weights are computed once per point (the quad kernel
@@ -860,6 +1092,19 @@ int launch_scatter(const PointSet &ps, uint32_t n, const int32_t *count, const f
     if (level_mask & ~runs_mask)
         hipLaunchKernelGGL(k_scatter, dim3((n + kTile - 1) / kTile), dim3(kWave * kWaves), 0, st, ps, n, count, dout, T,
                            merge_levels, level_mask & ~runs_mask, plane_rows, planes_half, n_rep, rep_stride, grad_params);
+    return (int)hipGetLastError();
+}
+
+// The second-order pass: the rows kernel where a row output is asked for, the table kernel where the table's is.
+int launch_second_order(const PointSet &ps, uint32_t n, const float *dout, const float *r, const float *r2,
+                        const float2 *table, const GridTable &T, float *grad_dout, float *grad_x, float *grad_x2,
+                        float *grad_params, hipStream_t st) {
+    const dim3 grid((n + kTile - 1) / kTile), block(kWave * kWaves);
+    if (grad_dout != nullptr || grad_x != nullptr)
+        hipLaunchKernelGGL(k_grid_backward_input_backward_rows, grid, block, 0, st, ps, n, dout, r, r2, table, T, grad_dout,
+                           grad_x, grad_x2);
+    if (grad_params != nullptr)
+        hipLaunchKernelGGL(k_grid_backward_input_backward_table, grid, block, 0, st, ps, n, dout, r, r2, T, grad_params);
     return (int)hipGetLastError();
 }
 
@@ -1907,6 +2152,39 @@ int mi3d_grid_points_backward_input(const float *x, const float *x2, uint32_t n,
     hipLaunchKernelGGL(k_grid_backward_input, dim3((n + kTile - 1) / kTile), dim3(kWave * kWaves), 0, as_stream(stream), ps,
                        n, dout, reinterpret_cast<const float2 *>(params), T, grad_x, x2 != nullptr ? grad_x2 : nullptr);
     return (int)hipGetLastError();
+}
+
+int mi3d_hashgrid_backward_input_backward(const float *x, uint32_t n, const float *dout, const float *params,
+                                          const float *r, uint32_t n_levels, uint32_t base_resolution,
+                                          float per_level_scale, uint32_t log2_hashmap_size, float *grad_dout,
+                                          float *grad_x, float *grad_params, void *stream) {
+    GridTable T;
+    if (!grid_table_for(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size)) return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    if (x == nullptr || dout == nullptr || params == nullptr || r == nullptr ||
+        (grad_dout == nullptr && grad_x == nullptr && grad_params == nullptr))
+        return (int)hipErrorInvalidValue;
+    const PointSet ps = make_points(x, nullptr, nullptr, 1, 1, 1.0f, 0);
+    return launch_second_order(ps, n, dout, r, nullptr, reinterpret_cast<const float2 *>(params), T, grad_dout, grad_x,
+                               nullptr, grad_params, as_stream(stream));
+}
+
+int mi3d_grid_points_backward_input_backward(const float *x, const float *x2, uint32_t n, const float *offsets_host,
+                                             uint32_t P0, uint32_t P, float bound, const float *dout, const float *params,
+                                             const float *r, const float *r2, uint32_t n_levels, uint32_t base_resolution,
+                                             float per_level_scale, uint32_t log2_hashmap_size, float *grad_dout,
+                                             float *grad_x, float *grad_x2, float *grad_params, void *stream) {
+    GridTable T;
+    if (!grid_table_for(T, n_levels, base_resolution, per_level_scale, log2_hashmap_size) || !valid_stencil(P0, P, x2) ||
+        (x2 != nullptr) != (r2 != nullptr) || (grad_x2 != nullptr) != (x2 != nullptr && grad_x != nullptr))
+        return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    if (x == nullptr || offsets_host == nullptr || dout == nullptr || params == nullptr || r == nullptr ||
+        (grad_dout == nullptr && grad_x == nullptr && grad_params == nullptr))
+        return (int)hipErrorInvalidValue;
+    const PointSet ps = make_points(x, x2, offsets_host, P0, P, bound, 1);
+    return launch_second_order(ps, n, dout, r, r2, reinterpret_cast<const float2 *>(params), T, grad_dout, grad_x, grad_x2,
+                               grad_params, as_stream(stream));
 }
 
 int mi3d_grid_encode_points_planes(const float *x, const float *x2, uint32_t n, const float *offsets_host, uint32_t P0,

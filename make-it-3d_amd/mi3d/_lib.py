@@ -45,9 +45,12 @@ _SIGNATURES = {
     "mi3d_hashgrid_forward": [vp, u32, vp, u32, u32, f32, u32, vp, vp],
     "mi3d_hashgrid_backward": [vp, u32, vp, u32, u32, f32, u32, vp, vp],
     "mi3d_hashgrid_backward_input": [vp, u32, vp, vp, u32, u32, f32, u32, vp, vp],
+    "mi3d_hashgrid_backward_input_backward": [vp, u32, vp, vp, vp, u32, u32, f32, u32, vp, vp, vp, vp],
     # Part 3 ------------------------------------------------------------------------------------------
     "mi3d_grid_encode_points": [vp, vp, u32, vp, vp, u32, u32, f32, vp, u32, u32, f32, u32, vp, vp],
     "mi3d_grid_points_backward_input": [vp, vp, u32, vp, u32, u32, f32, vp, vp, u32, u32, f32, u32, vp, vp, vp],
+    "mi3d_grid_points_backward_input_backward": [vp, vp, u32, vp, u32, u32, f32, vp, vp, vp, vp, u32, u32, f32, u32, vp, vp,
+                                                 vp, vp, vp],
     "mi3d_grid_scatter_points": [vp, vp, u32, vp, vp, u32, u32, f32, vp, u32, u32, f32, u32, f32, vp, vp],
     "mi3d_grid_encode_points_planes": [vp, vp, u32, vp, u32, u32, f32, vp, u32, u32, f32, u32, f32, vp, i32, vp],
     "mi3d_grid_scatter_binned": [vp, vp, u32, vp, u32, u32, f32, vp, i32, u32, u32, f32, u32, f32, vp, C.c_size_t, vp, vp],

@@ -1,5 +1,6 @@
 """Stencil-aware hash-grid encode (autograd): all P evaluation points of every sample in one launch, backward through
-the request-minimising scatter of csrc/hashgrid.hip (Part 3 of include/mi3d.h)."""
+the request-minimising scatter of csrc/hashgrid.hip (Part 3 of include/mi3d.h).  The positions' gradient is first order
+by default; encode_points(second_order=True) returns it from a node with a second-order pass (the last section below)."""
 import contextlib
 import ctypes as C
 
@@ -189,7 +190,7 @@ class _EncodePoints(Function):
         grid = (cfg["n_levels"], cfg["base_resolution"], cfg["per_level_scale"], cfg["log2_hashmap_size"])
         _, offs_p = _offs_arg(offs)
         grad = grad_x = grad_x2 = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:  # first order only (once_differentiable)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:  # first order only here (once_differentiable): _EncodePoints2
             grad_x = torch.empty_like(x)
             grad_x2 = torch.empty_like(x2) if has_x2 else None
             with L.on(x):
@@ -209,10 +210,140 @@ class _EncodePoints(Function):
         return grad, grad_x, grad_x2, None, None, None, None, None, None
 
 
-def encode_points(params, x, offsets, cfg, bound=1.0, x2=None, P0=None, step=0.0, count=None):
+# ------------------------------------------------------------------------------------------------ second order
+# encode_points(second_order=True) with positions that require grad: the same launches in the same order, behind nodes
+# whose input gradient can be differentiated once more (mi3d_grid_points_backward_input_backward, include/mi3d.h Part 3).
+# The positions and the table are saved as the INPUTS they are - flat fp32 tensors, cast and reshaped by tracked torch ops
+# in front of the node - so that a backward pass run under create_graph=True finds their graph again.
+
+def _grid_args(cfg):
+    return (cfg["n_levels"], cfg["base_resolution"], cfg["per_level_scale"], cfg["log2_hashmap_size"])
+
+
+class _PointsInputGrad(Function):
+    """dL/dx, dL/dx2 of encode_points as a differentiable node.  Its backward is the second-order pass: the rows kernel for
+    the gradients of dout and of the positions, the table kernel for the table's, each only where needs_input_grad asks."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, x, x2, dout, params, meta):
+        offs, P0, bound, cfg, _ = meta
+        dout = L.dev_f32(dout.contiguous(), "dout")
+        _, offs_p = _offs_arg(offs)
+        grad_x = torch.empty_like(x)
+        grad_x2 = torch.empty_like(x2) if x2 is not None else None
+        with L.on(x):
+            _timed("input_grad_rows", lambda: L.call(
+                "mi3d_grid_points_backward_input", L.ptr(x), L.ptr(x2), x.shape[0], offs_p, P0, offs.shape[0], bound,
+                L.ptr(dout), L.ptr(params), *_grid_args(cfg), L.ptr(grad_x), L.ptr(grad_x2), L.stream(x)),
+                x.shape[0] * offs.shape[0])
+        ctx.save_for_backward(x, dout, params, *(() if x2 is None else (x2,)))
+        ctx.meta = meta
+        return grad_x, grad_x2
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    @once_differentiable
+    def backward(ctx, r, r2):
+        x, dout, params = ctx.saved_tensors[:3]
+        x2 = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+        offs, P0, bound, cfg, _ = ctx.meta
+        _, offs_p = _offs_arg(offs)
+        n, evals = x.shape[0], x.shape[0] * offs.shape[0]
+        r = L.dev_f32(r.float().contiguous().view(-1, 3), "r", 3)
+        if x2 is not None:
+            r2 = L.dev_f32((torch.zeros_like(x2) if r2 is None else r2.float().contiguous()).view(-1, 3), "r2", 3)
+        need_x, need_x2, need_d, need_p = ctx.needs_input_grad[:4]
+        gx = torch.empty_like(x) if need_x or need_x2 else None
+        gx2 = torch.empty_like(x2) if gx is not None and x2 is not None else None
+        gd = torch.empty_like(dout) if need_d else None
+        gp = torch.zeros_like(params) if need_p else None
+
+        def launch(gd, gx, gx2, gp):
+            L.call("mi3d_grid_points_backward_input_backward", L.ptr(x), L.ptr(x2), n, offs_p, P0, offs.shape[0], bound,
+                   L.ptr(dout), L.ptr(params), L.ptr(r), L.ptr(r2 if x2 is not None else None), *_grid_args(cfg),
+                   L.ptr(gd), L.ptr(gx), L.ptr(gx2), L.ptr(gp), L.stream(x))
+        with L.on(x):
+            if gd is not None or gx is not None:
+                _timed("second_order_rows", lambda: launch(gd, gx, gx2, None), evals)
+            if gp is not None:
+                _timed("second_order_table", lambda: launch(None, None, None, gp), evals)
+        return (gx if need_x else None), (gx2 if need_x2 else None), gd, gp, None
+
+
+class _PointsParamGrad(Function):
+    """The parameter gradient of encode_points under second_order=True: the scatter of the first-order node.  It stays once
+    differentiable - differentiating it again raises, it is never a silent zero."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, x, x2, dout, n_params, meta):
+        offs, P0, bound, cfg, step = meta
+        dout = L.dev_f32(dout.contiguous(), "dout")
+        _, offs_p = _offs_arg(offs)
+        grad = torch.zeros(n_params, dtype=torch.float32, device=x.device)
+        with L.on(x):
+            _timed("scatter_rows", lambda: L.call(
+                "mi3d_grid_scatter_points", L.ptr(x), L.ptr(x2), x.shape[0], L.ptr(None), offs_p, P0, offs.shape[0], bound,
+                L.ptr(dout), *_grid_args(cfg), step, L.ptr(grad), L.stream(x)), x.shape[0] * offs.shape[0])
+        return grad
+
+    @staticmethod
+    def backward(ctx, *_):
+        raise RuntimeError("the hash grid's parameter gradient is once differentiable: only the input gradient has a "
+                           "second-order pass")
+
+
+class _EncodePoints2(Function):
+    """_EncodePoints for encode_points(second_order=True) with positions that require grad: the same forward launch; the
+    backward hands the same first-order launches to the two nodes above, so it can run under create_graph=True."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, params, x, x2, offsets, P0, bound, cfg, step):
+        L.dev_f32(x, "x", 3)
+        if x2 is not None:
+            L.dev_f32(x2, "x2", 3)
+        L.dev_f32(params, "params")
+        offs, offs_p = _offs_arg(offsets)
+        P, n = offs.shape[0], x.shape[0]
+        out = torch.empty(n * P, cfg["n_levels"] * 2, dtype=torch.float32, device=x.device)
+        with L.on(x):
+            _timed("encode_rows", lambda: L.call(
+                "mi3d_grid_encode_points", L.ptr(x), L.ptr(x2), n, L.ptr(None), offs_p, int(P0), P, float(bound),
+                L.ptr(params), *_grid_args(cfg), L.ptr(out), L.stream(x)), n * P)
+        ctx.save_for_backward(params, x, *(() if x2 is None else (x2,)))
+        ctx.meta = (offs, int(P0), float(bound), cfg, float(step))
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dout):
+        params, x = ctx.saved_tensors[:2]
+        x2 = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
+        dout = dout.float().contiguous()
+        grad = grad_x = grad_x2 = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            grad_x, grad_x2 = _PointsInputGrad.apply(x, x2, dout, params, ctx.meta)
+        if ctx.needs_input_grad[0]:
+            grad = _PointsParamGrad.apply(x, x2, dout, params.numel(), ctx.meta)
+        return (grad, grad_x if ctx.needs_input_grad[1] else None, grad_x2 if ctx.needs_input_grad[2] else None, None, None,
+                None, None, None)
+
+
+def encode_points(params, x, offsets, cfg, bound=1.0, x2=None, P0=None, step=0.0, count=None, second_order=False):
     """features [P*n, 2L] (point-major: row = point*n + sample) of clamp(base + offsets[p]) for every sample;
-    differentiable w.r.t. `params` and - first order, without `count` - w.r.t. `x` and `x2`."""
+    differentiable w.r.t. `params` and - without `count` - w.r.t. `x` and `x2`.  The input gradient is first order only
+    unless `second_order` is set: then it comes from a node that can be differentiated once more (an eikonal term, a loss
+    on analytic normals), by the same kernels with the same bits; the parameter gradient stays once differentiable.  With
+    the flag off, or with positions that do not require grad, nodes, saved tensors and launches are unchanged."""
     P = np.asarray(offsets).reshape(-1, 3).shape[0]
     if P0 is None:
         P0 = P
+    if second_order and torch.is_grad_enabled() and (x.requires_grad or (x2 is not None and x2.requires_grad)):
+        if count is not None:
+            raise L.Mi3dError("encode_points with a device-side count does not differentiate the positions: the counted "
+                              "rows belong to the inference loop")
+        flat = [None if t is None else t.float().contiguous().view(-1, 3) for t in (x, x2)]
+        return _EncodePoints2.apply(params, flat[0], flat[1], offsets, P0, bound, cfg, step)
     return _EncodePoints.apply(params, x, x2, offsets, P0, bound, cfg, step, count)

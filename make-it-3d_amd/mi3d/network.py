@@ -159,7 +159,8 @@ class NeRFNetwork(NeRFRenderer):
         """sigma [n] and its analytic gradient d sigma / dx [n, 3] in world units at x in [-bound, bound]^3: ONE forward and
         ONE backward per point through common_forward's chain - the hash grid's input gradient (include/mi3d.h Part 3), the
         MLP's, the blob term and trunc_exp's clamped derivative - where the finite-difference stencil takes seven
-        forwards and blurs over epsilon.  First order only.  fp32 whatever autocast says, in chunks of
+        forwards and blurs over epsilon.  First order only: the grid has a second-order pass, the fused MLP
+        between it and the density has none yet.  fp32 whatever autocast says, in chunks of
         mesh.CHUNK, and usable under torch.no_grad(); the table and the MLP weights enter detached: no scatter runs and no
         parameter's `.grad` is created or touched."""
         from . import mesh
