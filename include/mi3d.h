@@ -398,6 +398,28 @@ int mi3d_mlp_backward(const void *x, uint32_t x_plane_rows, int planes_half, con
                       const float *b3, uint32_t dim_in, uint32_t dim_hidden, uint32_t dim_out, int half_mode, void *dx,
                       uint32_t dx_plane_rows, float *dW1, float *db1, float *dW2, float *db2, float *dW3, float *db3,
                       void *stream);
+/* SECOND ORDER: the backward of mi3d_mlp_backward's dx, for losses on the input gradient.  Exact fp32, rows
+ * only: x, dout and r = dL/d(dx) are [n, dim_in], [n, dim_out] and [n, dim_in] rows.  With a1 = W1 x + b1, M1 = [a1 > 0],
+ * a2 = W2 relu(a1) + b2, M2 = [a2 > 0] (open iff not (activation <= 0), the first-order kernel's masks bit for bit: the
+ * forward is recomputed with the same product sequence) and the first-order chain
+ *   d2 = M2 (W3^T dy),  d1 = M1 (W2^T d2),  dx = W1^T d1
+ * one tangent chain through the same masks,
+ *   u1 = M1 (W1 r),  u2 = M2 (W2 u1),  u3 = W3 u2          (so that <dx, r> = dy^T u3),
+ * gives every output:
+ *   grad_dout [n, dim_out] = u3                                            plain stores
+ *   gW3 += sum_rows dy u2^T,  gW2 += sum_rows d2 u1^T,  gW1 += sum_rows d1 r^T     ACCUMULATED, caller zeroes
+ * Two layers (W2 == b2 == NULL; gW2 is ignored): u1 = M1 (W1 r), u3 = W3 u1, gW3 += dy u1^T, gW1 += d1 r^T.
+ * The gradients with respect to x and to the biases are exact zeros - dx depends on them through the piecewise constant
+ * masks only - and are not written.  grad_dout == NULL skips it; gW1 == gW2 == gW3 == NULL skips the weight gradients,
+ * which otherwise come together (gW1, gW3 and, with three layers, gW2); grad_dout has the same bits either way.  Rows at or
+ * past n are neither read nor written.  hipErrorInvalidValue: unsupported dims, a null x / dout / r / weight / bias, some but
+ * not all weight outputs, every output null.  (dout must be given even when grad_dout alone is asked for, although u3 does
+ * not depend on it and that launch never reads it: one rule for every call.)  n == 0 returns 0.  Never allocates, never synchronises.  No output may
+ * overlap an input. */
+int mi3d_mlp_backward_backward(const float *x, const float *dout, const float *r, uint32_t n, const float *W1,
+                               const float *b1, const float *W2, const float *b2, const float *W3, const float *b3,
+                               uint32_t dim_in, uint32_t dim_hidden, uint32_t dim_out, float *grad_dout, float *gW1,
+                               float *gW2, float *gW3, void *stream);
 
 /* ------------------------------------------------------------------ Part 5: the field head */
 

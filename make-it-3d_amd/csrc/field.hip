@@ -763,6 +763,203 @@ __global__ __launch_bounds__(kWave *kWavesPerWG, (bwd_waves_per_simd<P, NTH, LAY
     }
 }
 
+// ---------------------------------------------------------------- second-order pass (exact fp32, rows)
+// The backward of k_mlp_bwd_g's dx for r = dL/d(dx) [n, dim_in] (include/mi3d.h Part 4).  With the masks
+// M_l of the forward and the first-order chain d2 = M2 (W3^T dy), d1 = M1 (W2^T d2), dx = W1^T d1, one tangent chain
+//   u1 = M1 (W1 r),  u2 = M2 (W2 u1),  u3 = W3 u2
+// gives grad_dout = u3 and grad_W3 += dy u2^T, grad_W2 += d2 u1^T, grad_W1 += d1 r^T (two layers: drop the middle).  x and
+// the biases reach dx through the masks only: their gradients are exact zeros and are not written.
+//
+// Per tile the forward is recomputed with k_mlp_bwd_g's own product sequence (the masks are the ones the first-order pass
+// applied, bit for bit) and the d chain runs as it does there; the u chain is the forward's products on r without the
+// biases, each mask a select on the recomputed activation.  ROWS: u3 is stored (16 bytes per row, as the forward stores
+// y).  WG: the six factors are turned round with the identity blocks and the three weight-gradient tile sets accumulate
+// across the tiles of a persistent wave, leaving as in k_mlp_bwd_g.  The two are template flags, not branches: the
+// rows-only instance carries no accumulators, no d chain and no transposed blocks.  The u chain is the same code in all
+// three, so grad_dout does not depend on whether the weights were asked for.
+// Rows at or past n contribute nothing: their dy and r are zeroed, and every term carries one of them as a factor.
+//
+// Registers: as for k_mlp_bwd_g, hidden 64 x 3 layers with weight gradients is held to one wave per SIMD (128 accumulator
+// registers + 16-register K-blocks), every other instance to two; none uses scratch (table: DESIGN.md 15).
+template <int NTH, int LAYERS, bool WG> constexpr int bwd2_waves_per_simd() { return WG && NTH == 2 && LAYERS == 3 ? 1 : 2; }
+template <int NTH, int LAYERS, bool ROWS, bool WG>
+__global__ __launch_bounds__(kWave *kWavesPerWG, (bwd2_waves_per_simd<NTH, LAYERS, WG>())) void k_mlp_bwd2_g(
+    const float *__restrict__ x, const float *__restrict__ dout, const float *__restrict__ r, uint32_t n, uint32_t din,
+    Weights w, float *__restrict__ grad_dout, float *gW1o, float *gW2o, float *gW3o) {
+    using P = F32;
+    using B = Blk<NTH, LAYERS>;
+    using KB = typename P::KB;
+    constexpr int H = 32 * NTH;
+    constexpr int N_BLOCKS = WG ? B::ALL_COUNT : B::FWD_COUNT;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    float *biasT = reinterpret_cast<float *>(lds + (size_t)N_BLOCKS * block_bytes<P>());
+    build_blocks_g<P, NTH, LAYERS>(lds, biasT, w, (int)din, N_BLOCKS);
+    __syncthreads();
+    const int lane = threadIdx.x & (kWave - 1), p = lane & 31, h = lane >> 5;
+    const uint32_t wave = blockIdx.x * kWavesPerWG + threadIdx.x / kWave, n_waves = gridDim.x * kWavesPerWG;
+    const uint32_t n_tiles = (n + 31) / 32;
+    // (the laundered lane offsets: see k_mlp_bwd_g)
+    int lt = lane, ht = h;
+    auto blk = [&](int b) { return P::load_block(lds + (size_t)b * block_bytes<P>(), lt); };
+    auto blk_fresh = [&](int b) {
+        int l = lane;
+        asm volatile("" : "+v"(l));
+        return P::load_block(lds + (size_t)b * block_bytes<P>(), l);
+    };
+    auto bias = [&](int tile) { return bias_tile(biasT, tile, ht); };
+    auto transpose = [&](const KB &a, int id_block) {
+        f32x16 t = splat(0.f);
+        P::mma(t, a, blk_fresh(id_block));
+        return P::cast(t);
+    };
+
+    [[maybe_unused]] f32x16 gW1[NTH], gW2[NTH][NTH], gW3[NTH];
+    if constexpr (WG) {
+#pragma unroll
+        for (int a = 0; a < NTH; ++a) {
+            gW1[a] = splat(0.f); gW3[a] = splat(0.f);
+#pragma unroll
+            for (int b = 0; b < NTH; ++b) gW2[a][b] = splat(0.f);
+        }
+    }
+
+    float raw[16], rawr[16];
+    [[maybe_unused]] f32x4 dor;
+    {
+        const size_t r0 = (size_t)wave * 32 + p;
+        load_rows_raw_g(x, r0, n, h, 0, din, raw);
+        load_rows_raw_g(r, r0, n, h, 0, din, rawr);
+        if constexpr (WG) dor = load_dout_raw(dout, r0, n);
+    }
+    for (uint32_t tile = wave; tile < n_tiles; tile += n_waves) {
+        const size_t row = (size_t)tile * 32 + p;
+        const bool valid = row < n;
+        asm volatile("" : "+v"(lt), "+v"(ht));
+        const KB X = rows_kb<P>(raw);
+        KB R;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) R.v[q] = valid ? rawr[q] : 0.f;
+        [[maybe_unused]] KB dO;
+        if constexpr (WG) dO = dout_kb<P>(dor, valid && h == 0);
+        if (tile + n_waves < n_tiles) {   // the next tile's rows, in flight under this tile's products
+            const size_t rn = ((size_t)tile + n_waves) * 32 + p;
+            load_rows_raw_g(x, rn, n, h, 0, din, raw);
+            load_rows_raw_g(r, rn, n, h, 0, din, rawr);
+            if constexpr (WG) dor = load_dout_raw(dout, rn, n);
+        }
+        // ---- forward recompute (k_mlp_bwd_g's sequence) and, beside it, the tangent chain through the same masks
+        KB H1[NTH], U1[NTH], HL[NTH], UL[NTH];
+#pragma unroll
+        for (int t = 0; t < NTH; ++t) {
+            f32x16 acc = bias(t);
+            P::mma(acc, blk(B::W1 + t), X);
+            H1[t] = P::relu(acc);
+            f32x16 u = splat(0.f);
+            P::mma(u, blk(B::W1 + t), R);
+            U1[t] = P::masked(u, H1[t]);
+        }
+        [[maybe_unused]] KB Rp;   // lane = input feature, values = samples
+        if constexpr (WG) Rp = transpose(R, B::IDX);
+        if constexpr (LAYERS == 3) {
+#pragma unroll
+            for (int t = 0; t < NTH; ++t) {
+                f32x16 acc = bias(NTH + t);
+#pragma unroll
+                for (int tk = 0; tk < NTH; ++tk) P::mma(acc, blk(B::W2 + t * NTH + tk), H1[tk]);
+                HL[t] = P::relu(acc);
+                f32x16 u = splat(0.f);
+#pragma unroll
+                for (int tk = 0; tk < NTH; ++tk) P::mma(u, blk(B::W2 + t * NTH + tk), U1[tk]);
+                UL[t] = P::masked(u, HL[t]);
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < NTH; ++t) { HL[t] = H1[t]; UL[t] = U1[t]; }
+        }
+        if constexpr (ROWS) {   // grad_dout = u3 = W_last u_last: register q < 4 of lane-half 0 = output q of the lane's row
+            f32x16 acc = splat(0.f);
+#pragma unroll
+            for (int tk = 0; tk < NTH; ++tk) P::mma(acc, blk(B::W3 + tk), UL[tk]);
+            if (valid && h == 0) {
+                f32x4 o = {acc[0], acc[1], acc[2], acc[3]};
+                __builtin_nontemporal_store(o, reinterpret_cast<f32x4 *>(grad_dout + row * DOUT));
+            }
+        }
+        if constexpr (WG) {
+            {   // grad_W_last[o][f] += sum_s dy[s][o] u_last[s][f]
+                f32x16 tO = splat(0.f);
+                P::mma_lo(tO, dO, blk_fresh(B::IDX));
+                const KB dOp = P::cast(tO);   // lane = output index, values = samples
+#pragma unroll
+                for (int t = 0; t < NTH; ++t) P::mma(gW3[t], dOp, transpose(UL[t], B::IDD));
+            }
+            // ---- the first-order chain, as k_mlp_bwd_g runs it
+            KB dHL[NTH];
+#pragma unroll
+            for (int t = 0; t < NTH; ++t) {
+                f32x16 acc = splat(0.f);
+                P::mma_lo(acc, blk(B::W3T + t), dO);
+                dHL[t] = P::masked(acc, HL[t]);
+            }
+            KB dH1p[NTH];   // lane = hidden-1 feature, values = samples
+            if constexpr (LAYERS == 3) {
+                {   // grad_W2[i][j] += sum_s d2[s][i] u1[s][j]
+                    KB U1p[NTH];
+#pragma unroll
+                    for (int t = 0; t < NTH; ++t) U1p[t] = transpose(U1[t], B::IDD);
+#pragma unroll
+                    for (int ti = 0; ti < NTH; ++ti) {
+                        const KB dHLp = transpose(dHL[ti], B::IDD);
+#pragma unroll
+                        for (int tj = 0; tj < NTH; ++tj) P::mma(gW2[ti][tj], dHLp, U1p[tj]);
+                    }
+                }
+#pragma unroll
+                for (int t = 0; t < NTH; ++t) {   // d1 formed in orientation 2, where its mask (the transposed activations) is
+                    f32x16 acc = splat(0.f);
+#pragma unroll
+                    for (int tk = 0; tk < NTH; ++tk) P::mma(acc, dHL[tk], blk(B::W2T + t * NTH + tk));
+                    dH1p[t] = P::masked(acc, transpose(H1[t], B::IDD));
+                }
+            } else {
+#pragma unroll
+                for (int t = 0; t < NTH; ++t) dH1p[t] = transpose(dHL[t], B::IDD);
+            }
+#pragma unroll
+            for (int t = 0; t < NTH; ++t) P::mma(gW1[t], dH1p[t], Rp);   // grad_W1[i][j] += sum_s d1[s][i] r[s][j]
+        }
+    }
+
+    if constexpr (WG) {
+        // ---- reduce across the workgroup in LDS, then one atomic per element per workgroup (as k_mlp_bwd_g, no biases)
+        __syncthreads();
+        float *red = reinterpret_cast<float *>(lds);
+        const int OFF_W1 = 0, OFF_W2 = OFF_W1 + H * (int)din, OFF_W3 = OFF_W2 + (LAYERS == 3 ? H * H : 0),
+                  TOTAL = OFF_W3 + DOUT * H;
+        for (int e = threadIdx.x; e < TOTAL; e += blockDim.x) red[e] = 0.f;
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int rr = rowmap(q, h);
+#pragma unroll
+            for (int ti = 0; ti < NTH; ++ti) {
+                if (p < (int)din) atomicAdd(&red[OFF_W1 + (32 * ti + rr) * (int)din + p], gW1[ti][q]);
+                if constexpr (LAYERS == 3) {
+#pragma unroll
+                    for (int tj = 0; tj < NTH; ++tj) atomicAdd(&red[OFF_W2 + (32 * ti + rr) * H + 32 * tj + p], gW2[ti][tj][q]);
+                }
+                if (rr < DOUT) atomicAdd(&red[OFF_W3 + rr * H + 32 * ti + p], gW3[ti][q]);
+            }
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < TOTAL; e += blockDim.x) {
+            const float v = red[e];
+            float *dst = e < OFF_W2 ? gW1o + (e - OFF_W1) : e < OFF_W3 ? gW2o + (e - OFF_W2) : gW3o + (e - OFF_W3);
+            if (v != 0.f) unsafeAtomicAdd(dst, v);
+        }
+    }
+}
+
 // ---------------------------------------------------------------- field head (elementwise, one thread per sample)
 // sigma, albedo and the two finite-difference normals from the MLP output of the P = 7 or 13 stencil points
 // (network_tcnn.py:94-138, activation.py:5-18, nerf/utils.py:47-48) in one pass instead of ~40 elementwise launches
@@ -912,6 +1109,8 @@ int grid_for(uint32_t n, int wgs_per_cu) {
     return (int)(wgs < cap ? (wgs ? wgs : 1) : cap);
 }
 
+constexpr int kBwd2WgsPerCU = 2;   // k_mlp_bwd2_g: persistent beyond 512 workgroups (65 536 rows), as the first-order backward
+
 // network_tcnn.py:13-32: dim_in = 2 x levels (even, <= 32), hidden 32 or 64, 4 outputs, 2 or 3 layers
 bool dims_ok(uint32_t di, uint32_t dh, uint32_t dout, uint32_t layers) {
     return di >= 2 && di <= (uint32_t)DIN && di % 2 == 0 && (dh == 32 || dh == 64) && dout == DOUT &&
@@ -936,6 +1135,19 @@ void launch_bwd(dim3 grid, hipStream_t st, const float *x, uint32_t x_planes, co
     else
         hipLaunchKernelGGL((k_mlp_bwd_g<P, NTH, LAYERS, HP, false>), grid, dim3(kWave * kWavesPerWG),
                            lds_bytes_g<P>(B::ALL_COUNT, B::BIAS_TILES, true), st, x, x_planes, dout, n, din, w, dx, dx_planes, g);
+}
+template <class, int NTH, int LAYERS, bool>
+void launch_bwd2(dim3 grid, hipStream_t st, const float *x, const float *dout, const float *r, uint32_t n, uint32_t din,
+                 const Weights &w, float *grad_dout, float *gW1, float *gW2, float *gW3) {
+    using B = Blk<NTH, LAYERS>;
+    const dim3 block(kWave * kWavesPerWG);
+    const size_t lds_all = lds_bytes_g<F32>(B::ALL_COUNT, B::BIAS_TILES), lds_fwd = lds_bytes_g<F32>(B::FWD_COUNT, B::BIAS_TILES);
+    if (grad_dout && gW1)
+        hipLaunchKernelGGL((k_mlp_bwd2_g<NTH, LAYERS, true, true>), grid, block, lds_all, st, x, dout, r, n, din, w, grad_dout, gW1, gW2, gW3);
+    else if (gW1)
+        hipLaunchKernelGGL((k_mlp_bwd2_g<NTH, LAYERS, false, true>), grid, block, lds_all, st, x, dout, r, n, din, w, grad_dout, gW1, gW2, gW3);
+    else
+        hipLaunchKernelGGL((k_mlp_bwd2_g<NTH, LAYERS, true, false>), grid, block, lds_fwd, st, x, dout, r, n, din, w, grad_dout, gW1, gW2, gW3);
 }
 // runtime (hidden width, layer count) -> the template instance
 #define MI3D_MLP_DISPATCH(FN, P, HP, nth, layers, ...)                     \
@@ -1011,6 +1223,27 @@ int mi3d_mlp_backward(const void *xv, uint32_t x_plane_rows, int planes_half, co
         MI3D_MLP_DISPATCH(launch_bwd, F16, false, nth, layers, grid, st, x, x_plane_rows, dout, n, dim_in, w, dx, dx_plane_rows, g);
     else
         MI3D_MLP_DISPATCH(launch_bwd, F32, false, nth, layers, grid, st, x, x_plane_rows, dout, n, dim_in, w, dx, dx_plane_rows, g);
+    return (int)hipGetLastError();
+}
+
+int mi3d_mlp_backward_backward(const float *x, const float *dout, const float *r, uint32_t n, const float *W1, const float *b1,
+                               const float *W2, const float *b2, const float *W3, const float *b3, uint32_t dim_in,
+                               uint32_t dim_hidden, uint32_t dim_out, float *grad_dout, float *gW1, float *gW2, float *gW3,
+                               void *stream) {
+    const uint32_t layers = (W2 == nullptr && b2 == nullptr) ? 2u : 3u;
+    if (!dims_ok(dim_in, dim_hidden, dim_out, layers) || x == nullptr || dout == nullptr || r == nullptr || W1 == nullptr ||
+        b1 == nullptr || W3 == nullptr || b3 == nullptr || (layers == 3 && (W2 == nullptr || b2 == nullptr)))
+        return (int)hipErrorInvalidValue;
+    // the weight gradients come together or not at all (gW2 belongs to three layers only)
+    const bool any_w = gW1 != nullptr || gW3 != nullptr || (layers == 3 && gW2 != nullptr);
+    const bool all_w = gW1 != nullptr && gW3 != nullptr && (layers == 2 || gW2 != nullptr);
+    if ((any_w && !all_w) || (!any_w && grad_dout == nullptr)) return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    const Weights w{W1, b1, W2, b2, W3, b3};
+    const int nth = (int)dim_hidden / 32;
+    const dim3 grid(grid_for(n, kBwd2WgsPerCU));
+    MI3D_MLP_DISPATCH(launch_bwd2, F32, false, nth, layers, grid, as_stream(stream), x, dout, r, n, dim_in, w, grad_dout,
+                      all_w ? gW1 : nullptr, gW2, gW3);
     return (int)hipGetLastError();
 }
 

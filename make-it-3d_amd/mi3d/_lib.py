@@ -65,6 +65,7 @@ _SIGNATURES = {
     "mi3d_mlp_forward": [vp, u32, i32, u32, vp, vp, vp, vp, vp, vp, u32, u32, u32, i32, vp, vp],
     "mi3d_mlp_forward_counted": [vp, u32, i32, u32, vp, u32, vp, vp, vp, vp, vp, vp, u32, u32, u32, i32, vp, vp],
     "mi3d_mlp_backward": [vp, u32, i32, vp, u32, vp, vp, vp, vp, vp, vp, u32, u32, u32, i32, vp, u32, vp, vp, vp, vp, vp, vp, vp],
+    "mi3d_mlp_backward_backward": [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp],
     # Part 5 ------------------------------------------------------------------------------------------
     "mi3d_field_head_forward": [vp, vp, vp, u32, vp, u32, f32, f32, f32, f32, vp, vp, vp, vp, vp],
     "mi3d_field_head_forward_counted": [vp, vp, vp, u32, vp, vp, u32, f32, f32, f32, f32, vp, vp, vp, vp, vp],

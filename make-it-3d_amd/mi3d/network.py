@@ -155,18 +155,26 @@ class NeRFNetwork(NeRFRenderer):
     def normal(self, x):
         return torch.nan_to_num(safe_normalize(self.finite_difference_normal(x)))
 
-    def density_gradient(self, x):
+    def density_gradient(self, x, create_graph=False):
         """sigma [n] and its analytic gradient d sigma / dx [n, 3] in world units at x in [-bound, bound]^3: ONE forward and
         ONE backward per point through common_forward's chain - the hash grid's input gradient (include/mi3d.h Part 3), the
         MLP's, the blob term and trunc_exp's clamped derivative - where the finite-difference stencil takes seven
-        forwards and blurs over epsilon.  First order only: the grid has a second-order pass, the fused MLP
-        between it and the density has none yet.  fp32 whatever autocast says, in chunks of
-        mesh.CHUNK, and usable under torch.no_grad(); the table and the MLP weights enter detached: no scatter runs and no
-        parameter's `.grad` is created or touched."""
+        forwards and blurs over epsilon.  fp32 whatever autocast says, in chunks of mesh.CHUNK.
+
+        create_graph=False: usable under torch.no_grad(); the table and the MLP weights enter detached: no scatter runs and
+        no parameter's `.grad` is created or touched.
+
+        create_graph=True: sigma and d sigma / dx come back attached to `encoder.params` and to the MLP's weights, so a loss
+        on them trains the field: the chain runs through the grid's and the fused MLP's second-order passes (DESIGN.md 14,
+        15).  It needs grad mode.  The positions still enter detached: an x that requires grad is not differentiated
+        through.  The MLP's biases get a gradient through sigma only: d sigma / dx depends on them through the ReLU masks
+        alone, which are piecewise constant."""
         from . import mesh
         x = x.reshape(-1, 3).float()
         if not (self.sigma_net.fused_ok(x) and self.encoder.cfg["n_levels"] * 2 == self.sigma_net.dim_in):
             raise grid_ops.L.Mi3dError("density_gradient needs the model on the GPU and an MLP the matrix-core kernels cover")
+        if create_graph:
+            return self._density_gradient_attached(x, mesh.CHUNK)
         n = x.shape[0]
         sigma = torch.empty(n, dtype=torch.float32, device=x.device)
         grad = torch.empty(n, 3, dtype=torch.float32, device=x.device)
@@ -183,10 +191,30 @@ class NeRFNetwork(NeRFRenderer):
                 grad[s:s + mesh.CHUNK] = g
         return sigma, grad
 
-    def analytic_normal(self, x):
+    def _density_gradient_attached(self, x, chunk):
+        if not torch.is_grad_enabled():
+            raise grid_ops.L.Mi3dError("density_gradient(create_graph=True) builds a graph: call it with grad mode on")
+        sigmas, grads = [], []
+        with torch.autocast("cuda", enabled=False):
+            for s in range(0, x.shape[0], chunk):
+                xc = x[s:s + chunk].detach().requires_grad_()
+                feat = grid_ops.encode_points(self.encoder.params, xc, self._CENTER, self.encoder.cfg, float(self.bound),
+                                              second_order=True)
+                h = mlp_ops.fused_mlp(feat, self.sigma_net.net, half_mode=False, second_order=True)
+                sig = trunc_exp(h[..., 0] + self.gaussian(xc))
+                (g,) = torch.autograd.grad(sig.sum(), xc, create_graph=True)
+                sigmas.append(sig)
+                grads.append(g)
+        if not sigmas:   # no points: empty results, attached like any other (a loss on them gives zero gradients, not None)
+            zero = sum(p.sum() for p in (self.encoder.params, *(l.weight for l in self.sigma_net.net))) * 0
+            return x.new_zeros(0) + zero, x.new_zeros(0, 3) + zero
+        return torch.cat(sigmas), torch.cat(grads)
+
+    def analytic_normal(self, x, create_graph=False):
         """The smooth normal of the density isosurface through x, -grad sigma / |grad sigma| [n, 3], from density_gradient;
-        the sign and the clean-up (safe_normalize, nan_to_num) are normal()'s."""
-        return torch.nan_to_num(safe_normalize(-self.density_gradient(x)[1]))
+        the sign and the clean-up (safe_normalize, nan_to_num) are normal()'s.  create_graph=True: attached to the table and
+        the MLP's weights, as density_gradient's outputs are."""
+        return torch.nan_to_num(safe_normalize(-self.density_gradient(x, create_graph)[1]))
 
     def field_stencil(self, x, x2=None, step=0.0):
         x = x.reshape(-1, 3).float()
