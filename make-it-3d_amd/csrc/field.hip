@@ -981,6 +981,8 @@ __device__ __forceinline__ float head_gauss(const HeadArgs &a, const float *base
     return a.blob_density * expf(-d2 / a.two_r2);  // divide like torch does (network_tcnn.py:98)
 }
 
+__device__ __forceinline__ bool head_is_nan(float f) { return (__float_as_uint(f) & 0x7fffffffu) > 0x7f800000u; }
+
 // v / sqrt(clamp(|v|^2, 1e-20, 1e32)), NaN -> 0, +-inf -> +-FLT_MAX  (safe_normalize, then torch.nan_to_num)
 __device__ __forceinline__ void head_normal(const float s[6], float inv_2eps, float n[3], float v[3], float &c) {
     v[0] = -((s[0] - s[1]) * inv_2eps); v[1] = -((s[2] - s[3]) * inv_2eps); v[2] = -((s[4] - s[5]) * inv_2eps);
@@ -990,7 +992,10 @@ __device__ __forceinline__ void head_normal(const float s[6], float inv_2eps, fl
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         float t = v[d] * r;
-        if (t != t) t = 0.f;
+        // torch.clamp hands a NaN |v|^2 on (inf - inf on one axis: both neighbours overflowed) where fminf / fmaxf drop it
+        // for 1e-20: every component is NaN -> 0 then, not that axis alone.  (The test reads the bits: written as ss != ss
+        // it moved the compiler to contract the blob's sum of squares differently, and finite rows changed.)
+        if (t != t || head_is_nan(ss)) t = 0.f;
         else if (t > 3.4028234663852886e38f) t = 3.4028234663852886e38f;
         else if (t < -3.4028234663852886e38f) t = -3.4028234663852886e38f;
         n[d] = t;
@@ -1042,7 +1047,7 @@ __device__ __forceinline__ void head_normal_backward(const float u[6], float inv
     const float k = inside ? dot * (r / c) : 0.f;      // d(1/sqrt(c))/d(ss) * 2 v = -c^-1.5 v
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
-        const float dv = r * dn[d] - k * v[d];
+        const float dv = head_is_nan(ss) ? ss : r * dn[d] - k * v[d];  // (NaN |v|^2: 0 / NaN on every axis in torch's graph)
         const float dg = -dv * inv_2eps;  // v = -(s+ - s-) * inv_2eps
         du[2 * d] = dg * expf(fminf(u[2 * d], 15.0f));
         du[2 * d + 1] = -dg * expf(fminf(u[2 * d + 1], 15.0f));
