@@ -697,6 +697,72 @@ int mi3d_canny_classify(const uint8_t *image, uint32_t H, uint32_t W, int32_t lo
                         unsigned long long *counts, void *stream);
 int mi3d_canny_hysteresis(uint8_t *cls, uint32_t H, uint32_t W, uint32_t sweeps, int32_t *changed, void *stream);
 
+/* ------------------------------------------------------------------ Part 13: mesh components (mesh export) */
+
+/* The connected components of an indexed triangle mesh (Part 8's output, or any other) and a filter that drops the small
+ * ones - the islands a density field leaves above the threshold - with the bit-exact, order-preserving standing of
+ * Part 8.  What the `clean_mesh` step (min_f / min_d, through pymeshlab) of projects of this family does on the CPU;
+ * pymeshlab is on no machine this project builds on, so the semantics below are this project's own contract - PARITY
+ * UNPINNED.  Added under ABI version 5: new symbols only.  (Declared ahead of the point-cloud part, like Part 12.)
+ *
+ * vertices float[nv][3], triangles int32[nt][3]; nv, nt <= 2^31 - 1.
+ *   - CONNECTIVITY: two vertices are connected iff some triangle cites both; components are the transitive closure.  By
+ *     shared vertex INDEX - not by position, not by shared edge: two surfaces that touch in one welded vertex are one
+ *     component.  Duplicate and degenerate (a == b) triangles are legal: they count as faces and connect what they cite.
+ *   - BAD INDICES: a triangle with an index outside [0, nv) connects nothing, is no face, is never emitted and never
+ *     dereferenced; it is COUNTED in counts[2] - the convention counts[2] of Part 8 and `bad` of Part 9 set.
+ *   - LABELS: label[v] (int32[nv]) = the smallest vertex index of v's component.  A vertex no triangle cites is its own
+ *     component with zero faces.  The label does not depend on scheduling: two runs give byte-identical buffers.
+ *   - PER COMPONENT, at the row of its label vertex L (label[L] == L); the rows of all other vertices hold 0:
+ *       faces[L]   (uint32[nv]) the number of valid triangles whose FIRST index lies in the component;
+ *       box_min[L], box_max[L] (float[nv][3]) per axis the smallest and largest coordinate of the component's vertices in
+ *                  the order of the order-preserving integer image of binary32 (-0 below +0, infinities at the ends).  A
+ *                  NaN coordinate is ignored; an axis on which the component has no other coordinate gets [0, 0].
+ *   - DIAGONAL: d_c = box_max[c] - box_min[c] in binary32, a NaN d_c (both ends the same infinity) taken as 0;
+ *     diag2 = dx*dx + dy*dy + dz*dz in binary32, each operation rounded once, left to right, no fused multiply-add.  A
+ *     component without a finite coordinate has diag2 = 0; one that reaches an infinity from elsewhere has diag2 = +inf.
+ *   - KEEP RULE (min_faces >= 0, min_diagonal >= 0 and not NaN, largest): a component is kept iff faces >= 1 and
+ *     faces >= min_faces and diag2 >= min_diagonal * min_diagonal (that product one binary32 multiply).  Equality
+ *     keeps.  With `largest` it must ALSO be the component with the most faces, ties going to the smaller label: if the
+ *     thresholds exclude that one, nothing is kept.
+ *   - OUTPUT: the kept vertices and the kept triangles in their ORIGINAL RELATIVE ORDER (stable compaction: per-workgroup
+ *     counts, an exclusive scan, an emit - no atomic appends), vertex rows copied bit for bit, triangle indices renumbered;
+ *     vertex_map int32[nv] = the new index of every old vertex, -1 for a dropped one.
+ *   - counts (device uint64[8], 8-byte aligned): [0] kept vertices, [1] kept triangles, [2] bad triangles, [3] threads
+ *     that GAVE UP, [4] (faces << 32) | ~label of the largest component (0: no component has a face), [5] components
+ *     with at least one face, [6] elements mi3d_mesh_clean_emit could not place, [7] 0.
+ *   - GIVING UP: the labelling is a lock-free union-find whose parents only ever decrease (parent[v] <= v), so every
+ *     loop walks a strictly decreasing chain and no correct execution takes more than nv + 1 steps per chain.  No wave
+ *     waits for another.  A thread that exceeds the bound adds to counts[3] and leaves: a non-zero counts[3] means the
+ *     result is invalid - an error for the caller to raise, never a hang.
+ *
+ *   mi3d_mesh_components_workspace  host only: bytes of device scratch mi3d_mesh_clean_count / _emit need for a mesh of
+ *                          this size (0 for nv = nt = 0 and for sizes out of range).  mi3d_mesh_components needs none:
+ *                          it works inside its outputs.
+ *   mi3d_mesh_components   label, faces, box_min, box_max as above; counts zeroed in-stream, then [2] .. [5] filled.
+ *   mi3d_mesh_clean_count  the keep rule, per-workgroup counts and their scan -> ws; counts[0], counts[1] (and [6] = 0).
+ *                          label .. counts as mi3d_mesh_components left them.  The caller reads counts ONCE here to size
+ *                          the outputs and to see [2] and [3] - the only host read of a clean.
+ *   mi3d_mesh_clean_emit   out_vertices float[nv_cap][3], out_triangles int32[nt_cap][3], vertex_map int32[nv].  Nothing
+ *                          is written past the caps; what could not be placed is counted in counts[6].
+ * components, count and emit of one clean go to the same stream, in this order, with the same mesh and ws.  No entry
+ * point allocates or synchronises.  nv = nt = 0 launches nothing and succeeds (counts is not touched); nt = 0 or nv = 0
+ * alone is served (every vertex its own faceless component; every triangle bad).  Sizes out of range, a negative or NaN
+ * min_diagonal, a workspace that is too small or not 8-byte aligned and every NULL pointer that would be dereferenced
+ * are refused (hipErrorInvalidValue) and launch nothing. */
+size_t mi3d_mesh_components_workspace(unsigned long long nv, unsigned long long nt);
+int mi3d_mesh_components(const float *vertices, unsigned long long nv, const int32_t *triangles, unsigned long long nt,
+                         int32_t *label, uint32_t *faces, float *box_min, float *box_max, unsigned long long *counts,
+                         void *stream);
+int mi3d_mesh_clean_count(const int32_t *triangles, unsigned long long nv, unsigned long long nt, const int32_t *label,
+                          const uint32_t *faces, const float *box_min, const float *box_max, uint32_t min_faces,
+                          float min_diagonal, int largest, void *ws, size_t ws_bytes, unsigned long long *counts,
+                          void *stream);
+int mi3d_mesh_clean_emit(const float *vertices, unsigned long long nv, const int32_t *triangles, unsigned long long nt,
+                         const int32_t *label, void *ws, size_t ws_bytes, unsigned long long *counts, float *out_vertices,
+                         unsigned long long nv_cap, int32_t *out_triangles, unsigned long long nt_cap, int32_t *vertex_map,
+                         void *stream);
+
 /* ------------------------------------------------------------------ Part 11: the refine stage's point cloud */
 
 /* Depth / mask / rgb views -> the coloured point cloud the refine stage starts from: what `depth2point`,

@@ -22,6 +22,7 @@ UNITS = [
     ("optim.hip", ["-ffp-contract=off"]),
     ("raster.hip", ["-ffp-contract=off"]),
     ("mesh.hip", ["-ffp-contract=off"]),
+    ("meshclean.hip", ["-ffp-contract=off"]),
     ("texture.hip", ["-ffp-contract=off"]),
     ("groupnorm.hip", []),
     ("pointcloud.hip", ["-ffp-contract=off"]),

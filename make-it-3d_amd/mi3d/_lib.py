@@ -104,6 +104,10 @@ _SIGNATURES = {
     # Part 12 -----------------------------------------------------------------------------------------
     "mi3d_canny_classify": [vp, u32, u32, i32, i32, vp, vp, vp],
     "mi3d_canny_hysteresis": [vp, u32, u32, u32, vp, vp],
+    # Part 13 -----------------------------------------------------------------------------------------
+    "mi3d_mesh_components": [vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, vp, vp],
+    "mi3d_mesh_clean_count": [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, u32, f32, i32, vp, C.c_size_t, vp, vp],
+    "mi3d_mesh_clean_emit": [vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_size_t, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp],
 }
 
 # host-only queries whose return value is not a hipError_t: (argtypes, restype), bound in lib() like the block below
@@ -113,6 +117,7 @@ _LATE_SIGNATURES = {
     "mi3d_atlas_cell": ([C.c_uint64, u32], u32),
     "mi3d_groupnorm_chunks": ([u32], u32),
     "mi3d_pc_unproject_workspace": ([u32, u32], C.c_size_t),
+    "mi3d_mesh_components_workspace": ([C.c_uint64, C.c_uint64], C.c_size_t),
 }
 
 

@@ -6,6 +6,10 @@
   marching_cubes   the kernels of csrc/mesh.hip (include/mi3d.h Part 8 states the conventions): device volume in,
                    welded indexed mesh out; the host reads the two counts once to size the outputs (and
                    the overflow counter once after emit)
+  components       the kernels of csrc/meshclean.hip (include/mi3d.h Part 13): the connected components of an indexed
+                   mesh - label, face count and bounding box of each - by a lock-free union-find on the device
+  clean            drops the components below `min_faces` / `min_diagonal` (or all but the largest): stable compaction
+                   on the device; the host reads the counts once to size the outputs
   bake_texture     the kernels of csrc/texture.hip (include/mi3d.h Part 9): a texel patch per triangle, the field's albedo
                    at every texel's surface point, packed to 8-bit RGB on the device
   export           volume -> surface -> per-vertex albedo (-> texture) -> files; what `NeRFRenderer.export_mesh` calls
@@ -64,6 +68,106 @@ def marching_cubes(volume, iso, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0))
     if lost != 0:
         raise Mi3dError(f"marching cubes could not place {lost} elements (the volume changed between count and emit?)")
     return vertices, triangles
+
+
+MAX_COUNT = 2 ** 31 - 1
+
+
+def _check_mesh(vertices, triangles):
+    vertices = _lib.dev_f32(vertices, "vertices", 3)
+    if not isinstance(triangles, torch.Tensor):
+        raise TypeError("triangles must be a torch.Tensor")
+    triangles = _lib.dev_typed(triangles, "triangles", torch.int32)
+    if vertices.dim() != 2 or triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.device != vertices.device:
+        raise Mi3dError(f"vertices {tuple(vertices.shape)} and triangles {tuple(triangles.shape)} must be [nv, 3] and "
+                        f"[nt, 3] on one device")
+    if vertices.shape[0] > MAX_COUNT or triangles.shape[0] > MAX_COUNT:
+        raise Mi3dError(f"{vertices.shape[0]} vertices / {triangles.shape[0]} triangles do not fit int32 indices")
+    return vertices, triangles
+
+
+def _check_keep_rule(min_faces, min_diagonal, largest):
+    if isinstance(min_faces, bool) or not isinstance(min_faces, (int, np.integer)):
+        raise Mi3dError(f"min_faces must be an integer (got {min_faces!r})")
+    if not 0 <= int(min_faces) < 2 ** 32:
+        raise Mi3dError(f"min_faces must lie in [0, 2^32) (got {min_faces})")
+    if isinstance(min_diagonal, bool) or not isinstance(min_diagonal, (int, float, np.integer, np.floating)):
+        raise Mi3dError(f"min_diagonal must be a number (got {min_diagonal!r})")
+    if not float(min_diagonal) >= 0.0:
+        raise Mi3dError(f"min_diagonal must be >= 0 and not NaN (got {min_diagonal})")
+    if not isinstance(largest, (bool, np.bool_)):
+        raise Mi3dError(f"largest must be a bool (got {largest!r})")
+    return int(min_faces), float(min_diagonal), bool(largest)
+
+
+def _label_components(vertices, triangles):
+    """mi3d_mesh_components on the current stream: (label, faces, box_min, box_max, counts), nothing read back."""
+    nv, nt, dev = int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
+    label = torch.empty(nv, dtype=torch.int32, device=dev)
+    faces = torch.empty(nv, dtype=torch.int32, device=dev)
+    box_min = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    box_max = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    counts = torch.zeros(8, dtype=torch.int64, device=dev)
+    _lib.launch("mi3d_mesh_components", vertices, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, _lib.ptr(label),
+                _lib.ptr(faces), _lib.ptr(box_min), _lib.ptr(box_max), _lib.ptr(counts))
+    return label, faces, box_min, box_max, counts
+
+
+def _check_counts(counts, nv, nt):
+    """`counts` as a host list: refuses what include/mi3d.h Part 13 counts instead of dropping silently."""
+    if counts[2] != 0:
+        raise Mi3dError(f"{counts[2]} of the {nt} triangles hold a vertex index outside [0, {nv})")
+    if counts[3] != 0:
+        raise Mi3dError(f"mesh components: {counts[3]} threads gave up after more than {nv + 1} steps on a parent chain "
+                        f"(the labelling is invalid: a bug, or the buffers changed during the call)")
+
+
+def components(vertices, triangles):
+    """The connected components of an indexed mesh (include/mi3d.h Part 13): vertices float32 [nv, 3], triangles int32
+    [nt, 3] on the GPU.  Returns (label int32 [nv], faces int32 [nv], box_min float32 [nv, 3], box_max float32 [nv, 3]) on
+    the same device: label[v] is the smallest vertex index connected to v; faces and the box of a component stand in the
+    row of its label vertex, every other row holds 0.  A triangle index outside [0, nv) raises Mi3dError."""
+    vertices, triangles = _check_mesh(vertices, triangles)
+    nv, nt = int(vertices.shape[0]), int(triangles.shape[0])
+    label, faces, box_min, box_max, counts = _label_components(vertices, triangles)
+    if nv or nt:
+        _check_counts(counts.tolist(), nv, nt)
+    return label, faces, box_min, box_max
+
+
+def _clean(vertices, triangles, min_faces, min_diagonal, largest):
+    """clean() behind its argument checks; also returns the host copy of `counts`."""
+    nv, nt, dev = int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
+    vertex_map = torch.empty(nv, dtype=torch.int32, device=dev)
+    if nv == 0 and nt == 0:
+        return vertices.new_empty(0, 3), triangles.new_empty(0, 3), vertex_map, [0] * 8
+    label, faces, box_min, box_max, counts = _label_components(vertices, triangles)
+    ws_bytes = int(_lib.lib().mi3d_mesh_components_workspace(nv, nt))
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    _lib.launch("mi3d_mesh_clean_count", vertices, _lib.ptr(triangles), nv, nt, _lib.ptr(label), _lib.ptr(faces),
+                _lib.ptr(box_min), _lib.ptr(box_max), min_faces, min_diagonal, int(largest), _lib.ptr(ws), ws_bytes,
+                _lib.ptr(counts))
+    host = counts.tolist()                                   # the one host read a clean needs
+    _check_counts(host, nv, nt)
+    kv, kt = host[:2]
+    out_v = torch.empty(kv, 3, dtype=torch.float32, device=dev)
+    out_t = torch.empty(kt, 3, dtype=torch.int32, device=dev)
+    _lib.launch("mi3d_mesh_clean_emit", vertices, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, _lib.ptr(label),
+                _lib.ptr(ws), ws_bytes, _lib.ptr(counts), _lib.ptr(out_v), kv, _lib.ptr(out_t), kt, _lib.ptr(vertex_map))
+    return out_v, out_t, vertex_map, host
+
+
+def clean(vertices, triangles, min_faces=0, min_diagonal=0.0, largest=False):
+    """Drops the floaters of an indexed mesh by the keep rule of include/mi3d.h Part 13: a connected component stays iff it
+    has at least one face, at least `min_faces` faces and a bounding-box diagonal of at least `min_diagonal` (equality
+    keeps); with `largest=True` only the component with the most faces can stay (ties: the smaller label).  vertices
+    float32 [nv, 3], triangles int32 [nt, 3] on the GPU.  Returns (vertices, triangles, vertex_map int32 [nv]) on the same
+    device: what is kept, in its original relative order, the triangles renumbered; vertex_map is the new index of every
+    old vertex, -1 for a dropped one.  Nothing kept gives [0, 3] tensors.  A triangle index outside [0, nv) raises
+    Mi3dError."""
+    vertices, triangles = _check_mesh(vertices, triangles)
+    min_faces, min_diagonal, largest = _check_keep_rule(min_faces, min_diagonal, largest)
+    return _clean(vertices, triangles, min_faces, min_diagonal, largest)[:3]
 
 
 def _chunks(n):
@@ -279,9 +383,14 @@ def vertex_normals(model, vertices):
     return model.analytic_normal(vertices).float()
 
 
-def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False):
+def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False, min_faces=None,
+           min_diagonal=None, largest=False):
     """What NeRFRenderer.export_mesh does (see there).  `S` only sizes the reference's chunks and is ignored."""
     del S
+    cleaning = min_faces is not None or min_diagonal is not None or largest is not False
+    if cleaning:
+        rule = _check_keep_rule(0 if min_faces is None else min_faces, 0.0 if min_diagonal is None else min_diagonal,
+                                largest)
     if model.aabb_train.device.type != "cuda":
         raise Mi3dError(f"export_mesh needs the model on the GPU (it is on {model.aabb_train.device}): the field and "
                         f"the marching-cubes kernels have no CPU path")
@@ -298,6 +407,13 @@ def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, norma
             lo, hi = torch.nan_to_num(vol, nan=0.0).min().item(), torch.nan_to_num(vol, nan=0.0).max().item()
             raise Mi3dError(f"export_mesh: no surface at density threshold {thresh:g}: the {R}^3 volume spans "
                             f"[{lo:g}, {hi:g}]")
+        if cleaning:                                            # before the atlas, the colours and the normals
+            nv0, nt0 = vertices.shape[0], triangles.shape[0]
+            vertices, triangles, _, counts = _clean(vertices, triangles, *rule)
+            if vertices.shape[0] == 0 or triangles.shape[0] == 0:
+                raise Mi3dError(f"export_mesh: nothing survives min_faces={rule[0]}, min_diagonal={rule[1]:g}, "
+                                f"largest={rule[2]}: the surface has {counts[5]} components, the largest of "
+                                f"{counts[4] >> 32} triangles ({nv0} vertices, {nt0} triangles in all)")
         if texture_size is not None:
             _fitting_cell(triangles.shape[0], texture_size)     # refuse before the field is evaluated anywhere
         albedo = vertex_albedo(model, vertices)

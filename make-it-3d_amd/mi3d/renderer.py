@@ -117,7 +117,8 @@ class NeRFRenderer(nn.Module):
         self.local_step = 0
 
     @torch.no_grad()
-    def export_mesh(self, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False):
+    def export_mesh(self, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False, min_faces=None,
+                    min_diagonal=None, largest=False):
         """renderer.py:157-191 + the file writing of :300-328, reached through main.py's `--save_mesh`: sigma on the
         `resolution`^3 lattice of [-1, 1]^3 (default grid_size), marching cubes at min(mean_density, density_thresh)
         (density_thresh without cuda_ray) on the GPU (mi3d.mesh), `<path>/mesh.obj` + `mesh.mtl`.  By default
@@ -131,9 +132,16 @@ class NeRFRenderer(nn.Module):
         model raises Mi3dError.  With `normals=True` the field's analytic normal at every vertex (`analytic_normal`:
         -grad sigma / |grad sigma|, DESIGN.md 13) is written as `vn` lines, the faces become `f v//vn` (`f v/vt/vn` with a
         texture), and the returned tuple gains the [nv,3] float32 normals as its last element; with `normals=False` files
-        and return value are what they were without the argument."""
+        and return value are what they were without the argument.  `min_faces`, `min_diagonal` and `largest` drop the
+        floaters (mesh.clean, include/mi3d.h Part 13) right after marching cubes: a connected component
+        stays iff it has at least `min_faces` triangles and a bounding-box diagonal of at least `min_diagonal`, with
+        `largest=True` only the one with the most triangles; the atlas, the colours and the normals are those of the
+        cleaned mesh and the returned tuples keep their shapes.  Nothing surviving raises Mi3dError naming the component
+        count and the largest component.  With all three at their defaults nothing of this runs and the files are byte
+        for byte what they were without the arguments."""
         from . import mesh
-        return mesh.export(self, path, resolution, S, texture_size=texture_size, ssaa=ssaa, normals=normals)
+        return mesh.export(self, path, resolution, S, texture_size=texture_size, ssaa=ssaa, normals=normals,
+                           min_faces=min_faces, min_diagonal=min_diagonal, largest=largest)
 
     @torch.no_grad()
     def export_point_cloud(self, outputdir, poses, ref_rgb, fov, H, W, **kwargs):
