@@ -651,6 +651,34 @@ int mi3d_groupnorm_act_backward(const void *x, const void *dy, const float *mean
                                 const float *bias, const float *partial, uint32_t B, uint32_t C, uint32_t HW, uint32_t G,
                                 int act, void *dx, void *stream);
 
+/* The same four steps for CHANNELS-LAST tensors: x, y, dy, dx binary16 [B][HW][C] with C contiguous (what PyTorch calls
+ * torch.channels_last), so that the convolutions around a GroupNorm can run in NHWC without a transpose.  Added under
+ * ABI version 5: new symbols only.  The contract is that of the entry points above - binary16 in and out, fp32 in
+ * registers, one rounding, Chan's merge (a thread adds one element at a time to its 8 channels' sets; sets are then united
+ * by mean = sum n_i mean_i / n, M2 = sum M2_i + sum n_i (mean_i - mean)^2, or pairwise), ATen's dx formula, no atomics,
+ * fixed orders, nothing that cannot be captured - with these differences:
+ *   - C % 8 == 0 and lcm(C / G, 8) <= 2048; every tensor pointer 16-byte aligned: all access is by 16-byte vectors of 8
+ *     channels of one pixel.  Anything else is refused.
+ *   - SPANS: a sample's pixels are cut into Sc = mi3d_groupnorm_nhwc_spans(C, HW, G) spans of
+ *     P = mi3d_groupnorm_nhwc_span(C, HW, G) whole pixels (the last one shorter); both return 0 for a shape that is
+ *     refused.  One workgroup owns one (sample, span, slab of whole groups, at least 64 channels wide).  The workspaces
+ *     hold one entry per (sample, span, group), index (b * Sc + k) * G + g: ws float[B * Sc * G][3] = (count, mean, M2),
+ *     partial float[B * Sc * G][2] = (sum_c weight_c sum dz, sum_c weight_c sum dz (x - mean)) - weighted and centred,
+ *     unlike above: dx = rstd weight_c dz + c2 (x - mean) - db rstd / n with c2 = -(ds - db mean) rstd^3 / n is ATen's
+ *     dx = rstd weight_c dz + c2 x + c3 without its two large cancelling terms. */
+uint32_t mi3d_groupnorm_nhwc_span(uint32_t C, uint32_t HW, uint32_t G);
+uint32_t mi3d_groupnorm_nhwc_spans(uint32_t C, uint32_t HW, uint32_t G);
+int mi3d_groupnorm_nhwc_stats(const void *x, uint32_t B, uint32_t C, uint32_t HW, uint32_t G, float *ws, void *stream);
+int mi3d_groupnorm_nhwc_act_forward(const void *x, const float *ws, const float *weight, const float *bias, uint32_t B,
+                                    uint32_t C, uint32_t HW, uint32_t G, float eps, int act, void *y, float *mean,
+                                    float *rstd, void *stream);
+int mi3d_groupnorm_nhwc_act_backward_sums(const void *x, const void *dy, const float *mean, const float *rstd,
+                                          const float *weight, const float *bias, uint32_t B, uint32_t C, uint32_t HW,
+                                          uint32_t G, int act, float *partial, void *stream);
+int mi3d_groupnorm_nhwc_act_backward(const void *x, const void *dy, const float *mean, const float *rstd,
+                                     const float *weight, const float *bias, const float *partial, uint32_t B, uint32_t C,
+                                     uint32_t HW, uint32_t G, int act, void *dx, void *stream);
+
 /* ------------------------------------------------------------------ Part 12: the Canny depth-edge detector */
 
 /* The edge detector of the reference's load_views (nerf/refine_utils.py:386-393: `cv2.Canny(uint8 depth, 10, 10)`, dilated

@@ -22,6 +22,9 @@
 // 16-byte aligned base pointers the chunk's misalignment is (row * HW) mod 8 elements.  Up to 7 head elements and up to 7
 // tail elements go one by one, the rest as 16-byte vectors.  If any base pointer is not 16-byte aligned the whole chunk
 // goes element by element.
+//
+// The same four kernels for channels-last tensors ([B][HW][C], k_groupnorm_nhwc_*) follow the NCHW ones below, with
+// their own decomposition (spans of whole pixels x slabs of whole groups) described there.
 #include <hip/hip_runtime.h>
 
 #include "../../include/mi3d.h"
@@ -288,6 +291,404 @@ bool make_shape(uint32_t B, uint32_t C, uint32_t HW, uint32_t G, Shape &s, uint3
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// ------------------------------------------------------------------------------------------------ NHWC (channels-last)
+// x is [B][HW][C] with C contiguous and C % 8 == 0, so every 16-byte vector holds 8 channels of one pixel.  The channels
+// are cut into SLABS of whole groups, slabC = the smallest multiple of lcm(C/G, 8) that is >= 64 channels (128 bytes of a
+// pixel; the last slab may be shorter), and a sample's pixels into Sc spans of P whole pixels: one workgroup owns one
+// (sample, span, slab).  Its threads form a (pixel row, vector) tile - vt = slabC / 8 vectors wide, 256 / vt pixels high -
+// that walks down the span, so a thread keeps the same 8 channels throughout and carries their 8 partial results in
+// registers.  The partials are folded per channel over the tile's rows through LDS, then per group over the group's
+// channels (a vector of 8 may straddle two groups - 10 or 20 channels per group - which is why the fold is per channel
+// first), both with the k-set form of Chan's merge: mean = sum n_i mean_i / n, M2 = sum M2_i + sum n_i (mean_i - mean)^2.
+// The workspaces hold one entry per (sample, span, group); the second kernel of each direction merges its slab's groups
+// over the Sc spans, at most kNhwcMerge entries per workgroup.  Orders are fixed everywhere, there are no atomics.
+constexpr uint32_t kNhwcChunk = 8192;     // elements per workgroup aimed at, as kChunk
+constexpr uint32_t kNhwcMerge = 4096;     // entries (groups of the slab x spans) a workgroup of the second kernel merges
+constexpr uint32_t kNhwcRatio = 16;       // elements of a workgroup per workspace entry it merges, at least
+constexpr uint32_t kNhwcMaxSlab = 2048;   // channels per slab the LDS fold buffers hold (256 threads x 8 channels)
+
+struct NShape {
+    uint32_t C, HW, G, per, slabC, nslab, P, Sc, tpg;  // tpg: threads per group in the merge over spans, a power of two
+};
+
+struct NWork {
+    uint32_t b, span, c0, nc, g0, ng, len;  // the slab's first channel / channel count / first group / group count
+    size_t off;                             // element index of (sample, first pixel of the span, c0)
+    size_t entry0;                          // workspace entry of (sample, span 0, group 0)
+};
+
+__device__ __forceinline__ NWork nwork_of(const NShape &s) {
+    NWork w;
+    const uint32_t slab = blockIdx.x % s.nslab, rest = blockIdx.x / s.nslab;
+    w.b = rest / s.Sc;
+    w.span = rest - w.b * s.Sc;
+    w.c0 = slab * s.slabC;
+    w.nc = s.C - w.c0 < s.slabC ? s.C - w.c0 : s.slabC;
+    w.g0 = w.c0 / s.per;
+    w.ng = w.nc / s.per;
+    const uint32_t p0 = w.span * s.P;
+    w.len = s.HW - p0 < s.P ? s.HW - p0 : s.P;
+    w.off = ((size_t)w.b * s.HW + p0) * s.C + w.c0;
+    w.entry0 = (size_t)w.b * s.Sc * s.G;
+    return w;
+}
+
+// the thread's place in the (pixel row, vector) tile; rows r >= rows own nothing
+struct NTile {
+    uint32_t vt, rows, tc, r;
+    bool active;
+};
+
+__device__ __forceinline__ NTile ntile_of(const NWork &w) {
+    NTile t;
+    t.vt = w.nc >> 3;
+    t.rows = kBlock / t.vt;
+    t.r = threadIdx.x / t.vt;
+    t.tc = threadIdx.x - t.r * t.vt;
+    t.active = t.r < t.rows;
+    return t;
+}
+
+// pixels of a span of len that row r of a tile with `rows` rows visits: r, r + rows, ...
+__device__ __forceinline__ float row_count(uint32_t len, uint32_t r, uint32_t rows) {
+    return (float)(len / rows + (r < len % rows ? 1u : 0u));
+}
+
+// a_c, b_c and the group mean of the thread's 8 channels c .. c + 7 from the per-group mean / rstd (indexed by
+// group - g_base)
+__device__ __forceinline__ void chan_affine(const float (&wv)[8], const float (&bv)[8], const float *mean,
+                                            const float *rstd, uint32_t c, uint32_t per, uint32_t g_base, float (&a)[8],
+                                            float (&b)[8], float (&mu)[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint32_t g = (c + i) / per - g_base;
+        mu[i] = mean[g];
+        a[i] = rstd[g] * wv[i];
+        b[i] = bv[i] - mu[i] * a[i];
+    }
+}
+
+__device__ __forceinline__ void load8(const float *__restrict__ p, float (&v)[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = p[i];
+}
+
+constexpr uint32_t kNhwcPre = 2;  // pixels per thread whose loads the second kernels issue ahead of the merge over spans
+
+__global__ __launch_bounds__(kBlock) void k_groupnorm_nhwc_stats(const half_t *__restrict__ x, NShape s,
+                                                                 float *__restrict__ ws) {
+    __shared__ float rmean[kNhwcMaxSlab], rm2[kNhwcMaxSlab], cmean[kNhwcMaxSlab], cm2[kNhwcMaxSlab];
+    const NWork w = nwork_of(s);
+    const NTile t = ntile_of(w);
+    if (t.active) {
+        float mean[8], m2[8], cnt = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) mean[i] = m2[i] = 0.0f;
+        const half_t *px = x + w.off + (t.tc << 3);
+#pragma unroll 8
+        for (uint32_t p = t.r; p < w.len; p += t.rows) {
+            const half8 v = *reinterpret_cast<const half8 *>(px + (size_t)p * s.C);
+            cnt += 1.0f;
+            const float inv = 1.0f / cnt;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {  // Welford: one element joins the channel's set
+                const float f = (float)v[i], d = f - mean[i];
+                mean[i] += d * inv;
+                m2[i] = fmaf(d, f - mean[i], m2[i]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            rmean[t.r * w.nc + (t.tc << 3) + i] = mean[i];
+            rm2[t.r * w.nc + (t.tc << 3) + i] = m2[i];
+        }
+    }
+    __syncthreads();
+    const float n = (float)w.len;
+    for (uint32_t c = threadIdx.x; c < w.nc; c += kBlock) {  // the channel over the tile's rows
+        float sum = 0.0f;
+#pragma unroll 8
+        for (uint32_t r = 0; r < t.rows; ++r) sum = fmaf(row_count(w.len, r, t.rows), rmean[r * w.nc + c], sum);
+        const float mu = sum / n;
+        float q = 0.0f;
+#pragma unroll 8
+        for (uint32_t r = 0; r < t.rows; ++r) {
+            const float d = rmean[r * w.nc + c] - mu;
+            q += fmaf(row_count(w.len, r, t.rows) * d, d, rm2[r * w.nc + c]);
+        }
+        cmean[c] = mu;
+        cm2[c] = q;
+    }
+    __syncthreads();
+    for (uint32_t g = threadIdx.x; g < w.ng; g += kBlock) {  // the group over its channels, all of count n
+        float sum = 0.0f;
+#pragma unroll 8
+        for (uint32_t c = g * s.per; c < (g + 1) * s.per; ++c) sum += cmean[c];
+        const float mu = sum / (float)s.per;
+        float q = 0.0f;
+#pragma unroll 8
+        for (uint32_t c = g * s.per; c < (g + 1) * s.per; ++c) {
+            const float d = cmean[c] - mu;
+            q += fmaf(n * d, d, cm2[c]);
+        }
+        float *o = ws + 3 * (w.entry0 + (size_t)w.span * s.G + w.g0 + g);
+        o[0] = n * (float)s.per;
+        o[1] = mu;
+        o[2] = q;
+    }
+}
+
+// The workgroup's threads as (group of the slab, lane j of tpg): the entries of group w.g0 + gl over the spans
+// j, j + tpg, ...; four loads in flight per thread.  f(entry index) -> value, acc(value) folds it.
+template <class LOAD, class ACC>
+__device__ __forceinline__ void over_spans(const NShape &s, const NWork &w, uint32_t gl, uint32_t j, LOAD load, ACC acc) {
+    if (gl >= w.ng) return;
+    const size_t e0 = w.entry0 + w.g0 + gl;
+    for (uint32_t k0 = j; k0 < s.Sc; k0 += 4 * s.tpg) {
+        decltype(load((size_t)0, true)) v[4];
+#pragma unroll
+        for (uint32_t u = 0; u < 4; ++u) {
+            const uint32_t k = k0 + u * s.tpg;
+            v[u] = load(e0 + (size_t)(k < s.Sc ? k : 0u) * s.G, k < s.Sc);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 4; ++u) acc(v[u]);
+    }
+}
+
+template <int ACT>
+__global__ __launch_bounds__(kBlock) void k_groupnorm_nhwc_apply(const half_t *__restrict__ x, const float *__restrict__ ws,
+                                                                 const float *__restrict__ weight,
+                                                                 const float *__restrict__ bias, NShape s, float eps,
+                                                                 half_t *__restrict__ y, float *__restrict__ mean_out,
+                                                                 float *__restrict__ rstd_out) {
+    __shared__ float gmean[kBlock], grstd[kBlock];
+    const NWork w = nwork_of(s);
+    const NTile t = ntile_of(w);
+    const uint32_t gl = threadIdx.x / s.tpg, j = threadIdx.x - gl * s.tpg;
+    const uint32_t c = w.c0 + (t.tc << 3);
+    const size_t base = w.off + (t.tc << 3);
+    float wv[8], bv[8];
+    half8 pre[kNhwcPre];
+    if (t.active) {  // issued ahead of the merge: their latency runs beside it
+        load8(weight + c, wv);
+        load8(bias + c, bv);
+#pragma unroll
+        for (uint32_t u = 0; u < kNhwcPre; ++u)
+            if (t.r + u * t.rows < w.len) pre[u] = *reinterpret_cast<const half8 *>(x + base + (size_t)(t.r + u * t.rows) * s.C);
+    }
+    Mom m = {0.0f, 0.0f, 0.0f};
+    over_spans(
+        s, w, gl, j,
+        [&](size_t e, bool ok) { return ok ? Mom{ws[3 * e], ws[3 * e + 1], ws[3 * e + 2]} : Mom{0.0f, 0.0f, 0.0f}; },
+        [&](Mom v) { m = merge(m, v); });
+    for (uint32_t off = s.tpg >> 1; off > 0; off >>= 1) {
+        const Mom o = {__shfl_down(m.n, off, s.tpg), __shfl_down(m.mean, off, s.tpg), __shfl_down(m.m2, off, s.tpg)};
+        m = merge(m, o);
+    }
+    if (j == 0 && gl < w.ng) {
+        const float mean = m.mean, rstd = 1.0f / sqrtf(m.m2 / m.n + eps);
+        gmean[gl] = mean;
+        grstd[gl] = rstd;
+        if (w.span == 0) {
+            mean_out[w.b * s.G + w.g0 + gl] = mean;
+            rstd_out[w.b * s.G + w.g0 + gl] = rstd;
+        }
+    }
+    __syncthreads();
+    if (!t.active) return;
+    float a[8], b[8], mu[8];
+    chan_affine(wv, bv, gmean, grstd, c, s.per, w.g0, a, b, mu);
+    auto pixel = [&](uint32_t p, half8 v) {
+        half8 o;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] = (half_t)act_fwd<ACT>(fmaf((float)v[i], a[i], b[i]));
+        *reinterpret_cast<half8 *>(y + base + (size_t)p * s.C) = o;
+    };
+#pragma unroll
+    for (uint32_t u = 0; u < kNhwcPre; ++u)
+        if (t.r + u * t.rows < w.len) pixel(t.r + u * t.rows, pre[u]);
+#pragma unroll 8
+    for (uint32_t p = t.r + kNhwcPre * t.rows; p < w.len; p += t.rows)
+        pixel(p, *reinterpret_cast<const half8 *>(x + base + (size_t)p * s.C));
+}
+
+template <int ACT>
+__global__ __launch_bounds__(kBlock) void k_groupnorm_nhwc_bwd_sums(const half_t *__restrict__ x,
+                                                                    const half_t *__restrict__ dy,
+                                                                    const float *__restrict__ mean,
+                                                                    const float *__restrict__ rstd,
+                                                                    const float *__restrict__ weight,
+                                                                    const float *__restrict__ bias, NShape s,
+                                                                    float *__restrict__ partial) {
+    __shared__ float rdz[kNhwcMaxSlab], rdzx[kNhwcMaxSlab], cdz[kNhwcMaxSlab], cdzx[kNhwcMaxSlab];
+    const NWork w = nwork_of(s);
+    const NTile t = ntile_of(w);
+    if (t.active) {
+        float a[8], b[8], mu[8], sdz[8], sdzx[8];
+        float wv[8], bv[8];
+        load8(weight + w.c0 + (t.tc << 3), wv);
+        load8(bias + w.c0 + (t.tc << 3), bv);
+        chan_affine(wv, bv, mean + (size_t)w.b * s.G, rstd + (size_t)w.b * s.G, w.c0 + (t.tc << 3), s.per, 0u, a, b, mu);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sdz[i] = sdzx[i] = 0.0f;
+        const size_t base = w.off + (t.tc << 3);
+#pragma unroll 8
+        for (uint32_t p = t.r; p < w.len; p += t.rows) {
+            const size_t e = base + (size_t)p * s.C;
+            const half8 v = *reinterpret_cast<const half8 *>(x + e);
+            const half8 g = *reinterpret_cast<const half8 *>(dy + e);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float xf = (float)v[i], dz = act_bwd<ACT>((float)g[i], fmaf(xf, a[i], b[i]));
+                sdz[i] += dz;
+                sdzx[i] = fmaf(dz, xf - mu[i], sdzx[i]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            rdz[t.r * w.nc + (t.tc << 3) + i] = sdz[i];
+            rdzx[t.r * w.nc + (t.tc << 3) + i] = sdzx[i];
+        }
+    }
+    __syncthreads();
+    for (uint32_t c = threadIdx.x; c < w.nc; c += kBlock) {
+        float u = 0.0f, v = 0.0f;
+#pragma unroll 8
+        for (uint32_t r = 0; r < t.rows; ++r) {
+            u += rdz[r * w.nc + c];
+            v += rdzx[r * w.nc + c];
+        }
+        const float wc = weight[w.c0 + c];
+        cdz[c] = wc * u;
+        cdzx[c] = wc * v;
+    }
+    __syncthreads();
+    for (uint32_t g = threadIdx.x; g < w.ng; g += kBlock) {  // this span's share of (db, ds - db mean) of ATen's backward
+        float u = 0.0f, v = 0.0f;
+#pragma unroll 8
+        for (uint32_t c = g * s.per; c < (g + 1) * s.per; ++c) {
+            u += cdz[c];
+            v += cdzx[c];
+        }
+        float *o = partial + 2 * (w.entry0 + (size_t)w.span * s.G + w.g0 + g);
+        o[0] = u;
+        o[1] = v;
+    }
+}
+
+template <int ACT>
+__global__ __launch_bounds__(kBlock) void k_groupnorm_nhwc_bwd(const half_t *__restrict__ x, const half_t *__restrict__ dy,
+                                                               const float *__restrict__ mean,
+                                                               const float *__restrict__ rstd,
+                                                               const float *__restrict__ weight,
+                                                               const float *__restrict__ bias,
+                                                               const float *__restrict__ partial, NShape s,
+                                                               half_t *__restrict__ dx) {
+    __shared__ float gc2[kBlock], gc3[kBlock];
+    const NWork w = nwork_of(s);
+    const NTile t = ntile_of(w);
+    const uint32_t gl = threadIdx.x / s.tpg, j = threadIdx.x - gl * s.tpg;
+    const uint32_t c = w.c0 + (t.tc << 3);
+    const size_t base = w.off + (t.tc << 3);
+    float wv[8], bv[8];
+    half8 prex[kNhwcPre], preg[kNhwcPre];
+    if (t.active) {  // issued ahead of the merge, as in the apply kernel
+        load8(weight + c, wv);
+        load8(bias + c, bv);
+#pragma unroll
+        for (uint32_t u = 0; u < kNhwcPre; ++u)
+            if (t.r + u * t.rows < w.len) {
+                prex[u] = *reinterpret_cast<const half8 *>(x + base + (size_t)(t.r + u * t.rows) * s.C);
+                preg[u] = *reinterpret_cast<const half8 *>(dy + base + (size_t)(t.r + u * t.rows) * s.C);
+            }
+    }
+    float2 acc = {0.0f, 0.0f};
+    over_spans(
+        s, w, gl, j,
+        [&](size_t e, bool ok) { return ok ? float2{partial[2 * e], partial[2 * e + 1]} : float2{0.0f, 0.0f}; },
+        [&](float2 v) {
+            acc.x += v.x;
+            acc.y += v.y;
+        });
+    for (uint32_t off = s.tpg >> 1; off > 0; off >>= 1) {
+        acc.x += __shfl_down(acc.x, off, s.tpg);
+        acc.y += __shfl_down(acc.y, off, s.tpg);
+    }
+    const float *mu_b = mean + (size_t)w.b * s.G, *r_b = rstd + (size_t)w.b * s.G;
+    if (j == 0 && gl < w.ng) {
+        // ATen's c2 = (db mean - ds) rstd^3 / n with the difference summed centred (acc.y = ds - db mean), and its
+        // c2 x + c3, c3 = -c2 mean - db rstd / n, as c2 (x - mean) - db rstd / n: the same value without the two large
+        // terms that cancel when a group's spread is small against its mean
+        const float r = r_b[w.g0 + gl], inv_n = 1.0f / ((float)s.per * (float)s.HW);
+        gc2[gl] = -acc.y * r * r * r * inv_n;
+        gc3[gl] = -acc.x * r * inv_n;
+    }
+    __syncthreads();
+    if (!t.active) return;
+    float a[8], b[8], mu[8], c2[8], c3[8];
+    chan_affine(wv, bv, mu_b, r_b, c, s.per, 0u, a, b, mu);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        c2[i] = gc2[(c + i) / s.per - w.g0];
+        c3[i] = gc3[(c + i) / s.per - w.g0];
+    }
+    auto pixel = [&](uint32_t p, half8 v, half8 g) {
+        half8 o;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float xf = (float)v[i], dz = act_bwd<ACT>((float)g[i], fmaf(xf, a[i], b[i]));
+            o[i] = (half_t)fmaf(a[i], dz, fmaf(c2[i], xf - mu[i], c3[i]));
+        }
+        *reinterpret_cast<half8 *>(dx + base + (size_t)p * s.C) = o;
+    };
+#pragma unroll
+    for (uint32_t u = 0; u < kNhwcPre; ++u)
+        if (t.r + u * t.rows < w.len) pixel(t.r + u * t.rows, prex[u], preg[u]);
+#pragma unroll 8
+    for (uint32_t p = t.r + kNhwcPre * t.rows; p < w.len; p += t.rows)
+        pixel(p, *reinterpret_cast<const half8 *>(x + base + (size_t)p * s.C),
+              *reinterpret_cast<const half8 *>(dy + base + (size_t)p * s.C));
+}
+
+inline uint32_t gcd_u32(uint32_t a, uint32_t b) {
+    while (b) {
+        const uint32_t r = a % b;
+        a = b;
+        b = r;
+    }
+    return a;
+}
+
+// false = refuse: what make_shape refuses, channels that are no multiple of 8, or groups whose lcm with a vector of 8
+// channels exceeds the slab the LDS buffers hold
+bool make_nshape(uint32_t B, uint32_t C, uint32_t HW, uint32_t G, NShape &s, uint32_t &blocks) {
+    if (B == 0 || C == 0 || HW == 0 || G == 0 || C % G != 0 || C % 8 != 0) return false;
+    s.C = C; s.HW = HW; s.G = G; s.per = C / G;
+    if ((unsigned long long)s.per * HW > kMaxGroupElems) return false;
+    const unsigned long long lcm = (unsigned long long)s.per / gcd_u32(s.per, 8u) * 8u;
+    if (lcm > kNhwcMaxSlab) return false;
+    s.slabC = (uint32_t)lcm * (uint32_t)((64u + lcm - 1) / lcm);
+    if (s.slabC > C) s.slabC = C;  // (C is a multiple of the lcm)
+    s.nslab = (C + s.slabC - 1) / s.slabC;
+    const uint32_t gs = s.slabC / s.per;  // groups per slab: at most kNhwcMaxSlab / 8 = kBlock
+    const uint32_t cap = kNhwcMerge / gs > 0 ? kNhwcMerge / gs : 1u;
+    const uint32_t pmin = (kNhwcChunk + s.slabC - 1) / s.slabC, pcap = (HW + cap - 1) / cap;
+    s.P = pmin > pcap ? pmin : pcap;
+    // a workgroup of the second kernels reads gs * Sc workspace entries for its P * slabC elements: keep the entries below
+    // 1 / kNhwcRatio of the elements, P^2 >= kNhwcRatio * HW / per (measured: at 1 / 2 the merge costs as much as the data)
+    while ((unsigned long long)s.P * s.P * s.per < (unsigned long long)kNhwcRatio * HW) ++s.P;
+    if (s.P > HW) s.P = HW;
+    s.Sc = (HW + s.P - 1) / s.P;
+    uint32_t tpg = 1;  // no more lanes per group than there are spans to merge: a short shuffle tree for the small tensors
+    while (tpg * 2 <= 64u && tpg * 2 * gs <= (uint32_t)kBlock && tpg < s.Sc) tpg *= 2;
+    s.tpg = tpg;
+    const unsigned long long n = (unsigned long long)B * s.Sc * s.nslab;
+    if (n > 0x7FFFFFFFull) return false;
+    blocks = (uint32_t)n;
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -360,6 +761,86 @@ int mi3d_groupnorm_act_backward(const void *x, const void *dy, const float *mean
     else
         hipLaunchKernelGGL(k_groupnorm_bwd<1>, grid, block, 0, st, (const half_t *)x, (const half_t *)dy, mean, rstd,
                            weight, bias, partial, s, vec_ok, (half_t *)dx);
+    return (int)hipGetLastError();
+}
+
+uint32_t mi3d_groupnorm_nhwc_span(uint32_t C, uint32_t HW, uint32_t G) {
+    NShape s;
+    uint32_t blocks;
+    return make_nshape(1, C, HW, G, s, blocks) ? s.P : 0u;
+}
+
+uint32_t mi3d_groupnorm_nhwc_spans(uint32_t C, uint32_t HW, uint32_t G) {
+    NShape s;
+    uint32_t blocks;
+    return make_nshape(1, C, HW, G, s, blocks) ? s.Sc : 0u;
+}
+
+int mi3d_groupnorm_nhwc_stats(const void *x, uint32_t B, uint32_t C, uint32_t HW, uint32_t G, float *ws, void *stream) {
+    NShape s;
+    uint32_t blocks;
+    if (!make_nshape(B, C, HW, G, s, blocks) || x == nullptr || ws == nullptr || !aligned16(x))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_groupnorm_nhwc_stats, dim3(blocks), dim3(kBlock), 0, as_stream(stream), (const half_t *)x, s, ws);
+    return (int)hipGetLastError();
+}
+
+int mi3d_groupnorm_nhwc_act_forward(const void *x, const float *ws, const float *weight, const float *bias, uint32_t B,
+                                    uint32_t C, uint32_t HW, uint32_t G, float eps, int act, void *y, float *mean,
+                                    float *rstd, void *stream) {
+    NShape s;
+    uint32_t blocks;
+    if (!make_nshape(B, C, HW, G, s, blocks) || x == nullptr || ws == nullptr || weight == nullptr || bias == nullptr ||
+        y == nullptr || mean == nullptr || rstd == nullptr || (act != 0 && act != 1) || !aligned16(x) || !aligned16(y))
+        return (int)hipErrorInvalidValue;
+    const dim3 grid(blocks), block(kBlock);
+    const hipStream_t st = as_stream(stream);
+    if (act == 0)
+        hipLaunchKernelGGL(k_groupnorm_nhwc_apply<0>, grid, block, 0, st, (const half_t *)x, ws, weight, bias, s, eps,
+                           (half_t *)y, mean, rstd);
+    else
+        hipLaunchKernelGGL(k_groupnorm_nhwc_apply<1>, grid, block, 0, st, (const half_t *)x, ws, weight, bias, s, eps,
+                           (half_t *)y, mean, rstd);
+    return (int)hipGetLastError();
+}
+
+int mi3d_groupnorm_nhwc_act_backward_sums(const void *x, const void *dy, const float *mean, const float *rstd,
+                                          const float *weight, const float *bias, uint32_t B, uint32_t C, uint32_t HW,
+                                          uint32_t G, int act, float *partial, void *stream) {
+    NShape s;
+    uint32_t blocks;
+    if (!make_nshape(B, C, HW, G, s, blocks) || x == nullptr || dy == nullptr || mean == nullptr || rstd == nullptr ||
+        weight == nullptr || bias == nullptr || partial == nullptr || (act != 0 && act != 1) || !aligned16(x) ||
+        !aligned16(dy))
+        return (int)hipErrorInvalidValue;
+    const dim3 grid(blocks), block(kBlock);
+    const hipStream_t st = as_stream(stream);
+    if (act == 0)
+        hipLaunchKernelGGL(k_groupnorm_nhwc_bwd_sums<0>, grid, block, 0, st, (const half_t *)x, (const half_t *)dy, mean,
+                           rstd, weight, bias, s, partial);
+    else
+        hipLaunchKernelGGL(k_groupnorm_nhwc_bwd_sums<1>, grid, block, 0, st, (const half_t *)x, (const half_t *)dy, mean,
+                           rstd, weight, bias, s, partial);
+    return (int)hipGetLastError();
+}
+
+int mi3d_groupnorm_nhwc_act_backward(const void *x, const void *dy, const float *mean, const float *rstd,
+                                     const float *weight, const float *bias, const float *partial, uint32_t B, uint32_t C,
+                                     uint32_t HW, uint32_t G, int act, void *dx, void *stream) {
+    NShape s;
+    uint32_t blocks;
+    if (!make_nshape(B, C, HW, G, s, blocks) || x == nullptr || dy == nullptr || mean == nullptr || rstd == nullptr ||
+        weight == nullptr || bias == nullptr || partial == nullptr || dx == nullptr || (act != 0 && act != 1) ||
+        !aligned16(x) || !aligned16(dy) || !aligned16(dx))
+        return (int)hipErrorInvalidValue;
+    const dim3 grid(blocks), block(kBlock);
+    const hipStream_t st = as_stream(stream);
+    if (act == 0)
+        hipLaunchKernelGGL(k_groupnorm_nhwc_bwd<0>, grid, block, 0, st, (const half_t *)x, (const half_t *)dy, mean, rstd,
+                           weight, bias, partial, s, (half_t *)dx);
+    else
+        hipLaunchKernelGGL(k_groupnorm_nhwc_bwd<1>, grid, block, 0, st, (const half_t *)x, (const half_t *)dy, mean, rstd,
+                           weight, bias, partial, s, (half_t *)dx);
     return (int)hipGetLastError();
 }
 

@@ -93,6 +93,10 @@ _SIGNATURES = {
     "mi3d_groupnorm_act_forward": [vp, vp, vp, vp, u32, u32, u32, u32, f32, i32, vp, vp, vp, vp],
     "mi3d_groupnorm_act_backward_sums": [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, i32, vp, vp],
     "mi3d_groupnorm_act_backward": [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, i32, vp, vp],
+    "mi3d_groupnorm_nhwc_stats": [vp, u32, u32, u32, u32, vp, vp],
+    "mi3d_groupnorm_nhwc_act_forward": [vp, vp, vp, vp, u32, u32, u32, u32, f32, i32, vp, vp, vp, vp],
+    "mi3d_groupnorm_nhwc_act_backward_sums": [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, i32, vp, vp],
+    "mi3d_groupnorm_nhwc_act_backward": [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, i32, vp, vp],
     # Part 11 -----------------------------------------------------------------------------------------
     "mi3d_pc_unproject": [vp, vp, u32, u32, vp, vp, vp, C.c_size_t, vp, C.c_uint64, vp, vp],
     "mi3d_pc_project": [vp, C.c_uint64, vp, vp, vp, vp, vp],
@@ -116,6 +120,8 @@ _LATE_SIGNATURES = {
     "mi3d_mc_case": ([u32, C.POINTER(C.c_int8)], C.c_int),
     "mi3d_atlas_cell": ([C.c_uint64, u32], u32),
     "mi3d_groupnorm_chunks": ([u32], u32),
+    "mi3d_groupnorm_nhwc_span": ([u32, u32, u32], u32),
+    "mi3d_groupnorm_nhwc_spans": ([u32, u32, u32], u32),
     "mi3d_pc_unproject_workspace": ([u32, u32], C.c_size_t),
     "mi3d_mesh_components_workspace": ([C.c_uint64, C.c_uint64], C.c_size_t),
 }

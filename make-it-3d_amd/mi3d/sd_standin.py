@@ -51,10 +51,64 @@ import torch.nn.functional as F
 #                   7.5 -> 5.2); the whole step 98.8-100.4 -> 90.7-92.3 ms and 1.0 GiB less peak memory
 #                   (profiles/bench_gn_fused_ab.json) - ON.  With VAE_GRAPH on top: 22.0, still nothing.  With GN_FUSED and
 #                   GN_SPLIT_STATS both off the call takes 23.8 ms on the current PyTorch-ROCm.
+#   VAE_CHANNELS_LAST, UNET_CHANNELS_LAST   the network runs in torch.channels_last: MIOpen's winning convolutions are its
+#                   NHWC implicit-GEMM kernels, which on NCHW tensors it wraps in batched transposes of the input, the
+#                   (frozen) weight and the output.  With a switch on, the network's conv weights are converted once
+#                   (`set_channels_last`), its input once at the entry, every GroupNorm takes the NHWC kernels of
+#                   csrc/groupnorm.hip (GN_FUSED), and the attention blocks' [B, HW, C] is a view.  The small output goes
+#                   back to NCHW at the exit.  Per layer (NHWC_EXCEPT of each class lists what stays NCHW), from the trace:
+#                   the VAE's 3-channel conv_in stays NCHW - its NHWC data gradient is a 0.50 ms CK kernel per step against
+#                   0.04 ms of GEMM + col2im in NCHW, more than the two 67 MB layout copies of its output and its output
+#                   gradient (0.12 ms each) that the exception costs; its 8-channel conv_out / quant_conv (0.02 ms, 7 us
+#                   naive kernels) and the whole U-Net, 4-channel conv_in / conv_out included, follow the switch.
+#                   Measured (tools/sd_knobs.py --nhwc, profiles/sd_knobs_nhwc.json; off / on / off / on per network in one
+#                   process): VAE alone 21.9 -> 21.3-21.5 ms per guidance call (encode 5.26 -> 4.89, backward 5.04 -> 4.88),
+#                   U-Net alone 21.8 -> 20.9-21.0 (U-Net 11.54 -> 10.64), both 21.9 -> 20.4.  The whole step with both on
+#                   (profiles/bench_nhwc_ab.json, parent and change alternating, two sessions): parent 90.8 / 93.0 / 92.0,
+#                   change 90.6 / 91.2 / 91.1 ms, then 93.9 / 92.4 / 89.1 and 92.0 / 86.5 / 86.1 - `guidance_train_step`
+#                   22.7-23.2 -> 21.5-21.8 in every pair, but in neither session does the change's slowest run beat the
+#                   parent's fastest, so the gain is not told from the step's run-to-run spread - both OFF; the route ships
+#                   tested behind the switches.  What is left on the table: DESIGN 3.6.
 GN_SPLIT_STATS = True
 VAE_HALF_CACHE = False
 VAE_GRAPH = False
 GN_FUSED = True
+VAE_CHANNELS_LAST = False
+UNET_CHANNELS_LAST = False
+
+
+class _ChannelsLastMixin:
+    """A network whose convolutions can be switched between NCHW and torch.channels_last as a whole."""
+    NHWC_EXCEPT = ()       # names of direct-child convolutions that stay NCHW when the network is channels-last
+    channels_last = False
+
+    def set_channels_last(self, on):
+        """Convert the conv weights (once per change of `on`); forward() then converts its input at the entry."""
+        on = bool(on)
+        if on == self.channels_last:
+            return self
+        keep = {id(getattr(self, n)) for n in self.NHWC_EXCEPT}
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                fmt = torch.channels_last if on and id(m) not in keep else torch.contiguous_format
+                m.weight.data = m.weight.data.contiguous(memory_format=fmt)
+        self.channels_last = on
+        return self
+
+    def _entry(self, x):
+        return x.contiguous(memory_format=torch.channels_last) if self.channels_last else x
+
+    def _exit(self, y):
+        """The (small) output back in NCHW: what follows - chunk, randn_like, the scheduler arithmetic - sees the tensor it
+        sees with the switch off (randn_like fills in memory order: a channels-last mean would permute the noise)."""
+        return y.contiguous() if self.channels_last else y
+
+
+def _set_format(net, on):
+    """net.set_channels_last(on) where the network has the switch (any other module in its place runs as it is)."""
+    if hasattr(net, "set_channels_last"):
+        net.set_channels_last(on)
+    return net
 
 
 class _SplitStatsGroupNorm(torch.autograd.Function):
@@ -104,15 +158,17 @@ class GroupNorm(nn.GroupNorm):
         return cached[1], cached[2]
 
     def forward(self, x, act=None):
-        """act(group_norm(x)), act None or "silu".  Contiguous binary16 on the GPU with a frozen affine pair: the fused HIP
-        route (GN_FUSED), binary16 out.  Everything else: the stock routes, with F.silu on top for act == "silu"."""
+        """act(group_norm(x)), act None or "silu".  Binary16 on the GPU with a frozen affine pair, contiguous or
+        channels-last (norm_ops.layout): the fused HIP route (GN_FUSED), binary16 out in the input's memory format.
+        Everything else: the stock routes, with F.silu on top for act == "silu"."""
         if act not in (None, "silu"):
             raise ValueError(f"act must be None or 'silu' (got {act!r})")
-        if (GN_FUSED and x.is_cuda and x.dtype == torch.float16 and x.dim() >= 2 and x.is_contiguous()
+        if (GN_FUSED and x.is_cuda and x.dtype == torch.float16 and x.dim() >= 2
                 and self.affine and not self.weight.requires_grad and not self.bias.requires_grad):
             from . import norm_ops
-            w, b = self._affine_f32()
-            return norm_ops.group_norm_act(x, w, b, self.num_groups, self.eps, act)
+            if norm_ops.layout(x, self.num_groups) is not None:
+                w, b = self._affine_f32()
+                return norm_ops.group_norm_act(x, w, b, self.num_groups, self.eps, act)
         y = self._stock(x)
         return F.silu(y) if act == "silu" else y
 
@@ -188,12 +244,13 @@ class SpatialTransformer(nn.Module):
 
     def forward(self, x, ctx):
         B, C, H, W = x.shape
+        # channels-last x: both reshapes are views of [B, HW, C] memory (a copy each way in NCHW), the sum stays channels-last
         h = self.norm(x).permute(0, 2, 3, 1).reshape(B, H * W, C)
         h = self.proj_out(self.block(self.proj_in(h), ctx))
         return x + h.reshape(B, H, W, C).permute(0, 3, 1, 2)
 
 
-class UNetSD2(nn.Module):
+class UNetSD2(_ChannelsLastMixin, nn.Module):
     def __init__(self, ch=(320, 640, 1280, 1280), ctx_dim=1024, layers=2):
         super().__init__()
         temb = ch[0] * 4
@@ -228,7 +285,7 @@ class UNetSD2(nn.Module):
         ang = t.float().view(-1, 1).expand(x.shape[0], 1) * freqs[None]
         temb = torch.cat([torch.cos(ang), torch.sin(ang)], -1).to(x.dtype)
         temb = self.time2(F.silu(self.time1(temb)))
-        h = self.conv_in(x)
+        h = self.conv_in(self._entry(x))
         hs = [h]
         for blk in self.down:
             if len(blk) == 1:
@@ -243,10 +300,12 @@ class UNetSD2(nn.Module):
             h = blk[1](h, encoder_hidden_states) if isinstance(blk[1], SpatialTransformer) else h
             if len(blk) == 3:
                 h = blk[2](F.interpolate(h, scale_factor=2.0, mode="nearest"))
-        return self.conv_out(self.norm_out(h, act="silu"))
+        return self._exit(self.conv_out(self.norm_out(h, act="silu")))
 
 
-class VAEEncoderSD(nn.Module):
+class VAEEncoderSD(_ChannelsLastMixin, nn.Module):
+    NHWC_EXCEPT = ("conv_in",)
+
     def __init__(self, ch=(128, 256, 512, 512), layers=2):
         super().__init__()
         self.conv_in = nn.Conv2d(3, ch[0], 3, padding=1)
@@ -264,7 +323,7 @@ class VAEEncoderSD(nn.Module):
         self.quant_conv = nn.Conv2d(8, 8, 1)
 
     def forward(self, x):
-        h = self.conv_in(x)
+        h = self._entry(self.conv_in(x))      # (conv_in itself stays NCHW: NHWC_EXCEPT)
         for b in self.blocks:
             if isinstance(b, nn.Conv2d):
                 h = b(F.pad(h, (0, 1, 0, 1)))
@@ -272,9 +331,9 @@ class VAEEncoderSD(nn.Module):
                 h = b(h)
         h = self.mid1(h)
         B, C, H, W = h.shape
-        a = self.mid_attn(self.mid_norm(h).permute(0, 2, 3, 1).reshape(B, H * W, C))
+        a = self.mid_attn(self.mid_norm(h).permute(0, 2, 3, 1).reshape(B, H * W, C))    # (views when h is channels-last)
         h = self.mid2(h + a.reshape(B, H, W, C).permute(0, 3, 1, 2))
-        return self.quant_conv(self.conv_out(self.norm_out(h, act="silu")))  # [B, 8, H/8, W/8] = (mean, logvar)
+        return self._exit(self.quant_conv(self.conv_out(self.norm_out(h, act="silu"))))  # [B, 8, H/8, W/8] = (mean, logvar)
 
 
 class VAEDecoderSD(nn.Module):
@@ -400,6 +459,9 @@ class StableDiffusionStandIn(nn.Module):
             self.vae_decoder = VAEDecoderSD(**(decoder_kw or {})) if with_decoder else None
         self.to(device)
         self.unet.to(dtype)  # frozen, weights kept in half like an inference deployment; VAE stays fp32 (has grad)
+        on_gpu = torch.device(device).type == "cuda"      # (a CPU stand-in stays NCHW, as its forwards would make it)
+        self.unet.set_channels_last(UNET_CHANNELS_LAST and on_gpu)
+        self.vae_encoder.set_channels_last(VAE_CHANNELS_LAST and on_gpu)
         for p in self.parameters():
             p.requires_grad_(False)
         self.num_train_timesteps = 1000
@@ -417,7 +479,7 @@ class StableDiffusionStandIn(nn.Module):
         """The encoder to run: its binary16 copy under autocast(float16) on the GPU (VAE_HALF_CACHE), else the fp32 one."""
         if not (VAE_HALF_CACHE and x.is_cuda and torch.is_autocast_enabled("cuda")
                 and torch.get_autocast_dtype("cuda") == torch.float16):
-            return self.vae_encoder
+            return _set_format(self.vae_encoder, VAE_CHANNELS_LAST and x.is_cuda)
         half = self.__dict__.get("_vae_encoder_half")
         if half is None:
             import copy
@@ -425,7 +487,7 @@ class StableDiffusionStandIn(nn.Module):
             for p in half.parameters():
                 p.requires_grad_(False)
             self.__dict__["_vae_encoder_half"] = half      # (not a registered sub-module: state_dict stays the fp32 model's)
-        return half
+        return _set_format(half, VAE_CHANNELS_LAST)
 
     def _vae_moments(self, x):
         """vae_encoder(x): through the graphed callable (VAE_GRAPH) when x is the [1, 3, 512, 512] image under
@@ -435,7 +497,7 @@ class StableDiffusionStandIn(nn.Module):
                 and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.float16
                 and not torch.cuda.is_current_stream_capturing()):
             return enc(x)
-        key = (id(enc), GN_SPLIT_STATS, GN_FUSED, x.requires_grad)
+        key = (id(enc), GN_SPLIT_STATS, GN_FUSED, x.requires_grad, getattr(enc, "channels_last", False))
         cached = self.__dict__.get("_vae_graphed")
         if cached is None or cached[0] != key:
             if self.__dict__.get("_vae_graph_failed"):
@@ -560,9 +622,11 @@ class StableDiffusionStandIn(nn.Module):
     def _unet_forward(self, x, t, ctx):
         """U-Net noise prediction; on the GPU through a captured hipGraph (torch.cuda.CUDAGraph) keyed on the shapes
         and the autocast state, eagerly if capture is unavailable."""
+        _set_format(self.unet, UNET_CHANNELS_LAST and x.is_cuda)   # (weights converted once per change of the switch)
         if not (getattr(self, "graph_unet", False) and x.is_cuda):  # (objects assembled without __init__: eager)
             return self.unet(x, t, encoder_hidden_states=ctx)
-        key = (tuple(x.shape), x.dtype, tuple(ctx.shape), tuple(t.shape), torch.is_autocast_enabled("cuda"), GN_FUSED)
+        key = (tuple(x.shape), x.dtype, tuple(ctx.shape), tuple(t.shape), torch.is_autocast_enabled("cuda"), GN_FUSED,
+               getattr(self.unet, "channels_last", False))
         if getattr(self, "_graph", None) is None or self._graph[0] != key:
             try:
                 gx, gt, gc = x.clone(), t.clone(), ctx.clone()
