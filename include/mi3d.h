@@ -454,12 +454,14 @@ int mi3d_field_head_backward(const float *h, const float *x, const float *x2, ui
  * the four state arrays are updated in place (the caller zero-initialises exp_avg / exp_avg_sq / exp_avg_diff once;
  * neg_pre_grad is initialised here when first_step != 0).
  * The global-norm clip stays on the device: call mi3d_sumsq_accumulate on every gradient tensor into ONE zeroed device
- * float, pass it as grad_sumsq; clip = min(max_grad_norm / (sqrt(sum) + clip_eps), 1) (optimizer.py:107-127, without
- * its `.item()` host sync).  grad_sumsq == NULL or max_grad_norm <= 0: no clipping. */
-int mi3d_sumsq_accumulate(const float *x, size_t n, float *acc, void *stream);
+ * double (8-byte aligned; the sum and the factor are formed in binary64, the factor rounded once), pass it as grad_sumsq; clip = min(max_grad_norm / (sqrt(sum) + clip_eps), 1) (optimizer.py:107-127, without
+ * its `.item()` host sync).  grad_sumsq == NULL or max_grad_norm <= 0: no clipping.
+ * The betas are binary64: the kernel uses (float)beta and (float)(1 - beta), each rounded once from the caller's value,
+ * as the reference's `mul_(beta)` / `alpha=1 - beta` do (1.0f - (float)beta is off 1 - beta by up to 2^-25 / (1 - beta)). */
+int mi3d_sumsq_accumulate(const float *x, size_t n, double *acc, void *stream);
 int mi3d_adan_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, float *exp_avg_diff,
-                   float *neg_pre_grad, size_t count, const float *grad_sumsq, float max_grad_norm, float clip_eps,
-                   int first_step, float beta1, float beta2, float beta3, float bias_correction1,
+                   float *neg_pre_grad, size_t count, const double *grad_sumsq, float max_grad_norm, float clip_eps,
+                   int first_step, double beta1, double beta2, double beta3, float bias_correction1,
                    float bias_correction2, float bias_correction3_sqrt, float lr, float weight_decay, float eps,
                    int no_prox, void *stream);
 
@@ -470,7 +472,8 @@ int mi3d_adan_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq,
  * pytorch3d NDC: +X left, +Y up; z = depth, points with z < 0 are skipped), image H x W, `radius` in NDC units,
  * K = points_per_pixel <= 8.  Outputs [H,W,K]: idx (point index, -1 = unused), zbuf (may be NULL), dists (squared NDC
  * distance to the pixel centre, -1 = unused), the K nearest covering points in ascending z (ties: lower index first).
- * `workspace` holds the per-tile point lists (mi3d_points_rasterize_workspace bytes cover the worst case).
+ * `workspace` holds the per-tile point lists (mi3d_points_rasterize_workspace bytes cover the worst case; P = 0 is
+ * legal, needs the tile table alone and gives -1 everywhere).
  * mi3d_points_composite_forward = alphas = 1 - sqrt(clamp(0.1 dists / radius^2, 1e-3, 1)) (refine_utils.py:321-326)
  * followed by compositing.alpha_composite: out [C,H,W] from features [P,C] (C <= 32), front to back.
  * mi3d_points_composite_backward ACCUMULATES d out / d features into grad_features [P,C] (caller zeroes it).

@@ -313,11 +313,13 @@ uint32_t tiles_per_point_max(const RasterGeom &g) {
 extern "C" {
 
 size_t mi3d_points_rasterize_workspace(uint32_t P, uint32_t H, uint32_t W, float radius) {
-    if (P == 0 || H == 0 || W == 0) return 0;
+    if (H == 0 || W == 0) return 0;
     const RasterGeom g = make_geom((int)H, (int)W, radius);
     const size_t n_tiles = (size_t)g.tiles_x * g.tiles_y;
-    // counts, offsets (+1), cursors, then the tile lists: every point can sit in tiles_per_point_max tiles
-    return (3 * n_tiles + 4) * sizeof(uint32_t) + (size_t)P * tiles_per_point_max(g) * sizeof(uint32_t);
+    // counts, offsets (+1), cursors, then the tile lists: every point can sit in tiles_per_point_max tiles.  An empty
+    // cloud still needs the tile table (every list is empty, every slot -1) and the one list entry the launch asks for
+    const size_t entries = P ? (size_t)P * tiles_per_point_max(g) : 1;
+    return (3 * n_tiles + 4) * sizeof(uint32_t) + entries * sizeof(uint32_t);
 }
 
 int mi3d_points_rasterize(const float *points_ndc, uint32_t P, uint32_t H, uint32_t W, float radius,

@@ -72,8 +72,8 @@ _SIGNATURES = {
     "mi3d_field_head_backward": [vp, vp, vp, u32, vp, u32, u32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp],
     # Part 6 ------------------------------------------------------------------------------------------
     "mi3d_sumsq_accumulate": [vp, C.c_size_t, vp, vp],
-    "mi3d_adan_step": [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, f32, f32, i32, f32, f32, f32, f32, f32, f32, f32, f32, f32,
-                       i32, vp],
+    "mi3d_adan_step": [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, f32, f32, i32, C.c_double, C.c_double, C.c_double, f32, f32,
+                       f32, f32, f32, f32, i32, vp],
     # Part 7 ------------------------------------------------------------------------------------------
     "mi3d_points_rasterize": [vp, u32, u32, u32, f32, u32, vp, C.c_size_t, vp, vp, vp, vp],
     "mi3d_points_composite_forward": [vp, vp, u32, u32, u32, vp, u32, C.c_double, vp, vp],

@@ -31,7 +31,7 @@ class Adan(torch.optim.Optimizer):
         sumsq = None
         with torch.cuda.device(dev):
             if max_norm > 0:
-                sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
+                sumsq = torch.zeros(1, dtype=torch.float64, device=dev)
                 for p in ps:
                     L.call("mi3d_sumsq_accumulate", L.ptr(p.grad), C.c_size_t(p.grad.numel()), L.ptr(sumsq), L.stream(p))
             for group in self.param_groups:

@@ -22,8 +22,11 @@ SHAPES = [
     ((1, 64, 96, 100), 32),    # rows of 9600 = 8192 + 1408: two chunks per row, four per group, a ragged last one
     ((2, 1280, 8, 8), 32),     # the U-Net's deepest level: 40 channels per group, 40 triples merged per workgroup
     ((1, 128, 64, 64), 4),     # a group count other than 32; 32 channels per group (the split-statistics stock route)
+    ((1, 128, 258, 256), 4),   # rows of 66048 = 8 x 8192 + 512: 9 chunks x 32 channels = 288 partials per group, so the
+                               # merge loops of k_groupnorm_apply / k_groupnorm_bwd go round twice (the second ragged)
 ]
-IDS = ["1x32x5x7", "2x64x17x19", "1x64x96x100", "2x1280x8x8", "1x128x64x64g4"]
+IDS = ["1x32x5x7", "2x64x17x19", "1x64x96x100", "2x1280x8x8", "1x128x64x64g4", "1x128x258x256g4"]
+MERGE_BLOCK = 256              # kBlock of csrc/groupnorm.hip: partials merged per round, `i += kBlock`
 DISTS = ["randn", "offset30"]
 
 
@@ -99,6 +102,18 @@ def test_parity_with_fp64_no_worse_than_the_stock_route(shape, groups, act, eps,
         print(msg)
         assert fm == fm and fr == fr, msg     # not NaN
         assert fm <= FACTOR * sm and fr <= FACTOR * sr, msg
+
+
+def test_the_last_shape_reaches_the_second_round_of_the_merge():
+    """S = (C / G) x chunks partials per group, merged MERGE_BLOCK per round by k_groupnorm_apply / k_groupnorm_bwd; the
+    chunk count is the library's own.  Every other shape stays within one round (the largest is 40)."""
+    from mi3d import _lib as L
+
+    def partials(shape, groups):
+        return shape[1] // groups * int(L.lib().mi3d_groupnorm_chunks(shape[2] * shape[3]))
+    assert [partials(s, g) for s, g in SHAPES[:-1]] == [1, 2, 4, 40, 32]
+    S = partials(*SHAPES[-1])
+    assert S == 288 and MERGE_BLOCK < S < 2 * MERGE_BLOCK and S % 64 != 0     # a second round, ragged: half a wave
 
 
 def _fused_once(x, w, b, dy, groups, eps, act):

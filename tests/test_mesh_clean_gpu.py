@@ -4,7 +4,9 @@ arrays equal, float rows bit-identical.  The inputs are the smallest at which th
 product's own marching cubes (two components, a component with specks, one long thin component, nothing) and hand-built
 index meshes (more than one workgroup and a multiple of neither 64 nor 256, three vertex numberings of one strip, labels
 past 16 bits, more elements than one pass of the statistics kernels' grid, unreferenced vertices, duplicate and degenerate
-triangles, non-finite coordinates).  Then export_mesh with the three arguments, end to end."""
+triangles, non-finite coordinates).  Three meshes lie above the sizes at which the statistics kernels' strides and both
+scans of k_cl_scan go round again (section "the loops' later rounds"); one of them holds bad indices and so goes
+through the entry points themselves.  Then export_mesh with the three arguments, end to end."""
 import os
 
 import numpy as np
@@ -305,6 +307,177 @@ def test_on_a_side_stream(cuda, inputs):
     assert np.array_equal(label.cpu().numpy(), comps[0])
     assert cv.cpu().numpy().tobytes() == rv.tobytes() and np.array_equal(ct.cpu().numpy(), rt)
     assert np.array_equal(cmap.cpu().numpy(), rmap)
+
+
+# ------------------------------------------------------------------------------------------------ the loops' later rounds
+
+CLEAN_BLOCK = 256                       # kBlock of csrc/meshclean.hip: elements per workgroup
+STAT_BLOCKS = 512                       # kStatBlocks: k_cc_faces / k_cc_boxes / k_cc_finish stride from at most this many
+STAT_SLOTS = 512                        # kSlots: labels a workgroup's LDS table holds (kProbes = 4 probes each)
+SCAN_ROUND = 1024                       # block sums per round of k_cl_scan's scan_row (its `b0 += 1024`)
+STAT_PASS, SCAN_PASS = STAT_BLOCKS * CLEAN_BLOCK, SCAN_ROUND * CLEAN_BLOCK       # 131 072 and 262 144 elements
+SINGLES, LONG_STRIP = 150_000, 300_000
+
+
+def many_singles():
+    """150 000 one-triangle components, nv = 450 000: the statistics kernels go round four times over the vertices and
+    twice over the triangles; a workgroup meets up to 342 labels in k_cc_boxes and 512 in k_cc_faces, which four probes
+    into 512 slots cannot all place, so the path to global atomics is an everyday one here.  The sizes of the triangles
+    spread over three decades: a diagonal rule keeps and drops on both sides of every round boundary."""
+    rng = np.random.default_rng(21)
+    scale = np.repeat(10.0 ** rng.uniform(-2, 1, SINGLES), 3)[:, None]
+    v = (rng.normal(size=(3 * SINGLES, 3)) * scale).astype(np.float32)
+    return v, np.arange(3 * SINGLES, dtype=np.int32).reshape(SINGLES, 3)
+
+
+def long_strip():
+    """One strip (i, i + 1, i + 2) of 300 000 triangles: a single label cited from every workgroup in every stride, and
+    more than 262 144 vertices AND triangles, so both scans of k_cl_scan carry a base into a second round."""
+    i = np.arange(LONG_STRIP)
+    return coords(LONG_STRIP + 2, 22), np.stack([i, i + 1, i + 2], 1).astype(np.int32)
+
+
+def both_with_dirt():
+    """The two above in one mesh, the triangles of both shuffled together with 3 000 that hold an index outside [0, nv)
+    (-1, nv, the int32 extremes, in any of the three places), NaN coordinates in a thousand vertices of either part and
+    1 000 vertices no triangle cites behind everything."""
+    rng = np.random.default_rng(23)
+    (va, ta), (vb, tb) = many_singles(), long_strip()
+    v = np.concatenate([va, vb, coords(1000, 24)])
+    nv = len(v)
+    bad = rng.integers(0, len(va) + len(vb), size=(3000, 3)).astype(np.int64)
+    bad[np.arange(3000), rng.integers(0, 3, 3000)] = rng.choice([-1, nv, nv + 7, 2 ** 31 - 1, -2 ** 31], 3000)
+    t = np.concatenate([ta, tb + len(va), bad.astype(np.int32)])
+    t = t[rng.permutation(len(t))]
+    for lo, hi in ((0, len(va)), (len(va), len(va) + len(vb))):
+        rows = rng.choice(np.arange(lo, hi), 1000, replace=False)
+        v[rows, rng.integers(0, 3, 1000)] = np.nan
+    v[len(va) + 5] = np.nan                                # a vertex of the strip without any number
+    return v, np.ascontiguousarray(t)
+
+
+LARGE = {"many_singles": many_singles, "long_strip": long_strip, "both_with_dirt": both_with_dirt}
+LARGE_BAD = {"many_singles": 0, "long_strip": 0, "both_with_dirt": 3000}
+
+
+@pytest.fixture(scope="module")
+def large(cuda):
+    """name -> (vertices, triangles, model components, the two on the GPU): made and modelled once, never changed."""
+    out = {}
+    for name, make in LARGE.items():
+        v, t = make()
+        comps = M.components(v, t)
+        out[name] = (v, t, comps) + upload(cuda, v, t)
+    return out
+
+
+def test_the_large_inputs_cross_the_thresholds(large):
+    """The block counts are the library's own (mi3d_mesh_components_workspace: a uint32 per block of vertices and of
+    triangles, a byte per vertex, each part padded to 8 bytes)."""
+    from mi3d import _lib
+    pad8 = lambda b: (b + 7) // 8 * 8                      # noqa: E731
+    blocks = {}
+    for name, (v, t, comps, _, _) in large.items():
+        nbv, nbt = -(-len(v) // CLEAN_BLOCK), -(-len(t) // CLEAN_BLOCK)
+        assert int(_lib.lib().mi3d_mesh_components_workspace(len(v), len(t))) == pad8(nbv * 4) + pad8(nbt * 4) + pad8(len(v))
+        assert nbv > STAT_BLOCKS and nbt > STAT_BLOCKS and len(v) > STAT_PASS and len(t) > STAT_PASS    # every statistics loop
+        assert nbv > SCAN_ROUND and nbv % 64 != 0                                                  # the vertex scan, ragged
+        assert comps[4] == LARGE_BAD[name]
+        blocks[name] = (nbv, nbt)
+    assert blocks["long_strip"][1] > SCAN_ROUND and blocks["both_with_dirt"][1] > SCAN_ROUND        # the triangle scan
+    label, faces = large["many_singles"][2][:2]
+    assert np.array_equal(label, np.repeat(np.arange(0, 3 * SINGLES, 3), 3)) and int(faces.sum()) == SINGLES
+    # labels one workgroup of a statistics kernel meets (its vertices / triangles over all strides) against its table
+    assert -(-len(label) // STAT_PASS) * CLEAN_BLOCK // 3 > STAT_SLOTS // 2 and 2 * CLEAN_BLOCK >= STAT_SLOTS
+    label, faces = large["long_strip"][2][:2]
+    assert not label.any() and faces[0] == LONG_STRIP
+    v, t, (label, faces, _, _, _), _, _ = large["both_with_dirt"]
+    roots = np.flatnonzero((label == np.arange(len(v))) & (faces > 0))
+    assert len(roots) == SINGLES + 1 and faces.max() == LONG_STRIP and np.isnan(v).any(1).sum() > 1900
+    assert (faces[len(v) - 1000:] == 0).all() and (label[len(v) - 1000:] == np.arange(len(v) - 1000, len(v))).all()
+
+
+@pytest.mark.parametrize("name", list(LARGE))
+def test_large_components_against_the_model(cuda, large, name):
+    from mi3d import mesh
+    v, t, (rl, rf, rmin, rmax, bad), gv, gt = large[name]
+    outs = [mesh._label_components(gv, gt) for _ in range(2)]          # the entry point itself: a bad index is counted
+    label, faces, bmin, bmax, counts = outs[0]
+    assert np.array_equal(label.cpu().numpy(), rl)
+    assert np.array_equal(faces.cpu().numpy(), rf)
+    assert bmin.cpu().numpy().tobytes() == rmin.tobytes() and bmax.cpu().numpy().tobytes() == rmax.tobytes()
+    counts = counts.tolist()
+    top = int(rf.max())
+    assert counts[2] == bad and counts[3] == 0 and counts[5] == int((rf > 0).sum())
+    assert counts[4] == (top << 32) | (~int(np.flatnonzero(rf == top)[0]) & 0xFFFFFFFF)
+    for a, b in zip(outs[0], outs[1]):                                 # a second call, the same bytes
+        assert a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes()
+    if bad == 0:                                                       # and the checked front door agrees
+        for a, b in zip(mesh.components(gv, gt), outs[0][:4]):
+            assert a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes()
+    else:
+        from mi3d import _lib
+        with pytest.raises(_lib.Mi3dError, match=rf"\b{bad} of the {len(t)} triangles"):
+            mesh.components(gv, gt)
+
+
+def clean_through_the_abi(gv, gt, min_faces, min_diagonal, largest):
+    """mi3d.mesh._clean without its refusal of bad indices: (vertices, triangles, vertex_map, counts after the count pass,
+    counts after the emit pass)."""
+    import torch
+    from mi3d import _lib, mesh
+    nv, nt, p = len(gv), len(gt), _lib.ptr
+    label, faces, bmin, bmax, counts = mesh._label_components(gv, gt)
+    need = int(_lib.lib().mi3d_mesh_components_workspace(nv, nt))
+    ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=gv.device)
+    _lib.launch("mi3d_mesh_clean_count", gv, p(gt), nv, nt, p(label), p(faces), p(bmin), p(bmax), min_faces, min_diagonal,
+                int(largest), p(ws), need, p(counts))
+    host = counts.tolist()
+    out_v = torch.empty(host[0], 3, dtype=torch.float32, device=gv.device)
+    out_t = torch.empty(host[1], 3, dtype=torch.int32, device=gv.device)
+    vmap = torch.empty(nv, dtype=torch.int32, device=gv.device)
+    _lib.launch("mi3d_mesh_clean_emit", gv, p(gv), nv, p(gt), nt, p(label), p(ws), need, p(counts), p(out_v), host[0],
+                p(out_t), host[1], p(vmap))
+    return out_v, out_t, vmap, host, counts.tolist()
+
+
+@pytest.mark.parametrize("name", list(LARGE))
+def test_large_clean_against_the_model(cuda, large, name):
+    import torch
+    from mi3d import mesh
+    v, t, comps, gv, gt = large[name]
+    label, faces, bmin, bmax, bad = comps
+    roots = np.flatnonzero((label == np.arange(len(v))) & (faces > 0))
+    d2 = M.diag2(bmin[roots], bmax[roots])
+    md = float(np.sqrt(np.float32(np.median(d2[np.isfinite(d2) & (d2 > 0)])), dtype=np.float32))
+    both_sides = lambda keep: bool(keep[:SCAN_PASS].any() and keep[SCAN_PASS:].any())      # noqa: E731
+    crossed = set()
+    for min_faces, min_diagonal, largest in ((2, 0.0, False), (0, 0.0, True), (0, md, False)):
+        what = f"{name} min_faces={min_faces} min_diagonal={min_diagonal!r} largest={largest}"
+        rv, rt, rmap, rbad = M.clean(v, t, min_faces, min_diagonal, largest, comps=comps)
+        cv, ct, cmap, counted, emitted = clean_through_the_abi(gv, gt, min_faces, min_diagonal, largest)
+        assert counted[:4] == [len(rv), len(rt), rbad, 0] and rbad == bad and emitted[6] == 0, what
+        assert cv.cpu().numpy().tobytes() == rv.tobytes(), what              # bit for bit, NaNs too, in the original order
+        assert np.array_equal(ct.cpu().numpy(), rt) and np.array_equal(cmap.cpu().numpy(), rmap), what
+        cv2, ct2, cmap2, _, _ = clean_through_the_abi(gv, gt, min_faces, min_diagonal, largest)
+        assert cv2.cpu().numpy().tobytes() == cv.cpu().numpy().tobytes(), what
+        assert torch.equal(ct2, ct) and torch.equal(cmap2, cmap), what
+        if bad == 0:
+            for a, b in zip(mesh.clean(gv, gt, min_faces, min_diagonal, largest), (cv, ct, cmap)):
+                assert a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes(), what
+        # kept AND dropped elements on both sides of the first scan round's end: the base carried over is neither 0 nor
+        # the round's size
+        keep_v, keep_t = rmap >= 0, np.zeros(len(t), bool)
+        ok = M.valid_triangles(t, len(v))
+        keep_t[ok] = keep_v[t[ok, 0]]
+        if both_sides(keep_v) and both_sides(~keep_v):
+            crossed.add("v")
+        if len(t) > SCAN_PASS and both_sides(keep_t) and both_sides(~keep_t):
+            crossed.add("t")
+        print(f"[clean] {what}: kept {len(rv)} of {len(v)} vertices, {len(rt)} of {len(t)} triangles")
+    assert crossed == {"many_singles": {"v"}, "long_strip": set(), "both_with_dirt": {"v", "t"}}[name]
+    if name == "long_strip":                                   # all or nothing: the base equals the round's size
+        assert len(M.clean(v, t, 2, 0.0, False, comps=comps)[1]) == LONG_STRIP > SCAN_PASS
 
 
 # ------------------------------------------------------------------------------------------------ bad indices, the C ABI

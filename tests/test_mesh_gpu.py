@@ -73,8 +73,58 @@ def vol_h(rest):
     return v, 0.25, INDEX_FRAME
 
 
+MC_BLOCK = 256                # kBlock of csrc/mesh.hip: grid points per workgroup of k_mc_count / k_mc_vertices / k_mc_triangles
+MC_SCAN_ROUND = 1024          # block sums per round of k_mc_scan (its `b0 += 1024`, launch_bounds 1024)
+FIRST_ROUND = MC_SCAN_ROUND * MC_BLOCK       # grid points whose block offsets the scan's first round makes
+
+
+def _ball(shape, centre, r0):
+    """r0 - distance to `centre`, both in grid units (the index frame)."""
+    i, j, k = np.meshgrid(*[np.arange(n, dtype=np.float64) for n in shape], indexing="ij")
+    return (r0 - np.sqrt((i - centre[0]) ** 2 + (j - centre[1]) ** 2 + (k - centre[2]) ** 2)).astype(np.float32)
+
+
+def vol_i():
+    """65 x 64 x 64 = 266 240 points, 1040 blocks: the blocks of the second scan round are the plane i = 64, whose points own
+    only edges inside that plane and no cell.  The ball is pushed so far towards high i that this plane cuts it: a cap
+    is missing, the cut's rim consists of vertices owned by blocks >= 1024."""
+    return _ball((65, 64, 64), (59.3, 31.4, 30.7), 10.2), 0.0, INDEX_FRAME
+
+
+def vol_j():
+    """A closed ball across the round boundary, which needs more planes behind it: 72 x 64 x 64 = 1152 blocks, the surface
+    spans i = 54.7 .. 69.9 - vertices and triangles on both sides of block 1024, so the second round's offsets start
+    from a base that is not 0."""
+    return _ball((72, 64, 64), (62.3, 31.4, 30.7), 7.6), 0.0, INDEX_FRAME
+
+
+def vol_k():
+    """3 x 300 x 300 = 270 000 points, 1055 blocks, a ragged second round; crossings everywhere.  (Coordinates above 256
+    carry 15 fraction bits, so a vertex may round onto a grid point and meet a neighbour there: with this seed none does,
+    which test_vertices_are_welded needs.)"""
+    return np.random.default_rng(1).random((3, 300, 300), dtype=np.float32), 0.5, INDEX_FRAME
+
+
 VOLUMES = {"a": vol_a, "b": vol_b, "c": vol_c, "d": vol_d, "e": vol_e, "f": vol_f, "g": vol_g,
-           "h_below": lambda: vol_h(-1.0), "h_above": lambda: vol_h(1.0)}
+           "h_below": lambda: vol_h(-1.0), "h_above": lambda: vol_h(1.0), "i": vol_i, "j": vol_j, "k": vol_k}
+SECOND_ROUND = ("i", "j", "k")
+
+
+def owned_elements(vol, iso, first, last=None):
+    """(vertices, triangles) the grid points with linear index in [first, last) own, counted from the volume alone: crossing
+    edges towards +axis, and the non-trivial cells they are the min corner of (a trivial cell has all corners on one side)."""
+    ins = (vol >= iso).reshape(vol.shape)
+    lin = np.arange(vol.size).reshape(vol.shape)
+    sel = (lin >= first) & (lin < (vol.size if last is None else last))
+    nv = 0
+    for axis in range(3):
+        lo, hi = [slice(None)] * 3, [slice(None)] * 3
+        lo[axis], hi[axis] = slice(0, -1), slice(1, None)
+        nv += int(((ins[tuple(lo)] != ins[tuple(hi)]) & sel[tuple(lo)]).sum())
+    corners = sum(ins[a:ins.shape[0] - 1 + a, b:ins.shape[1] - 1 + b, c:ins.shape[2] - 1 + c].astype(np.int64)
+                  for a in (0, 1) for b in (0, 1) for c in (0, 1))
+    cells = int((((corners > 0) & (corners < 8)) & sel[:-1, :-1, :-1]).sum())
+    return nv, cells
 
 
 def run_gpu(cuda, vol, iso, frame):
@@ -120,7 +170,25 @@ def test_against_the_restatement_bitwise_and_in_order(cuda, meshes, name):
     assert v2.tobytes() == v.tobytes() and t2.tobytes() == t.tobytes()
 
 
-@pytest.mark.parametrize("name,euler", [("a", 2), ("b", 0), ("c", 4)])
+@pytest.mark.parametrize("name", SECOND_ROUND)
+def test_the_large_volumes_reach_the_second_scan_round(name):
+    """The block count is the library's own (mi3d_mc_workspace: u64 + u32 per block, padded, and u32 per point); what lies
+    behind the first round is counted from the volume, not taken from the kernels."""
+    from mi3d import _lib
+    vol, iso, _ = VOLUMES[name]()
+    nb = -(-vol.size // MC_BLOCK)
+    assert int(_lib.lib().mi3d_mc_workspace(*vol.shape)) == nb * 8 + (nb + 1) // 2 * 8 + vol.size * 4
+    assert MC_SCAN_ROUND < nb < 2 * MC_SCAN_ROUND and vol.size > FIRST_ROUND
+    early, late = owned_elements(vol, iso, 0, FIRST_ROUND), owned_elements(vol, iso, FIRST_ROUND)
+    print(f"[mesh] {name}: {nb} blocks; first round owns {early} (vertices, cells with triangles), later rounds {late}")
+    # a base to carry, and vertices to place by it ("i": the rim of the cut, a circle of 2 pi sqrt(10.2^2 - 4.7^2) = 57 grid
+    # units in the plane i = 64, crosses more edges than that)
+    assert early[0] > 100 and early[1] > 100 and late[0] > (57 if name == "i" else 100)
+    if name == "j":
+        assert late[1] > 100                                                     # and triangles
+
+
+@pytest.mark.parametrize("name,euler", [("a", 2), ("b", 0), ("c", 4), ("j", 2)])
 def test_closed_surfaces(meshes, name, euler):
     _, _, _, v, t = meshes[name]
     E = assert_closed_and_oriented(t)
@@ -138,7 +206,7 @@ def test_sphere_vertices_lie_within_one_spacing_of_the_surface(meshes):
     assert np.all(dist <= frame[1][0])
 
 
-@pytest.mark.parametrize("name", ["d", "e"])
+@pytest.mark.parametrize("name", ["d", "e", "i"])
 def test_open_surfaces_have_their_boundary_on_the_box(meshes, name):
     vol, _, _, v, t = meshes[name]                     # index frame: a vertex has two integer coordinates
     uses = edge_uses(t)
@@ -157,7 +225,7 @@ def test_open_surfaces_have_their_boundary_on_the_box(meshes, name):
     assert once > 0
 
 
-@pytest.mark.parametrize("name", ["a", "b", "c", "d", "e", "g"])
+@pytest.mark.parametrize("name", ["a", "b", "c", "d", "e", "g", "i", "j", "k"])
 def test_vertices_are_welded(meshes, name):
     _, _, _, v, t = meshes[name]
     assert len(np.unique(v, axis=0)) == len(v)

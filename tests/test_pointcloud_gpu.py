@@ -124,17 +124,41 @@ def test_depth2point_matches_the_reference(cuda, case_b):
 
 
 # ---------------------------------------------------------------------------------------------------------- compaction
-@pytest.mark.parametrize("kind", ["random", "zero", "one", "last"])
-def test_unproject_compacts_in_pixel_order(cuda, kind):
+PC_BLOCK = 256                          # kBlock of csrc/pointcloud.hip: pixels per workgroup of k_pc_count / k_pc_unproject
+PC_SCAN_ROUND = 1024                    # workgroup sums per round of k_pc_scan (its `b0 += 1024`, launch_bounds 1024)
+SMALL, LARGE = (70, 67), (520, 513)     # 19 workgroups; 266 760 pixels = 1043 workgroups: a second, ragged scan round
+KINDS = ["random", "zero", "one", "last"]
+COMPACT_CASES = ([pytest.param(*SMALL, k, id=k) for k in KINDS] + [pytest.param(*LARGE, k, id=f"520x513-{k}") for k in KINDS]
+                 + [pytest.param(*LARGE, "late", id="520x513-late")])
+
+
+@pytest.mark.parametrize("H,W,kind", COMPACT_CASES)
+def test_unproject_compacts_in_pixel_order(cuda, H, W, kind):
     import torch
+    from mi3d import _lib
     from mi3d import pointcloud as pc
-    H, W = 70, 67                                      # 4690 pixels: 19 workgroups, the last one partial, W no multiple of 64
+    # SMALL: 4690 pixels, the last workgroup partial, W no multiple of 64.  The workgroup count is the library's own: the
+    # workspace holds one uint32 per workgroup, padded to 8 bytes
+    nb = -(-H * W // PC_BLOCK)
+    assert int(_lib.lib().mi3d_pc_unproject_workspace(H, W)) == (nb * 4 + 7) // 8 * 8
+    if (H, W) == SMALL:
+        assert nb == 19
+    else:
+        assert PC_SCAN_ROUND < nb < 2 * PC_SCAN_ROUND and nb % 64 != 0     # the second round exists and is ragged
     rng = np.random.default_rng(11)
     D = rng.uniform(0.5, 2.0, (H, W))
     mask = {"random": rng.random((H, W)) < 0.4, "zero": np.zeros((H, W), bool), "one": np.ones((H, W), bool),
-            "last": np.zeros((H, W), bool)}[kind]
+            "last": np.zeros((H, W), bool), "late": np.zeros((H, W), bool)}[kind]
     if kind == "last":
         mask[-1, -1] = True
+    if kind == "late":                                 # only image rows that lie wholly in workgroups of the second scan
+        first = -(-PC_SCAN_ROUND * PC_BLOCK // W)      # round: every kept pixel's offset is made there ("random" and "one"
+        assert 0 < first < H - 1                       # have kept pixels in both rounds: they check the base carried over)
+        mask[first:] = rng.random((H - first, W)) < 0.4
+        assert mask.sum() > 1000 and not mask.reshape(-1)[:PC_SCAN_ROUND * PC_BLOCK].any()
+    if (H, W) == LARGE and kind in ("random", "one"):  # kept pixels on both sides of the round boundary
+        flat = mask.reshape(-1)
+        assert flat[:PC_SCAN_ROUND * PC_BLOCK].any() and flat[PC_SCAN_ROUND * PC_BLOCK:].any()
     K = gen.intrinsics(40.0, H, W)
     c2w = gen.look_at([0.4, 0.3, 1.1])
     want = unproject_np(D, K, c2w)[mask.reshape(-1)]

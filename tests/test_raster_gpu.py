@@ -2,7 +2,9 @@
 numpy oracle (oracle/raster_ref.py: refine_utils.py:306-333 with pytorch3d's rasterize_points / alpha_composite
 restated - PARITY UNPINNED for those two, pytorch3d is absent).  Indices bit-exact, squared distances and composited
 features to fp32 rounding, feature gradients against the oracle's closed form; at BASELINE config 5's size (512 x 512,
-half a million points) through properties checked against a brute-force torch evaluation of sampled pixels."""
+half a million points) through properties checked against a brute-force torch evaluation of sampled pixels.  NDC points
+fed to the rasteriser directly cover what the camera's clouds do not reach: more tiles than one round of the tile scan,
+portrait images, discs wider than a tile (the worst-case workspace), the compositor's channel limits, an empty cloud."""
 import numpy as np
 import pytest
 import torch
@@ -28,7 +30,8 @@ def _camera(dev, radius=1.25):
     return torch.linalg.inv(c2w)
 
 
-@pytest.mark.parametrize("H,W,K", [(64, 64, 8), (48, 80, 8), (40, 40, 1), (33, 70, 3)])
+# the last two are portrait: range_y, pix_to_ndc with S1 > S2 on the y axis and the y half of point_bbox
+@pytest.mark.parametrize("H,W,K", [(64, 64, 8), (48, 80, 8), (40, 40, 1), (33, 70, 3), (70, 33, 3), (80, 48, 8)])
 def test_rasterize_and_composite_match_the_oracle(cuda, H, W, K):
     from mi3d import refine
     from oracle import raster_ref as O
@@ -66,6 +69,157 @@ def test_rasterize_and_composite_match_the_oracle(cuda, H, W, K):
     g_o = O.alpha_composite_backward(idx_o, w_o, dout, P)
     scale = np.abs(g_o).max()
     assert np.abs(f.grad.cpu().numpy() - g_o).max() <= 2e-5 * scale
+
+
+TILE_PX = 16             # kTilePx of csrc/raster.hip: a tile is 16 x 16 pixels, one workgroup of k_raster_tiles
+SCAN_ROUND = 1024        # tiles per round of k_raster_scan's single workgroup (its `i0 += 1024`, launch_bounds 1024)
+TILE_CHUNK = 256         # kTileThreads: points of a tile's list k_raster_tiles stages in LDS per round
+
+
+def _tile_of(H, W):
+    """[H, W]: the index of the tile every pixel lies in, and the tile count."""
+    tiles_x, tiles_y = -(-W // TILE_PX), -(-H // TILE_PX)
+    return (np.arange(H)[:, None] // TILE_PX) * tiles_x + np.arange(W)[None, :] // TILE_PX, tiles_x * tiles_y
+
+
+def _centres(H, W):
+    """(xs [W], ys [H]): the NDC point every pixel column / row looks at, as the oracle computes it."""
+    from oracle import raster_ref as O
+    return O.pix_to_ndc(W - 1 - np.arange(W), W, H), O.pix_to_ndc(H - 1 - np.arange(H), H, W)
+
+
+def _against_the_oracle(cuda, ndc, H, W, radius, K):
+    """The assertions of test_rasterize_and_composite_match_the_oracle on NDC points; returns both sides' outputs."""
+    from mi3d import refine
+    from oracle import raster_ref as O
+    got = refine.rasterize_points(T(ndc, cuda), (H, W), radius, K)
+    want = O.rasterize_points(ndc, H, W, radius, K)
+    idx, zbuf, dists = (a.cpu().numpy() for a in got)
+    assert np.array_equal(idx, want[0])
+    np.testing.assert_allclose(dists, want[2], rtol=1e-6, atol=1e-9)
+    np.testing.assert_allclose(zbuf, want[1], rtol=0, atol=0)
+    return got, want
+
+
+def _composite_against_the_oracle(cuda, rng, got, want, P, Cn, radius):
+    """Forward and feature gradient on the given hits, with the bounds of test_rasterize_and_composite_match_the_oracle."""
+    from mi3d import refine
+    from oracle import raster_ref as O
+    idx, _, dists = got
+    idx_o, _, dists_o = want
+    H, W, _ = idx_o.shape
+    feats = rng.uniform(0, 1, (P, Cn)).astype(np.float32)
+    f = T(feats, cuda).requires_grad_(True)
+    out = refine._PointComposite.apply(f, idx, dists, float(radius))
+    img_o, w_o = O.alpha_composite(idx_o, O.point_alphas(dists_o, radius), feats)
+    np.testing.assert_allclose(out.detach().cpu().numpy(), img_o, rtol=1e-5, atol=1e-6)
+    dout = rng.normal(size=(Cn, H, W)).astype(np.float32)
+    out.backward(T(dout, cuda))
+    g_o = O.alpha_composite_backward(idx_o, w_o, dout, P)
+    assert np.abs(g_o).max() > 0
+    assert np.abs(f.grad.cpu().numpy() - g_o).max() <= 2e-5 * np.abs(g_o).max()
+
+
+@pytest.mark.parametrize("H,W", [(528, 512), (512, 528)])
+def test_more_tiles_than_one_round_of_the_scan(cuda, H, W):
+    """1056 tiles: the offsets of tiles 1024 .. 1055 are made in the scan's second round, from the count of everything
+    before them.  Those tiles are the bottom 16 rows (portrait: all of them; landscape: all but their first tile); a
+    block of points is planted on pixel centres there, in front of everything else."""
+    rng = np.random.default_rng(H)
+    tile, n_tiles = _tile_of(H, W)
+    assert SCAN_ROUND < n_tiles < 2 * SCAN_ROUND and n_tiles % 64 != 0           # a second round, ragged
+    P, K, radius = 3000, 8, 2.0 / min(H, W) * 2.0                                 # 2 pixels
+    ndc = np.concatenate([rng.uniform(-1.05, 1.05, (P, 2)), rng.uniform(0.5, 2.0, (P, 1))], 1).astype(np.float32)
+    ys, xs = np.nonzero((tile >= SCAN_ROUND) & (np.arange(H)[:, None] % 5 == 2) & (np.arange(W)[None, :] % 5 == 2))
+    assert len(ys) >= 250 and set(np.unique(tile[ys, xs])) == set(range(SCAN_ROUND, n_tiles))    # every late tile
+    planted = np.arange(100, 100 + len(ys))
+    cx, cy = _centres(H, W)
+    ndc[planted] = np.stack([cx[xs], cy[ys], np.full(len(ys), 0.25, np.float32)], 1)
+    got, want = _against_the_oracle(cuda, ndc, H, W, radius, K)
+    idx = got[0].cpu().numpy()
+    assert np.array_equal(idx[ys, xs, 0], planted)                                # hits in the late tiles, the planted ones
+    early = idx[tile < SCAN_ROUND]
+    assert (early[:, 0] >= 0).mean() > 0.05 and (idx[tile >= SCAN_ROUND][:, 0] >= 0).mean() > 0.05
+    assert (idx[..., 1] >= 0).any()
+
+
+@pytest.mark.parametrize("K", [8, 1])
+@pytest.mark.parametrize("H,W", [(96, 40), (40, 96)])
+def test_discs_wider_than_a_tile(cuda, H, W, K):
+    """A radius of 30 pixels: a disc's bounding box spans up to 5 x 5 tiles (tiles_per_point_max and the multi-tile loops
+    of k_raster_count / k_raster_fill), and a tile's list runs to several rounds of k_raster_tiles.  Agreement with the
+    brute force is the test that the worst-case workspace is enough: a list cut short would lose points.  Then the
+    compositor on these hits, at the register limit C = 32 and at C = 1."""
+    from mi3d import _lib as L
+    rng = np.random.default_rng(H * 10 + K)
+    P = 1500
+    short = min(H, W)
+    radius = 30 * 2.0 / short                              # 30 pixels in NDC of the shorter side, which spans [-1, 1]
+    assert 2 * 30 + 1 > 3 * TILE_PX
+    half_long = max(H, W) / short                          # the longer side spans [-half_long, half_long]
+    # the cloud fills the image's lower three quarters along the long axis and overhangs every other edge by the radius:
+    # discs centred outside the image reach in, and the far quarter is covered by disc edges or not at all
+    along = rng.uniform(-half_long - radius, 0.5 * half_long - radius, P)
+    across = rng.uniform(-1 - radius, 1 + radius, P)
+    xy = np.stack([across, along] if H > W else [along, across], 1)
+    ndc = np.concatenate([xy, rng.uniform(0.5, 2.0, (P, 1))], 1).astype(np.float32)
+    # planted: within a pixel of tile corners, and outside the image by less than the radius along either axis
+    cx, cy = _centres(H, W)
+    px = 2.0 / short
+    # (the corners of the image's far third only: a disc this wide, centred anywhere else, would close the uncovered part)
+    corners = [(ty, tx) for ty in range(TILE_PX, H, TILE_PX) for tx in range(TILE_PX, W, TILE_PX)
+               if max(ty, tx) >= 2 * max(H, W) // 3]
+    assert len(corners) == 4
+    for n, (ty, tx) in enumerate(corners):                 # the corner between pixels (ty - 1, tx - 1) and (ty, tx)
+        mid = np.array([(cx[tx - 1] + cx[tx]) / 2, (cy[ty - 1] + cy[ty]) / 2])
+        ndc[10 + n, :2] = mid + rng.uniform(-1, 1, 2) * px
+    n0 = 10 + len(corners)
+    outside = np.array([[cx[0] + 0.9 * radius, 0.0], [cx[-1] - 0.9 * radius, 0.3], [0.1, cy[0] + 0.9 * radius],
+                        [-0.2, cy[-1] - 0.9 * radius], [cx[0] + 0.99 * radius, cy[0] + 0.1 * radius]], np.float32)
+    ndc[n0:n0 + len(outside), :2] = outside
+    ndc[n0:n0 + len(outside), 2] = 0.25                    # in front of everything: where they reach, slot 0 is theirs
+    ndc[n0 + len(outside), 2] = -0.5                       # one behind the camera
+    ws = int(L.lib().mi3d_points_rasterize_workspace(P, H, W, radius))
+    tiles = _tile_of(H, W)[1]
+    per_point = (ws - (3 * tiles + 4) * 4) // (4 * P)
+    assert per_point >= 25, per_point                      # the worst case: 5 x 5 tiles and more
+    got, want = _against_the_oracle(cuda, ndc, H, W, radius, K)
+    idx_o = want[0]
+    covered = (idx_o[..., 0] >= 0).mean()
+    print(f"{H}x{W} K={K}: {covered:.3f} of the pixels covered, {per_point} list entries per point provided")
+    assert 0.5 < covered < 0.95                            # both outcomes, and the discs' edges cross the image
+    assert all((idx_o == n0 + i).any() for i in range(len(outside))) and not (idx_o == n0 + len(outside)).any()
+    if K > 1:
+        assert (idx_o[..., K - 1] >= 0).mean() > 0.4       # K overflow: more covering points than slots
+    for Cn in (32, 1):
+        _composite_against_the_oracle(cuda, rng, got, want, P, Cn, radius)
+
+
+@pytest.mark.parametrize("H,W,K", [(70, 33, 3)])
+def test_compositor_limits_on_portrait_hits(cuda, H, W, K):
+    """C = 32 (the register limit) and C = 1 on a portrait image; C = 33 and K = 9 are refused; an empty cloud gives -1
+    everywhere."""
+    from mi3d import _lib as L
+    from mi3d import refine
+    rng = np.random.default_rng(3)
+    P, radius = 2000, 2.0 / W * 2.0
+    half = H / W
+    ndc = np.concatenate([rng.uniform(-1.05, 1.05, (P, 1)), rng.uniform(-half * 1.05, half * 1.05, (P, 1)),
+                          rng.uniform(0.5, 2.0, (P, 1))], 1).astype(np.float32)
+    got, want = _against_the_oracle(cuda, ndc, H, W, radius, K)
+    assert (want[0][..., 0] >= 0).mean() > 0.3 and (want[0][H // 2:, :, 0] >= 0).any() and (want[0][:H // 2, :, 0] >= 0).any()
+    for Cn in (32, 1):
+        _composite_against_the_oracle(cuda, rng, got, want, P, Cn, radius)
+    idx, _, dists = got
+    with pytest.raises(L.Mi3dError):
+        refine._PointComposite.apply(torch.rand(P, 33, device=cuda), idx, dists, float(radius))
+    with pytest.raises(L.Mi3dError):
+        refine.rasterize_points(T(ndc, cuda), (H, W), radius, 9)
+    for shape in ((H, W), (33, 70), (512, 528)):
+        e_idx, e_z, e_d = refine.rasterize_points(torch.empty(0, 3, device=cuda), shape, radius, K)
+        assert e_idx.shape == shape + (K,) and bool((e_idx == -1).all() and (e_z == -1).all() and (e_d == -1).all())
+        blank = refine._PointComposite.apply(torch.empty(0, 5, device=cuda), e_idx, e_d, float(radius))
+        assert blank.shape == (5,) + shape and bool((blank == 0).all())
 
 
 def test_render_point_end_to_end_against_the_oracle(cuda):

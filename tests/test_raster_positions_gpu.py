@@ -25,7 +25,8 @@ pytestmark = pytest.mark.gpu
 
 P = 6000
 FOCAL = 1.0 / (2 * np.tan(np.radians(20) / 2))
-CASES = [(64, 64, 8, 19), (33, 70, 3, 19), (40, 40, 1, 19), (64, 64, 8, 3)]
+CASES = [(64, 64, 8, 19), (33, 70, 3, 19), (40, 40, 1, 19), (64, 64, 8, 3),
+         (70, 33, 3, 19)]                       # portrait: k_raster_bwd_points recomputes the pixel centre with H > W
 COINCIDENT, PLANTED, PLANT_DEPTH = 40, slice(300, 330), 0.8     # the planted block sits in front of the shell
 REPORT_PATH = os.path.join(os.environ.get("MI3D_REPORT_DIR") or os.path.join(ROOT, "test_reports"),
                            "refine_positions.json")

@@ -305,17 +305,23 @@ def test_inference_march_composite_loop(cuda, oracle):
     np.testing.assert_allclose(dep.cpu().numpy(), dep_r, rtol=RTOL, atol=1e-5)
 
 
-def test_compact_budget_rounds_kernels_against_oracle(cuda, oracle):
+COMPACT_ROUND = 1024     # rays per round of k_compact_alive_ctl's single workgroup (its `i0 += 1024`, launch_bounds 1024)
+
+
+@pytest.mark.parametrize("N", [600, 2600])
+def test_compact_budget_rounds_kernels_against_oracle(cuda, oracle, N):
     """The four entry points of the budget loop (C ABI Part 1b, second half: mi3d_infer_begin2, mi3d_march_rays_compact_ctl,
     mi3d_composite_rays_compact_ctl, mi3d_compact_alive_ctl2) driven directly, round by round, against the CPU oracle's
     march_rays / composite_rays (raymarching.cu:906-1115 restated): the plan in the control block, the slab packing (one
     slab per ray, slabs tile [0, rows) exactly), every slab row bit-exact, the accumulators, the death rule, the
     order-preserving compaction, the restart point (t_next = the march's own t, which the reference's running sum of
     deltas[:, 1] reproduces to float rounding) and the step cap (the only coverage used to be the
-    end-to-end render comparison)."""
+    end-to-end render comparison).  N = 2600 (the budget scaled with it): the compaction's workgroup goes round three
+    times, the last round ragged, and carries the count of the survivors so far from round to round."""
     import raymarching
     rng = np.random.default_rng(31)
-    N, H, max_steps, budget = 600, 128, 96, 2500
+    H, max_steps, budget = 128, 96, 2500 * N // 600
+    carried = False          # a compaction of more than two rounds with rays dropped in the first and kept in the third
     o, d = make_rays(rng, N)
     aabb = np.array([-1, -1, -1, 1, 1, 1], np.float32)
     nears, fars = oracle.near_far_from_aabb(o, d, aabb)
@@ -386,6 +392,7 @@ def test_compact_budget_rounds_kernels_against_oracle(cuda, oracle):
         assert np.array_equal(t_g[alive_r[keep]], t_next[:n_alive].cpu().numpy()[keep])
         t_r[alive_r[keep]] = t_g[alive_r[keep]]     # (both sides start the next round from the same t)
         raymarching.compact_alive_ctl2(ctl, alive, spare, N, max_steps)
+        carried |= bool(n_alive > 2 * COMPACT_ROUND and not keep[:COMPACT_ROUND].all() and keep[2 * COMPACT_ROUND:].any())
         alive, spare = spare, alive
         alive_r = alive_r[keep]
         done += n_step
@@ -395,6 +402,7 @@ def test_compact_budget_rounds_kernels_against_oracle(cuda, oracle):
         assert np.array_equal(alive[:alive_r.shape[0]].cpu().numpy(), alive_r)                   # compaction keeps the order
     assert rounds >= 3 and done <= max_steps + 0 or alive_r.shape[0] == 0
     assert float(ws_r.max()) > 0.5
+    assert carried == (N > 2 * COMPACT_ROUND)
 
     # a sample buffer smaller than the round needs: the rows are COUNTED in ctl[8], not dropped silently
     ctl, alive = raymarching.infer_begin2(N, cuda, budget, 1, max_steps)
