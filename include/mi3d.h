@@ -794,6 +794,79 @@ int mi3d_mesh_clean_emit(const float *vertices, unsigned long long nv, const int
                          unsigned long long nv_cap, int32_t *out_triangles, unsigned long long nt_cap, int32_t *vertex_map,
                          void *stream);
 
+/* ------------------------------------------------------------------ Part 14: mesh simplification (mesh export) */
+
+/* Vertex clustering (Rossignac-Borrel) of an indexed triangle mesh: every vertex falls into a cell of a uniform lattice,
+ * the vertices of a cell become one vertex at their mean position, triangles that lose a corner or repeat another are
+ * dropped.  One pass over the vertices and one over the triangles; integer atomics only, so the result does not depend on
+ * scheduling: two runs give byte-identical buffers, and a NumPy restatement gives the same bytes.  Projects of this
+ * family expose decimation as a target face count through pymeshlab's edge collapse, which is on no machine this project
+ * builds on: the semantics below are this project's own contract - PARITY UNPINNED.  Added under ABI version 5: new
+ * symbols only.  (Declared ahead of the point-cloud part, like Parts 12 and 13.)
+ *
+ * vertices float[nv][3], triangles int32[nt][3]; nv, nt <= 2^31 - 1.  The lattice: origin_host = 3 floats o (a HOST
+ * pointer read during the call, all finite) and cell (finite, > 0).
+ *   - CLUSTER of a vertex, per axis: g = (v - o) / cell, a binary32 subtraction and a binary32 division, each rounded on
+ *     its own; c = floorf(g) clamped to [-2^30, 2^30 - 1], an int32.  The cluster is the triple c.  A vertex with a
+ *     non-finite coordinate joins NO cluster and is counted in counts[4].
+ *   - LEADER of a cluster: the smallest vertex index in it.  Found with an open-addressing table whose slots hold a
+ *     vertex index (-1: empty): atomicCAS claims an empty slot; a thread that meets an occupied slot recomputes the
+ *     cluster of the vertex stored there from the read-only input and, if it equals its own, lowers the slot by atomicMin
+ *     and is done, else probes the next slot.  A slot is only ever replaced by a vertex of the same cluster: its key
+ *     never changes.  No key is packed; the clamp is the only limit on c.  The hash function is not part of the contract.
+ *   - POSITION of a cluster: per member and axis f = g - (float)c in binary32, taken into [0, 1] (this moves nothing
+ *     unless c was clamped), q = (int64)floorf(f * 2^20).  S = sum of q and n = the member count are accumulated in the
+ *     leader's row by 64-bit integer atomics.  The new coordinate is (float)(o + cell * (c + (S / n) * 2^-20)) with o,
+ *     cell, c, S, n converted to binary64, every operation a separately rounded binary64 one (no fused multiply-add) and
+ *     ONE final rounding to binary32.  It does not depend on the order in which the atomics land.  It lies in the
+ *     cluster's cell (up to that final rounding), not on the original surface.
+ *   - TRIANGLES: every corner is replaced by its cluster.  A triangle with an index outside [0, nv) is never
+ *     dereferenced; it and a triangle that cites a vertex without a cluster are COUNTED in counts[2] and dropped.  A
+ *     triangle with two corners in one cluster is DEGENERATE: dropped, counts[6].  Two triangles are DUPLICATES iff their
+ *     three clusters are the same SET, whatever the orientation: of each such set the smallest triangle index survives,
+ *     with its own corner order; the others are dropped, counts[7].  Found with a second table of the same kind: a slot
+ *     holds a triangle index, its key is re-derived from the leaders of the stored triangle's corners, atomicMin on
+ *     equal keys.
+ *   - OUTPUT: a cluster is emitted iff a surviving triangle cites it; the emitted clusters in ascending order of their
+ *     LEADER index, the surviving triangles in ascending original index, renumbered (stable compaction: per-workgroup
+ *     counts, an exclusive scan, an emit - no atomic appends).  vertex_map int32[nv] = the new index of every old
+ *     vertex's cluster, -1 if the cluster was not emitted or the vertex has none.
+ *   - counts (device uint64[8], 8-byte aligned): [0] emitted vertices kv, [1] surviving triangles kt, [2] bad triangles,
+ *     [3] threads that GAVE UP, [4] non-finite vertices, [5] clusters (before the uncited ones are dropped),
+ *     [6] degenerate triangles, [7] duplicate triangles.  kt + counts[6] + counts[7] + counts[2] == nt always.
+ *   - GIVING UP: every probe sequence ends after at most `capacity` steps; no thread waits for another.  A thread that
+ *     runs out adds to counts[3] and leaves: a non-zero counts[3] means the result is invalid - an error for the caller
+ *     to raise, never a hang.
+ *   - NON-MANIFOLD OUTPUT: clustering can join sheets that did not touch: edges with more than two triangles and
+ *     vertices whose triangles form more than one fan are legal output.  Nothing repairs them.
+ *
+ *   mi3d_mesh_simplify_workspace  host only: bytes of device scratch for a mesh of this size (0 for nv = nt = 0 and for
+ *                          sizes out of range).  tight = 0: the recommended size, table capacities = twice the smallest
+ *                          power of two above the element count (at most 2^31), a load below one half; tight != 0: the
+ *                          minimum, capacities = the smallest power of two above the element count.  A call uses the
+ *                          recommended capacities if ws_bytes holds them, else the tight ones: the largest powers of two
+ *                          that fit.  The result does not depend on the capacity.
+ *   mi3d_mesh_simplify_count   everything above but the output buffers: tables and accumulators initialised in-stream,
+ *                          counts zeroed in-stream and filled.  The caller reads counts ONCE here to size the outputs and
+ *                          to see [2], [3] and [4] - the only host read of a simplification.  Called alone it answers
+ *                          "how many faces would this cell leave".
+ *   mi3d_mesh_simplify_emit    out_vertices float[nv_cap][3], out_triangles int32[nt_cap][3], vertex_map int32[nv].
+ *                          Nothing is written past the caps; what could not be placed is counted in *lost (device
+ *                          uint64, 8-byte aligned, zeroed in-stream).
+ * count and emit of one simplification go to the same stream, in this order, with the same mesh, lattice, ws and
+ * ws_bytes.  No entry point allocates or synchronises.  nv = nt = 0 launches nothing and succeeds; nt = 0 or nv = 0 alone
+ * is served (nothing is emitted; every triangle is bad).  Sizes out of range, a cell that is not finite and > 0, a
+ * non-finite origin, a workspace below the tight size or not 8-byte aligned and every NULL pointer that would be
+ * dereferenced are refused (hipErrorInvalidValue) and launch nothing. */
+size_t mi3d_mesh_simplify_workspace(unsigned long long nv, unsigned long long nt, int tight);
+int mi3d_mesh_simplify_count(const float *vertices, unsigned long long nv, const int32_t *triangles, unsigned long long nt,
+                             const float *origin_host, float cell, void *ws, size_t ws_bytes, unsigned long long *counts,
+                             void *stream);
+int mi3d_mesh_simplify_emit(const float *vertices, unsigned long long nv, const int32_t *triangles, unsigned long long nt,
+                            const float *origin_host, float cell, void *ws, size_t ws_bytes, float *out_vertices,
+                            unsigned long long nv_cap, int32_t *out_triangles, unsigned long long nt_cap,
+                            int32_t *vertex_map, unsigned long long *lost, void *stream);
+
 /* ------------------------------------------------------------------ Part 11: the refine stage's point cloud */
 
 /* Depth / mask / rgb views -> the coloured point cloud the refine stage starts from: what `depth2point`,

@@ -23,6 +23,7 @@ UNITS = [
     ("raster.hip", ["-ffp-contract=off"]),
     ("mesh.hip", ["-ffp-contract=off"]),
     ("meshclean.hip", ["-ffp-contract=off"]),
+    ("meshsimplify.hip", ["-ffp-contract=off"]),
     ("texture.hip", ["-ffp-contract=off"]),
     ("groupnorm.hip", []),
     ("pointcloud.hip", ["-ffp-contract=off"]),

@@ -112,6 +112,10 @@ _SIGNATURES = {
     "mi3d_mesh_components": [vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, vp, vp],
     "mi3d_mesh_clean_count": [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, u32, f32, i32, vp, C.c_size_t, vp, vp],
     "mi3d_mesh_clean_emit": [vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_size_t, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp],
+    # Part 14 -----------------------------------------------------------------------------------------
+    "mi3d_mesh_simplify_count": [vp, C.c_uint64, vp, C.c_uint64, vp, f32, vp, C.c_size_t, vp, vp],
+    "mi3d_mesh_simplify_emit": [vp, C.c_uint64, vp, C.c_uint64, vp, f32, vp, C.c_size_t, vp, C.c_uint64, vp, C.c_uint64,
+                                vp, vp, vp],
 }
 
 # host-only queries whose return value is not a hipError_t: (argtypes, restype), bound in lib() like the block below
@@ -124,6 +128,7 @@ _LATE_SIGNATURES = {
     "mi3d_groupnorm_nhwc_spans": ([u32, u32, u32], u32),
     "mi3d_pc_unproject_workspace": ([u32, u32], C.c_size_t),
     "mi3d_mesh_components_workspace": ([C.c_uint64, C.c_uint64], C.c_size_t),
+    "mi3d_mesh_simplify_workspace": ([C.c_uint64, C.c_uint64, C.c_int], C.c_size_t),
 }
 
 

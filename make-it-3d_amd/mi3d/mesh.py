@@ -10,6 +10,9 @@
                    mesh - label, face count and bounding box of each - by a lock-free union-find on the device
   clean            drops the components below `min_faces` / `min_diagonal` (or all but the largest): stable compaction
                    on the device; the host reads the counts once to size the outputs
+  simplify         the kernels of csrc/meshsimplify.hip (include/mi3d.h Part 14): vertex clustering on a uniform lattice -
+                   one vertex per occupied cell, degenerate and duplicate triangles dropped; the host reads the counts
+                   once to size the outputs
   bake_texture     the kernels of csrc/texture.hip (include/mi3d.h Part 9): a texel patch per triangle, the field's albedo
                    at every texel's surface point, packed to 8-bit RGB on the device
   export           volume -> surface -> per-vertex albedo (-> texture) -> files; what `NeRFRenderer.export_mesh` calls
@@ -168,6 +171,151 @@ def clean(vertices, triangles, min_faces=0, min_diagonal=0.0, largest=False):
     vertices, triangles = _check_mesh(vertices, triangles)
     min_faces, min_diagonal, largest = _check_keep_rule(min_faces, min_diagonal, largest)
     return _clean(vertices, triangles, min_faces, min_diagonal, largest)[:3]
+
+
+# decimate factors (cluster cell in grid steps) export_mesh tries for `target_faces`, from the fine end; multiples of 0.5
+DECIMATE_LADDER = (1.5, 2, 2.5, 3, 3.5, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 32, 40, 48, 56, 64)
+SIMPLIFY_COUNTS = ("vertices", "triangles", "bad_triangles", "gave_up", "non_finite_vertices", "clusters", "degenerate",
+                   "duplicate")                              # counts[0 .. 7] of include/mi3d.h Part 14
+
+
+def _check_positive(x, name):
+    """A finite number > 0 that is still finite and > 0 as a binary32; returns it as a float."""
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+        raise Mi3dError(f"{name} must be a number (got {x!r})")
+    with np.errstate(over="ignore"):
+        x32 = float(np.float32(x))
+    if not (np.isfinite(x32) and x32 > 0.0):
+        raise Mi3dError(f"{name} must be finite and > 0, as a float32 too (got {x!r})")
+    return float(x)
+
+
+def _simplify_count(vertices, triangles, origin, cell):
+    """mi3d_mesh_simplify_count on the current stream and the one host read: (state for _simplify_emit, counts as a
+    list).  `origin` 3 floats, `cell` a float; both are rounded to binary32 here."""
+    nv, nt, dev = int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
+    ws_bytes = int(_lib.lib().mi3d_mesh_simplify_workspace(nv, nt, 0))
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    org = (C.c_float * 3)(*[float(o) for o in origin])
+    cell = float(np.float32(cell))
+    _lib.launch("mi3d_mesh_simplify_count", vertices, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, org, cell,
+                _lib.ptr(ws), ws_bytes, _lib.ptr(counts))
+    host = counts.tolist()                                   # the one host read a simplification needs
+    if host[3] != 0:
+        raise Mi3dError(f"mesh simplify: {host[3]} threads gave up after probing every slot of a table (the result is "
+                        f"invalid: a bug, or the buffers changed during the call)")
+    return (ws, ws_bytes, org, cell), host
+
+
+def _simplify_emit(vertices, triangles, state, host):
+    nv, nt, dev = int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
+    ws, ws_bytes, org, cell = state
+    kv, kt = host[:2]
+    out_v = torch.empty(kv, 3, dtype=torch.float32, device=dev)
+    out_t = torch.empty(kt, 3, dtype=torch.int32, device=dev)
+    vertex_map = torch.empty(nv, dtype=torch.int32, device=dev)
+    lost = torch.empty(1, dtype=torch.int64, device=dev)
+    _lib.launch("mi3d_mesh_simplify_emit", vertices, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, org, cell,
+                _lib.ptr(ws), ws_bytes, _lib.ptr(out_v), kv, _lib.ptr(out_t), kt, _lib.ptr(vertex_map), _lib.ptr(lost))
+    return out_v, out_t, vertex_map
+
+
+def _check_simplify_counts(host, nv, nt):
+    """Refuses what include/mi3d.h Part 14 counts instead of dropping silently."""
+    if host[4] != 0 or host[2] != 0:
+        raise Mi3dError(f"mesh simplify: {host[4]} of the {nv} vertices have a non-finite coordinate and {host[2]} of the "
+                        f"{nt} triangles hold a vertex index outside [0, {nv}) or cite such a vertex")
+
+
+def simplify(vertices, triangles, cell, origin=None, return_stats=False):
+    """Vertex clustering by the contract of include/mi3d.h Part 14: the vertices in one cell of the lattice `origin` +
+    `cell` * Z^3 become one vertex at their mean position; triangles that lose a corner (degenerate) or repeat an earlier
+    one's three clusters (duplicate) are dropped.  vertices float32 [nv, 3], triangles int32 [nt, 3] on the GPU; `cell` a
+    finite number > 0 (checked first, on any device); `origin` 3 numbers, None: the smallest finite coordinate per axis
+    (`vertices.amin(0)`).  Returns (vertices [kv, 3], triangles [kt, 3], vertex_map int32 [nv]) on the same device - the
+    clusters a surviving triangle cites in ascending order of their smallest member, the surviving triangles in their
+    original order, renumbered; vertex_map is the new index of every old vertex's cluster, -1 where it was dropped - and,
+    with `return_stats=True`, a dict of the counts named in SIMPLIFY_COUNTS.  Nothing surviving gives [0, 3] tensors.
+    The output may have non-manifold edges and vertices; nothing repairs them.  A triangle index outside [0, nv) or a
+    non-finite vertex raises Mi3dError."""
+    cell = _check_positive(cell, "cell")
+    vertices, triangles = _check_mesh(vertices, triangles)
+    nv, nt, dev = int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
+    if origin is None:
+        if nv:
+            inf = torch.full_like(vertices, float("inf"))
+            lo = torch.where(torch.isfinite(vertices), vertices, inf).amin(0)
+            origin = [o if np.isfinite(o) else 0.0 for o in lo.tolist()]
+        else:
+            origin = [0.0, 0.0, 0.0]
+    else:
+        origin = [float(o) for o in np.asarray(origin, dtype=np.float32).reshape(-1)]
+        if len(origin) != 3 or not all(np.isfinite(o) for o in origin):
+            raise Mi3dError(f"origin must be 3 finite numbers (got {origin!r})")
+    if nv == 0 and nt == 0:
+        out = (vertices.new_empty(0, 3), triangles.new_empty(0, 3), torch.empty(0, dtype=torch.int32, device=dev))
+        return out + (dict(zip(SIMPLIFY_COUNTS, [0] * 8)),) if return_stats else out
+    state, host = _simplify_count(vertices, triangles, origin, cell)
+    _check_simplify_counts(host, nv, nt)
+    out = _simplify_emit(vertices, triangles, state, host)
+    return out + (dict(zip(SIMPLIFY_COUNTS, host)),) if return_stats else out
+
+
+def export_lattice(R, d):
+    """The lattice export_mesh clusters on for `decimate=d` at resolution R: (origin, cell) as binary32 values.  The cell
+    is d grid steps h = 2 / (R - 1); the origin lies a QUARTER step below the grid's corner, so that no grid plane - where
+    two of a marching-cubes vertex's three coordinates lie exactly - meets a cell boundary for any d that is a multiple
+    of 0.5, and rounding noise decides no cluster."""
+    h = 2.0 / (R - 1)
+    o = np.float32(-1.0) - np.float32(h) / np.float32(4.0)
+    return (float(o),) * 3, float(np.float32(d * h))
+
+
+def _check_decimate(decimate, target_faces):
+    if decimate is not None and target_faces is not None:
+        raise Mi3dError("decimate and target_faces are mutually exclusive: give one of them")
+    if decimate is not None:
+        decimate = _check_positive(decimate, "decimate")
+    if target_faces is not None:
+        if isinstance(target_faces, (bool, np.bool_)) or not isinstance(target_faces, (int, np.integer)):
+            raise Mi3dError(f"target_faces must be an integer (got {target_faces!r})")
+        if int(target_faces) < 1:
+            raise Mi3dError(f"target_faces must be >= 1 (got {target_faces})")
+        target_faces = int(target_faces)
+    return decimate, target_faces
+
+
+def _decimate(vertices, triangles, R, decimate, target_faces):
+    """export's simplify step: `decimate=d` clusters at d grid steps; `target_faces=N` walks DECIMATE_LADDER from the fine
+    end with the count phase alone (one host read per rung) and emits the first rung with at most N faces."""
+    nv, nt = int(vertices.shape[0]), int(triangles.shape[0])
+    if target_faces is not None:
+        if nt <= target_faces:
+            return vertices, triangles
+        left = nt
+        for d in DECIMATE_LADDER:
+            origin, cell = export_lattice(R, d)
+            state, host = _simplify_count(vertices, triangles, origin, cell)
+            _check_simplify_counts(host, nv, nt)
+            if 0 < host[1] <= target_faces:
+                break
+            if host[1] == 0:                                    # no mesh is no answer; coarser cells leave no more
+                raise Mi3dError(f"export_mesh: target_faces={target_faces} is not reached: decimate={d:g} leaves no "
+                                f"triangle, and the rung before it {left} of the {nt}")
+            left = host[1]
+        else:
+            raise Mi3dError(f"export_mesh: target_faces={target_faces} is not reached: decimate={DECIMATE_LADDER[-1]}, "
+                            f"the coarsest rung, leaves {left} of the {nt} triangles")
+    else:
+        d = decimate
+        origin, cell = export_lattice(R, d)
+        state, host = _simplify_count(vertices, triangles, origin, cell)
+        _check_simplify_counts(host, nv, nt)
+    if host[0] == 0 or host[1] == 0:
+        raise Mi3dError(f"export_mesh: nothing survives decimate={d:g}: the {nv} vertices fall into {host[5]} clusters, "
+                        f"{host[6]} of the {nt} triangles are degenerate and {host[7]} duplicates")
+    return _simplify_emit(vertices, triangles, state, host)[:2]
 
 
 def _chunks(n):
@@ -384,9 +532,10 @@ def vertex_normals(model, vertices):
 
 
 def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False, min_faces=None,
-           min_diagonal=None, largest=False):
+           min_diagonal=None, largest=False, decimate=None, target_faces=None):
     """What NeRFRenderer.export_mesh does (see there).  `S` only sizes the reference's chunks and is ignored."""
     del S
+    decimate, target_faces = _check_decimate(decimate, target_faces)
     cleaning = min_faces is not None or min_diagonal is not None or largest is not False
     if cleaning:
         rule = _check_keep_rule(0 if min_faces is None else min_faces, 0.0 if min_diagonal is None else min_diagonal,
@@ -414,6 +563,8 @@ def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, norma
                 raise Mi3dError(f"export_mesh: nothing survives min_faces={rule[0]}, min_diagonal={rule[1]:g}, "
                                 f"largest={rule[2]}: the surface has {counts[5]} components, the largest of "
                                 f"{counts[4] >> 32} triangles ({nv0} vertices, {nt0} triangles in all)")
+        if decimate is not None or target_faces is not None:    # after the floater filter, which sees the original mesh
+            vertices, triangles = _decimate(vertices, triangles, R, decimate, target_faces)
         if texture_size is not None:
             _fitting_cell(triangles.shape[0], texture_size)     # refuse before the field is evaluated anywhere
         albedo = vertex_albedo(model, vertices)

@@ -118,7 +118,7 @@ class NeRFRenderer(nn.Module):
 
     @torch.no_grad()
     def export_mesh(self, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False, min_faces=None,
-                    min_diagonal=None, largest=False):
+                    min_diagonal=None, largest=False, decimate=None, target_faces=None):
         """renderer.py:157-191 + the file writing of :300-328, reached through main.py's `--save_mesh`: sigma on the
         `resolution`^3 lattice of [-1, 1]^3 (default grid_size), marching cubes at min(mean_density, density_thresh)
         (density_thresh without cuda_ray) on the GPU (mi3d.mesh), `<path>/mesh.obj` + `mesh.mtl`.  By default
@@ -138,10 +138,17 @@ class NeRFRenderer(nn.Module):
         `largest=True` only the one with the most triangles; the atlas, the colours and the normals are those of the
         cleaned mesh and the returned tuples keep their shapes.  Nothing surviving raises Mi3dError naming the component
         count and the largest component.  With all three at their defaults nothing of this runs and the files are byte
-        for byte what they were without the arguments."""
+        for byte what they were without the arguments.  `decimate=d` (a finite number > 0) simplifies the mesh by vertex
+        clustering (mesh.simplify, include/mi3d.h Part 14) after the floater filter and before the atlas,
+        the colours and the normals: the vertices in one cell of d grid steps become one vertex, degenerate and duplicate
+        triangles go; `target_faces=N` (an integer >= 1) instead takes the finest d of mesh.DECIMATE_LADDER that leaves at
+        most N faces, keeps a mesh that already has no more, and raises Mi3dError if the coarsest does not get there.
+        The two are mutually exclusive.  Clustering can leave non-manifold edges and vertices.  With both None nothing
+        of this runs and the files are byte for byte what they were without the arguments."""
         from . import mesh
         return mesh.export(self, path, resolution, S, texture_size=texture_size, ssaa=ssaa, normals=normals,
-                           min_faces=min_faces, min_diagonal=min_diagonal, largest=largest)
+                           min_faces=min_faces, min_diagonal=min_diagonal, largest=largest, decimate=decimate,
+                           target_faces=target_faces)
 
     @torch.no_grad()
     def export_point_cloud(self, outputdir, poses, ref_rgb, fov, H, W, **kwargs):
