@@ -37,7 +37,8 @@ extern "C" {
  * (marching cubes), Part 9 (texture baking), Part 10 (GroupNorm), Part 12 (the Canny detector), Part 1's
  * mi3d_composite_rays_train_backward_depth and the hash grid's input gradients (mi3d_hashgrid_backward_input of Part 2,
  * mi3d_grid_points_backward_input of Part 3) and their second-order passes (mi3d_hashgrid_backward_input_backward,
- * mi3d_grid_points_backward_input_backward) were added under 5: new symbols only, nothing existing changed. */
+ * mi3d_grid_points_backward_input_backward) and Parts 11 and 13 to 15 were added under 5: new symbols only, nothing
+ * existing changed. */
 int mi3d_abi_version(void);
 const char *mi3d_last_error_string(int err);
 
@@ -866,6 +867,75 @@ int mi3d_mesh_simplify_emit(const float *vertices, unsigned long long nv, const 
                             const float *origin_host, float cell, void *ws, size_t ws_bytes, float *out_vertices,
                             unsigned long long nv_cap, int32_t *out_triangles, unsigned long long nt_cap,
                             int32_t *vertex_map, unsigned long long *lost, void *stream);
+
+/* ------------------------------------------------------------------ Part 15: texturing from views (mesh export) */
+
+/* Projective texturing of Part 9's atlas: a depth map of the mesh per view, and per atlas sample a visibility-tested,
+ * angle-weighted mean of the views' colours.  The reference bakes the field only (nerf/renderer.py:193-299); this
+ * contract is this project's own - PARITY UNPINNED, the standing of Parts 8, 9, 13 and 14.  Added under ABI version 5:
+ * new symbols only.  (Declared ahead of the point-cloud part, like Parts 12 to 14.)
+ *
+ * ARITHMETIC.  Everything is binary32, every operation rounded separately (no fused multiply-add), three-term sums in
+ * index order k = 0, 1, 2 as ((t0 + t1) + t2), a translation added last.  No sqrt, no transcendental function: cosines
+ * enter as squares.  A NumPy float32 restatement gives the same bits.
+ *   - VIEWS: V in [1, 64] views of one size H x W, each in [2, 16384].  views float[V][24], one record per view:
+ *     [0..8] R row-major and [9..11] t of the world-to-camera matrix [R | t]; [12..20] K row-major (last row 0 0 1);
+ *     [21..23] the camera centre (the translation column of c2w).  The caller inverts c2w in binary64 and rounds once.
+ *   - PROJECTION of a point p: cam_r = ((R_r0 p0 + R_r1 p1) + R_r2 p2) + t_r; q_r = (K_r0 cam0 + K_r1 cam1) + K_r2 cam2;
+ *     x = q0 / q2, y = q1 / q2, z = q2.  Pixel (i, j) - column i of row j - has its centre at (i + 0.5, j + 0.5).
+ *
+ * DEPTH MAP (mi3d_mesh_depth): depth float[V][H][W], +inf where nothing is drawn; counts uint64[2], 8-byte aligned,
+ * zeroed in-stream.  One fill launch, then one launch with thread = (triangle, view).
+ *   - A triangle with an index outside [0, nv) is never dereferenced; it is COUNTED in counts[0], once (not per view).
+ *   - A triangle with a vertex whose z <= 0, or whose x, y or z is not finite, is not drawn in that view and COUNTED in
+ *     counts[1], once per view.  Nothing is clipped at a near plane.
+ *   - The thread walks the pixel centres of the bounding box: columns max(ceil(min x - 0.5), 0) .. min(floor(max x -
+ *     0.5), W - 1), rows likewise; at most H W iterations.
+ *   - EDGE FUNCTION of the directed edge a -> b at a centre P, for vertex indices ia <= ib:
+ *     E = (xb - xa) (Py - ya) - (yb - ya) (Px - xa); for ia > ib the endpoints swap and E is negated (the WATERTIGHT
+ *     rule: two triangles sharing an edge by index see exactly opposite values).  w0, w1, w2 = the edges 1 -> 2, 2 -> 0,
+ *     0 -> 1.  s = (w0 + w1) + w2.  The pixel is covered iff (all w >= 0 or all w <= 0) and s != 0.  No back-face
+ *     culling.
+ *   - DEPTH: d = 1 / (((w0 / s) / z0 + (w1 / s) / z1) + (w2 / s) / z2); written iff 0 < d < inf, by atomicMin on its
+ *     uint32 bits (positive floats order like their bits): order-independent, two runs give identical bytes.
+ *
+ * PROJECTION OF THE VIEWS (mi3d_texture_project): thread = texel of a band of `rows` image rows, the mapping of
+ * mi3d_atlas_positions, whose xyz float[rows T ssaa^2][3] and owner int32[rows T] it reads.  N = (B - A) x (C - A) of
+ * the owner triangle: e1 = B - A, e2 = C - A, N = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x),
+ * nn = (Nx Nx + Ny Ny) + Nz Nz.  For each sample p and v = 0 .. V - 1 in order, view v CONTRIBUTES iff
+ *   (a) z > 0;
+ *   (b) 0.5 <= x <= W - 0.5 and 0.5 <= y <= H - 0.5; gx = x - 0.5, i0 = min(floor(gx), W - 2), fx = gx - i0; the
+ *       same in y (gy, j0, fy); the four taps are (i0 + a, j0 + b), a, b in {0, 1};
+ *   (c) all four depth taps are finite and z <= min(min(d00, d10), min(d01, d11)) + depth_tol  (d_ab at (i0+a, j0+b));
+ *   (d) with masks uint8[V][H][W]: all four mask taps are non-zero;
+ *   (e) with d = centre - p: nd = (Nx dx + Ny dy) + Nz dz > 0, dd = (dx dx + dy dy) + dz dz,
+ *       cos2 = (nd nd) / (nn dd) >= min_cos2.
+ * Its weight is w = weights[v] * cos2^(power / 2), power in {2, 4, 8, 16}, by power / 2 = 1, 2, 4, 8 -> 0 .. 3
+ * squarings of cos2.  Its colour per channel, images float[V][H][W][3]: hx = 1 - fx, hy = 1 - fy,
+ * top = c00 hx + c10 fx, bot = c01 hx + c11 fx, c = top hy + bot fy.  sw = sw + w and sc = sc + w c in view order from 0.
+ * Output per sample: colour = sc / sw if sw > 0 else base[sample] (base float[rows T ssaa^2][3], the layout
+ * mi3d_texture_pack reads); hits uint8 = the number of contributing views (a view of weight 0 counts).  nn == 0 (a
+ * degenerate triangle), a non-finite nn and owner < 0 contribute nothing: base, hits 0.  An owner or a vertex index out
+ * of range is never dereferenced (treated like owner < 0).  No atomics: two runs give identical bytes.
+ *
+ * ERROR AGAINST EXACT ARITHMETIC (what tests/test_texture_views_cpu.py counts; u = 2^-24): a component of cam passes 4
+ * roundings, one of q 4 more, x and y one more each; an edge function 2 subtractions per factor, 2 products and a
+ * subtraction on top of its inputs' errors; N 3 per component on top of the 1 of each edge vector; nd and dd 3 more.
+ * The test propagates these as first-order running bounds and leaves a sample out whose comparison in (b), (c) or (e)
+ * lies within twice the bound.
+ *
+ * No entry point allocates or synchronises.  A NULL pointer other than `masks`, V outside [1, 64], H or W outside
+ * [2, 16384], T or ssaa outside Part 9's ranges, rows outside [1, T], a power outside the set, a min_cos2 outside
+ * [0, 1] and a depth_tol that is negative or not finite are refused (hipErrorInvalidValue) and launch nothing.
+ * mi3d_mesh_depth accepts nt = 0 (the fill alone). */
+int mi3d_mesh_depth(const float *vertices, unsigned long long nv, const int32_t *triangles, unsigned long long nt,
+                    const float *views, uint32_t V, uint32_t H, uint32_t W, float *depth, unsigned long long *counts,
+                    void *stream);
+int mi3d_texture_project(const float *xyz, const int32_t *owner, const float *vertices, unsigned long long nv,
+                         const int32_t *triangles, unsigned long long nt, uint32_t T, uint32_t ssaa, uint32_t rows,
+                         const float *views, uint32_t V, uint32_t H, uint32_t W, const float *depth, const float *images,
+                         const uint8_t *masks, const float *weights, uint32_t power, float min_cos2, float depth_tol,
+                         const float *base, float *colour, uint8_t *hits, void *stream);
 
 /* ------------------------------------------------------------------ Part 11: the refine stage's point cloud */
 

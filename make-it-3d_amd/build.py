@@ -25,6 +25,7 @@ UNITS = [
     ("meshclean.hip", ["-ffp-contract=off"]),
     ("meshsimplify.hip", ["-ffp-contract=off"]),
     ("texture.hip", ["-ffp-contract=off"]),
+    ("textureviews.hip", ["-ffp-contract=off"]),
     ("groupnorm.hip", []),
     ("pointcloud.hip", ["-ffp-contract=off"]),
     ("canny.hip", []),

@@ -116,6 +116,10 @@ _SIGNATURES = {
     "mi3d_mesh_simplify_count": [vp, C.c_uint64, vp, C.c_uint64, vp, f32, vp, C.c_size_t, vp, vp],
     "mi3d_mesh_simplify_emit": [vp, C.c_uint64, vp, C.c_uint64, vp, f32, vp, C.c_size_t, vp, C.c_uint64, vp, C.c_uint64,
                                 vp, vp, vp],
+    # Part 15 -----------------------------------------------------------------------------------------
+    "mi3d_mesh_depth": [vp, C.c_uint64, vp, C.c_uint64, vp, u32, u32, u32, vp, vp, vp],
+    "mi3d_texture_project": [vp, vp, vp, C.c_uint64, vp, C.c_uint64, u32, u32, u32, vp, u32, u32, u32, vp, vp, vp, vp, u32,
+                             f32, f32, vp, vp, vp, vp],
 }
 
 # host-only queries whose return value is not a hipError_t: (argtypes, restype), bound in lib() like the block below

@@ -15,6 +15,9 @@
                    once to size the outputs
   bake_texture     the kernels of csrc/texture.hip (include/mi3d.h Part 9): a texel patch per triangle, the field's albedo
                    at every texel's surface point, packed to 8-bit RGB on the device
+  render_depth     the depth maps of a mesh from V pinhole cameras (csrc/textureviews.hip, include/mi3d.h Part 15)
+  bake_views       the same atlas coloured from views by projection: per sample the visibility-tested, angle-weighted
+                   mean of the views that see it, the field's albedo where none does (Part 15)
   export           volume -> surface -> per-vertex albedo (-> texture) -> files; what `NeRFRenderer.export_mesh` calls
   write_obj        vertex-coloured OBJ (`v x y z r g b`) + the reference's `mat0` material; with UVs `v` / `vt` /
                    `f v/vt` and `map_Kd`; with normals `vn` lines and `f v//vn` / `f v/vt/vn`
@@ -392,16 +395,29 @@ def bake_texture(model, vertices, triangles, texture_size, ssaa=1):
     [3 nt, 2], owner int32 [T, T]) on the same device; image row 0 is the top row, vt of triangle i are rows 3 i .. 3 i + 2.
     The texels are evaluated in bands of image rows of at most CHUNK points; bands below the last owned texel are not."""
     T, ssaa = _check_texture(texture_size, ssaa)
-    vertices = _lib.dev_f32(vertices, "vertices", 3)
-    if not isinstance(triangles, torch.Tensor):
-        raise TypeError("triangles must be a torch.Tensor")
-    triangles = _lib.dev_typed(triangles, "triangles", torch.int32)
-    if vertices.dim() != 2 or triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.device != vertices.device:
-        raise Mi3dError(f"vertices {tuple(vertices.shape)} and triangles {tuple(triangles.shape)} must be [nv, 3] and "
-                        f"[nt, 3] on one device")
+    vertices, triangles = _check_bake_mesh(vertices, triangles, "bake_texture")
+    return _bake_bands(vertices, triangles, T, ssaa, lambda xyz, owner, row0, rows: _field_albedo(model, xyz))
+
+
+def _check_bake_mesh(vertices, triangles, who):
+    vertices, triangles = _check_mesh(vertices, triangles)
+    if vertices.shape[0] == 0 or triangles.shape[0] == 0:
+        raise Mi3dError(f"{who} needs a mesh (got no vertices or no triangles)")
+    return vertices, triangles
+
+
+def _field_albedo(model, xyz):
+    albedo = model.density(xyz)["albedo"].float().contiguous()
+    if albedo.shape != xyz.shape:
+        raise Mi3dError(f"model.density returned albedo {tuple(albedo.shape)} for points {tuple(xyz.shape)}")
+    return albedo
+
+
+def _bake_bands(vertices, triangles, T, ssaa, colour):
+    """The band loop the two bakes share: mi3d_atlas_uv, then per band of image rows mi3d_atlas_positions,
+    `colour(xyz, owner_band, row0, rows)` -> float32 [rows T ssaa^2, 3], and mi3d_texture_pack; the one host read (the
+    bad-triangle counter) at the end.  Returns (image, vt, owner)."""
     nv, nt = int(vertices.shape[0]), int(triangles.shape[0])
-    if nv == 0 or nt == 0:
-        raise Mi3dError("bake_texture needs a mesh (got no vertices or no triangles)")
     c = _fitting_cell(nt, T)
     dev, ss2 = vertices.device, ssaa * ssaa
     vt = torch.empty(3 * nt, 2, dtype=torch.float32, device=dev)
@@ -418,15 +434,203 @@ def bake_texture(model, vertices, triangles, texture_size, ssaa=1):
             xyz = torch.empty(rows * T * ss2, 3, dtype=torch.float32, device=dev)
             _lib.launch("mi3d_atlas_positions", xyz, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, T, ssaa, row0, rows,
                         _lib.ptr(xyz), _lib.ptr(owner[row0]), _lib.ptr(bad))
-            albedo = model.density(xyz)["albedo"].float().contiguous()
-            if albedo.shape != xyz.shape:
-                raise Mi3dError(f"model.density returned albedo {tuple(albedo.shape)} for points {tuple(xyz.shape)}")
+            albedo = colour(xyz, owner[row0:row0 + rows], row0, rows)
             _lib.launch("mi3d_texture_pack", albedo, _lib.ptr(albedo), _lib.ptr(owner[row0]), T, ssaa, rows,
                         _lib.ptr(image[row0]))
     lost = int(bad)                                     # the one host read of a bake
     if lost != 0:
         raise Mi3dError(f"{lost} of the {nt} triangles hold a vertex index outside [0, {nv})")
     return image, vt, owner
+
+
+MIN_VIEW_SIDE, MAX_VIEW_SIDE, MAX_VIEWS = 2, 16384, 64
+POWERS = (2, 4, 8, 16)
+VIEW_KEYS = ("images", "c2w", "K", "masks", "weights", "power", "min_cos", "depth_tol")
+
+
+def _shape(a):
+    return tuple(a.shape) if isinstance(a, torch.Tensor) else tuple(np.shape(a))
+
+
+def _host64(a):
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def view_records(c2w, K):
+    """The float32 [V, 24] view records of include/mi3d.h Part 15 from camera-to-world matrices [V, 4, 4] and the shared
+    intrinsics [3, 3] (last row 0 0 1): per view the rows of [R | t] of the world-to-camera matrix (the NumPy float64
+    inverse, as pointcloud.build takes it), K, and the camera centre, each rounded once."""
+    c2w, K = _host64(c2w), _host64(K)
+    if c2w.ndim != 3 or c2w.shape[1:] != (4, 4) or not 1 <= c2w.shape[0] <= MAX_VIEWS:
+        raise Mi3dError(f"c2w must be [V, 4, 4] with V in [1, {MAX_VIEWS}] (got {c2w.shape})")
+    if K.shape != (3, 3):
+        raise Mi3dError(f"K must be [3, 3] (got {K.shape})")
+    if not (np.isfinite(c2w).all() and np.isfinite(K).all()):
+        raise Mi3dError("c2w and K must be finite")
+    if not np.array_equal(K[2], [0.0, 0.0, 1.0]):
+        raise Mi3dError(f"the last row of K must be 0 0 1 (got {K[2].tolist()})")
+    rec = np.empty((c2w.shape[0], 24), np.float64)
+    for v, pose in enumerate(c2w):
+        try:
+            w2c = np.linalg.inv(pose)
+        except np.linalg.LinAlgError:
+            raise Mi3dError(f"c2w[{v}] is singular") from None
+        rec[v] = np.concatenate([w2c[:3, :3].ravel(), w2c[:3, 3], K.ravel(), pose[:3, 3]])
+    return rec.astype(np.float32)
+
+
+def _check_view_size(V, H, W):
+    if not 1 <= V <= MAX_VIEWS:
+        raise Mi3dError(f"the number of views must lie in [1, {MAX_VIEWS}] (got {V})")
+    if not (MIN_VIEW_SIDE <= H <= MAX_VIEW_SIDE and MIN_VIEW_SIDE <= W <= MAX_VIEW_SIDE):
+        raise Mi3dError(f"H and W must lie in [{MIN_VIEW_SIDE}, {MAX_VIEW_SIDE}] (got {H} x {W})")
+
+
+def _number(x, name, lo, hi):
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+        raise Mi3dError(f"{name} must be a number (got {x!r})")
+    if not lo <= float(x) <= hi:                                # false for NaN
+        raise Mi3dError(f"{name} must lie in [{lo:g}, {hi:g}] (got {x!r})")
+    return float(np.float32(x))
+
+
+def check_views(images, c2w, K, masks=None, weights=None, power=4, min_cos=0.2, depth_tol=0.02):
+    """Every view argument of bake_views, on the host, before anything is uploaded or launched.  Returns (records float32
+    [V, 24], weights float32 [V], min_cos^2 as the binary32 product, depth_tol as a binary32, (V, H, W))."""
+    s = _shape(images)
+    if len(s) != 4 or s[3] != 3:
+        raise Mi3dError(f"images must be [V, H, W, 3] (got {s})")
+    V, H, W = s[:3]
+    _check_view_size(V, H, W)
+    if isinstance(images, torch.Tensor) and not images.dtype.is_floating_point or \
+            not isinstance(images, torch.Tensor) and np.asarray(images).dtype.kind != "f":
+        raise Mi3dError("images must be floating point, in [0, 1]")
+    if _shape(c2w) != (V, 4, 4):
+        raise Mi3dError(f"c2w must be [{V}, 4, 4] for images {s} (got {_shape(c2w)})")
+    records = view_records(c2w, K)
+    if masks is not None and _shape(masks) != (V, H, W):
+        raise Mi3dError(f"masks must be [{V}, {H}, {W}] for images {s} (got {_shape(masks)})")
+    if weights is None:
+        weights = np.ones(V, np.float32)
+    else:
+        if _shape(weights) != (V,):
+            raise Mi3dError(f"weights must be [{V}] for images {s} (got {_shape(weights)})")
+        with np.errstate(over="ignore"):
+            weights = _host64(weights).astype(np.float32)
+        if not (np.isfinite(weights).all() and (weights >= 0).all()):
+            raise Mi3dError(f"weights must be finite and >= 0, as float32 too (got {weights.tolist()})")
+    if isinstance(power, (bool, np.bool_)) or power not in POWERS:
+        raise Mi3dError(f"power must be one of {POWERS} (got {power!r})")
+    min_cos = np.float32(_number(min_cos, "min_cos", 0.0, 1.0))
+    depth_tol = _number(depth_tol, "depth_tol", 0.0, float(np.finfo(np.float32).max))
+    return records, weights, float(min_cos * min_cos), depth_tol, (V, H, W)
+
+
+def _check_views_dict(views):
+    if not isinstance(views, dict):
+        raise Mi3dError(f"views must be a dict with the keys {VIEW_KEYS[:3]} and optionally {VIEW_KEYS[3:]} (got "
+                        f"{type(views).__name__})")
+    unknown = sorted(set(views) - set(VIEW_KEYS))
+    missing = [k for k in VIEW_KEYS[:3] if k not in views]
+    if unknown or missing:
+        raise Mi3dError(f"views: unknown keys {unknown}, missing keys {missing}; it takes {VIEW_KEYS}")
+    check_views(**views)
+    return dict(views)
+
+
+def _to_dev(a, dtype, dev):
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.detach().to(device=dev, dtype=dtype).contiguous()
+
+
+def _mesh_depth(vertices, triangles, records, H, W):
+    """mi3d_mesh_depth on the current stream: (depth float32 [V, H, W], counts int64 [2] on the device)."""
+    dev, V = vertices.device, int(records.shape[0])
+    depth = torch.empty(V, H, W, dtype=torch.float32, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    _lib.launch("mi3d_mesh_depth", vertices, _lib.ptr(vertices), int(vertices.shape[0]), _lib.ptr(triangles),
+                int(triangles.shape[0]), _lib.ptr(records), V, H, W, _lib.ptr(depth), _lib.ptr(counts))
+    return depth, counts
+
+
+def render_depth(vertices, triangles, c2w, K, H, W, return_counts=False):
+    """The depth maps of an indexed mesh from V pinhole cameras (include/mi3d.h Part 15): vertices float32 [nv, 3],
+    triangles int32 [nt, 3] on the GPU; c2w [V, 4, 4] and K [3, 3] as pointcloud.build takes them, pixel centres at
+    half-integers.  Returns depth float32 [V, H, W] on the same device: the camera-space z of the nearest surface at
+    every pixel centre (back faces included), +inf where nothing is drawn.  Nothing is clipped: a triangle with a vertex
+    at z <= 0 is left out of that view.  A triangle index outside [0, nv) raises Mi3dError - unless
+    `return_counts=True`, which returns (depth, {"bad": .., "skipped": ..}) instead: the triangles with such an index,
+    and the (triangle, view) pairs left out."""
+    records = view_records(c2w, K)
+    H, W = int(H), int(W)
+    _check_view_size(records.shape[0], H, W)
+    vertices, triangles = _check_mesh(vertices, triangles)
+    depth, counts = _mesh_depth(vertices, triangles, torch.from_numpy(records).to(vertices.device), H, W)
+    bad, skipped = counts.tolist()
+    if return_counts:
+        return depth, {"bad": bad, "skipped": skipped}
+    if bad != 0:
+        raise Mi3dError(f"{bad} of the {triangles.shape[0]} triangles hold a vertex index outside [0, {vertices.shape[0]})")
+    return depth
+
+
+def bake_views(model_or_base, vertices, triangles, texture_size, images, c2w, K, ssaa=1, masks=None, weights=None,
+               power=4, min_cos=0.2, depth_tol=0.02):
+    """The atlas of bake_texture coloured from VIEWS by projection (include/mi3d.h Part 15): every atlas sample takes the
+    weighted mean of the views that see it - inside the image, not behind a nearer surface of the mesh (the depth maps
+    of render_depth, made once), inside the view's mask, and facing the camera with cos >= `min_cos` - each weighted
+    by weights[v] * cos^power; a sample no view sees keeps the base colour.
+
+    images float [V, H, W, 3] in [0, 1], c2w [V, 4, 4], K [3, 3] (pointcloud.build's conventions; what
+    refine.render_views returns); masks [V, H, W] (non-zero: usable) and weights [V] (finite, >= 0) optional; NumPy or
+    tensors.  `model_or_base`: a model, whose density(xyz)["albedo"] is the base, or a base colour of 3 numbers, or a
+    float32 tensor [T, T, ssaa^2, 3] of per-sample base colours.  vertices and triangles as bake_texture takes them.
+    Returns (image uint8 [T, T, 3], vt float32 [3 nt, 2], owner int32 [T, T], hits uint8 [T, T, ssaa^2]: the number of
+    views that contributed to each sample).  Every argument is checked before anything is uploaded or launched.
+
+    The defaults power=4, min_cos=0.2 and depth_tol=0.02 (in world units, for an object in [-1, 1]^3) are choices
+    nobody has measured against alternatives."""
+    T, ssaa = _check_texture(texture_size, ssaa)
+    records, weights, min_cos2, depth_tol, (V, H, W) = check_views(images, c2w, K, masks, weights, power, min_cos,
+                                                                   depth_tol)
+    vertices, triangles = _check_bake_mesh(vertices, triangles, "bake_views")
+    dev, ss2 = vertices.device, ssaa * ssaa
+    _fitting_cell(int(triangles.shape[0]), T)
+    base = None
+    if not hasattr(model_or_base, "density"):
+        if _shape(model_or_base) == (3,):
+            base = _to_dev(model_or_base, torch.float32, dev)
+        elif isinstance(model_or_base, torch.Tensor) and _shape(model_or_base) == (T, T, ss2, 3):
+            base = _lib.dev_f32(model_or_base, "base", 3)
+        else:
+            raise Mi3dError(f"model_or_base must be a model, 3 numbers or a float32 tensor [{T}, {T}, {ss2}, 3] (got "
+                            f"{_shape(model_or_base)})")
+    records = torch.from_numpy(records).to(dev)
+    weights = torch.from_numpy(weights).to(dev)
+    images = _to_dev(images, torch.float32, dev)
+    if masks is not None:
+        masks = (_to_dev(masks, torch.float32, dev) != 0).to(torch.uint8).contiguous()
+    depth, _ = _mesh_depth(vertices, triangles, records, H, W)     # once, before the bands; a bad index raises below
+    hits = torch.zeros(T, T, ss2, dtype=torch.uint8, device=dev)
+    nv, nt = int(vertices.shape[0]), int(triangles.shape[0])
+
+    def colour(xyz, owner, row0, rows):
+        if base is None:
+            b = _field_albedo(model_or_base, xyz)
+        elif base.dim() == 1:
+            b = base.expand(xyz.shape[0], 3).contiguous()
+        else:
+            b = base[row0:row0 + rows].reshape(-1, 3)
+        out = torch.empty_like(xyz)
+        _lib.launch("mi3d_texture_project", xyz, _lib.ptr(xyz), _lib.ptr(owner), _lib.ptr(vertices), nv,
+                    _lib.ptr(triangles), nt, T, ssaa, rows, _lib.ptr(records), V, H, W, _lib.ptr(depth), _lib.ptr(images),
+                    _lib.ptr(masks), _lib.ptr(weights), int(power), min_cos2, depth_tol, _lib.ptr(b), _lib.ptr(out),
+                    _lib.ptr(hits[row0]))
+        return out
+
+    image, vt, owner = _bake_bands(vertices, triangles, T, ssaa, colour)
+    return image, vt, owner, hits
 
 
 MTL = ("newmtl mat0 \n"
@@ -532,9 +736,13 @@ def vertex_normals(model, vertices):
 
 
 def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False, min_faces=None,
-           min_diagonal=None, largest=False, decimate=None, target_faces=None):
+           min_diagonal=None, largest=False, decimate=None, target_faces=None, views=None):
     """What NeRFRenderer.export_mesh does (see there).  `S` only sizes the reference's chunks and is ignored."""
     del S
+    if views is not None:                                       # before any work
+        if texture_size is None:
+            raise Mi3dError("export_mesh: views colour the texture: give texture_size too")
+        views = _check_views_dict(views)
     decimate, target_faces = _check_decimate(decimate, target_faces)
     cleaning = min_faces is not None or min_diagonal is not None or largest is not False
     if cleaning:
@@ -568,7 +776,9 @@ def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, norma
         if texture_size is not None:
             _fitting_cell(triangles.shape[0], texture_size)     # refuse before the field is evaluated anywhere
         albedo = vertex_albedo(model, vertices)
-        if texture_size is not None:
+        if views is not None:                                   # after the floater filter and the decimation
+            image, vt = bake_views(model, vertices, triangles, texture_size, ssaa=ssaa, **views)[:2]
+        elif texture_size is not None:
             image, vt, _ = bake_texture(model, vertices, triangles, texture_size, ssaa)
         vn = vertex_normals(model, vertices).cpu().numpy() if normals else None
     v, f, c = vertices.cpu().numpy(), triangles.cpu().numpy(), albedo.cpu().numpy()

@@ -281,6 +281,25 @@ def refine_render(unet, points, feats, world2cam, focal, H, W, radius, ppp):
     return rgb, F.max_pool2d(mask, kernel_size=5, stride=1, padding=2)
 
 
+def render_views(unet, points, feats, c2ws, focal, H, W, radius, ppp):
+    """The refine stage's output as views for the texture bake: `refine_render` under no_grad for every pose of `c2ws`
+    [V, 4, 4] (camera-to-world; NumPy or a tensor).  Returns (images float32 [V, H, W, 3] in [0, 1] on the points'
+    device, K float64 [3, 3] NumPy: `intrinsics(focal, H, W)`) - the `images` / `K` that mesh.bake_views and
+    export_mesh(views=dict(images=, c2w=c2ws, K=)) take; the pixel centres are render_point's, at half-integers."""
+    poses = c2ws.detach().cpu().numpy() if isinstance(c2ws, torch.Tensor) else np.asarray(c2ws)
+    poses = np.asarray(poses, dtype=np.float64)
+    if poses.ndim != 3 or poses.shape[1:] != (4, 4):
+        raise ValueError(f"c2ws must be [V, 4, 4] (got {poses.shape})")
+    out = []
+    with torch.no_grad():
+        for pose in poses:
+            w2c = torch.tensor(np.linalg.inv(pose), device=points.device).float()
+            rgb, _ = refine_render(unet, points, feats, w2c, focal, H, W, radius, ppp)
+            out.append(rgb[0].permute(1, 2, 0).float().clamp(0, 1))
+    K = np.array([[focal * W, 0, 0.5 * W], [0, focal * H, 0.5 * H], [0, 0, 1]], dtype=np.float64)
+    return torch.stack(out).contiguous(), K
+
+
 def refine_train_step(unet, params, optimizer, guidance, text_z, points, world2cam, focal, H, W, radius, ppp,
                       colour_origin, guidance_scale=5.0, t=None, clip_model=None, ref_rgb=None, ref_text=None,
                       is_front=False, gt_mask=None, cx_model=None, points_origin=None, lambda_points=1e3):

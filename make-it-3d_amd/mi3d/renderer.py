@@ -118,7 +118,7 @@ class NeRFRenderer(nn.Module):
 
     @torch.no_grad()
     def export_mesh(self, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False, min_faces=None,
-                    min_diagonal=None, largest=False, decimate=None, target_faces=None):
+                    min_diagonal=None, largest=False, decimate=None, target_faces=None, views=None):
         """renderer.py:157-191 + the file writing of :300-328, reached through main.py's `--save_mesh`: sigma on the
         `resolution`^3 lattice of [-1, 1]^3 (default grid_size), marching cubes at min(mean_density, density_thresh)
         (density_thresh without cuda_ray) on the GPU (mi3d.mesh), `<path>/mesh.obj` + `mesh.mtl`.  By default
@@ -144,11 +144,18 @@ class NeRFRenderer(nn.Module):
         triangles go; `target_faces=N` (an integer >= 1) instead takes the finest d of mesh.DECIMATE_LADDER that leaves at
         most N faces, keeps a mesh that already has no more, and raises Mi3dError if the coarsest does not get there.
         The two are mutually exclusive.  Clustering can leave non-manifold edges and vertices.  With both None nothing
-        of this runs and the files are byte for byte what they were without the arguments."""
+        of this runs and the files are byte for byte what they were without the arguments.  `views` (a dict: `images`
+        [V, H, W, 3] in [0, 1], `c2w` [V, 4, 4], `K` [3, 3], optionally `masks`, `weights`, `power`, `min_cos`,
+        `depth_tol` - mesh.bake_views' arguments) colours `albedo.png` from those views by projection (include/mi3d.h
+        Part 15) instead of from the field alone: every texel some view sees takes the views' weighted
+        colour, every other keeps the field's albedo; what refine.render_views returns plugs in.  It needs
+        `texture_size` (without it: Mi3dError before any work), runs after the floater filter and the decimation and
+        writes the same three files.  With `views=None` nothing of this runs and the files are byte for byte what they
+        were without the argument."""
         from . import mesh
         return mesh.export(self, path, resolution, S, texture_size=texture_size, ssaa=ssaa, normals=normals,
                            min_faces=min_faces, min_diagonal=min_diagonal, largest=largest, decimate=decimate,
-                           target_faces=target_faces)
+                           target_faces=target_faces, views=views)
 
     @torch.no_grad()
     def export_point_cloud(self, outputdir, poses, ref_rgb, fov, H, W, **kwargs):
