@@ -35,7 +35,7 @@ extern "C" {
 /* the ABI version: 5 (4 = 3 + the compact-round inference loop of Part 1b; 5: that loop's ctl block is int32[16] with
  * the dropped-row count in [8], and its plan never passes max_steps; every other entry point is unchanged).  Part 8
  * (marching cubes), Part 9 (texture baking), Part 10 (GroupNorm), Part 12 (the Canny detector), Part 1's
- * mi3d_composite_rays_train_backward_depth and the hash grid's input gradients (mi3d_hashgrid_backward_input of Part 2,
+ * mi3d_composite_rays_train_backward_depth and mi3d_march_train_plan and the hash grid's input gradients (mi3d_hashgrid_backward_input of Part 2,
  * mi3d_grid_points_backward_input of Part 3) and their second-order passes (mi3d_hashgrid_backward_input_backward,
  * mi3d_grid_points_backward_input_backward) and Parts 11 and 13 to 15 were added under 5: new symbols only, nothing
  * existing changed. */
@@ -65,6 +65,12 @@ int mi3d_march_rays_train(const float *rays_o, const float *rays_d, const uint8_
                           float dt_gamma, uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M,
                           const float *nears, const float *fars, float *xyzs, float *dirs, float *deltas,
                           int32_t *rays, int32_t *counter, const float *noises, void *stream);
+/* Not in the reference, host only (no GPU, no stream): the launch shape mi3d_march_rays_train takes for N rays, from the
+ * very function the launch calls.  out_host [3] = (rays per wave: 64, 32 or 16 - the other lanes of a wave only help to
+ * store; batches = ceil(N / rays per wave); workgroups launched = min(batches, 4096), one wave each, a wave walking
+ * batches w, w + workgroups, ...).  N == 0: three zeros.  hipErrorInvalidValue for out_host == NULL.  Added under ABI
+ * version 5: a new symbol only. */
+int mi3d_march_train_plan(uint32_t N, uint32_t *out_host);
 /* Not in the reference: zero rows [counter[0], counter[0]+pad) of xyzs/dirs/deltas (pad < align), the rows
  * raymarching.py:237-241 exposes past the last sample; lets the caller skip the 537 MB zero fill of
  * raymarching.py:217-219. */

@@ -277,6 +277,22 @@ __global__ void k_march_zero_tail(const int32_t *__restrict__ counter, uint32_t 
     for (uint32_t i = threadIdx.x; i < pad * 2; i += blockDim.x) deltas[(size_t)m * 2 + i] = 0.f;
 }
 
+// The launch shape of k_march_train for N > 0 rays: what mi3d_march_rays_train launches and mi3d_march_train_plan reports.
+struct MarchTrainPlan { uint32_t rpw, batches, workgroups; };
+
+inline MarchTrainPlan march_train_plan(uint32_t N) {
+    // rays per wave.  The walk is ~150 instructions per step in a dependent chain, so a wave advances at one wave's issue
+    // rate whatever its lane count: a view of 16 384 rays as 256 full waves would use one SIMD in four.  Halve the rays
+    // per wave until every SIMD has a wave (1024), down to 16 rays each; more waves than SIMDs only add instructions
+    // (measured at C2, tools/march_bench.py: 64 rays per wave 0.75 ms, 16: 0.69, 8: 0.79, 4: 1.48).  One wave's worth of
+    // rays stays one wave (its slab order is then the ray order, which tests that compare two runs row by row rely on).
+    uint32_t rpw = kWave;
+    const uint32_t floor_rpw = (uint32_t)MI3D_TUNE(MI3D_T_MARCH_RPW_MIN, 16), want = (uint32_t)MI3D_TUNE(MI3D_T_MARCH_WAVES, 1024);
+    while (N > (uint32_t)kWave && rpw > floor_rpw && cdiv(N, rpw) < want) rpw >>= 1;
+    const uint32_t batches = cdiv(N, rpw), resident = 256u * 16u;  // persistent beyond 16 waves per CU
+    return MarchTrainPlan{rpw, batches, batches < resident ? batches : resident};
+}
+
 // ---------------------------------------------------------------- training composite (wave per ray)
 
 struct CompositeChunk {
@@ -850,19 +866,17 @@ int mi3d_march_rays_train(const float *rays_o, const float *rays_d, const uint8_
                           const float *fars, float *xyzs, float *dirs, float *deltas, int32_t *rays, int32_t *counter,
                           const float *noises, void *stream) {
     if (N == 0) return 0;
-    // rays per wave.  The walk is ~150 instructions per step in a dependent chain, so a wave advances at one wave's issue
-    // rate whatever its lane count: a view of 16 384 rays as 256 full waves would use one SIMD in four.  Halve the rays
-    // per wave until every SIMD has a wave (1024), down to 16 rays each; more waves than SIMDs only add instructions
-    // (measured at C2, tools/march_bench.py: 64 rays per wave 0.75 ms, 16: 0.69, 8: 0.79, 4: 1.48).  One wave's worth of
-    // rays stays one wave (its slab order is then the ray order, which tests that compare two runs row by row rely on).
-    uint32_t rpw = kWave;
-    const uint32_t floor_rpw = (uint32_t)MI3D_TUNE(MI3D_T_MARCH_RPW_MIN, 16), want = (uint32_t)MI3D_TUNE(MI3D_T_MARCH_WAVES, 1024);
-    while (N > (uint32_t)kWave && rpw > floor_rpw && cdiv(N, rpw) < want) rpw >>= 1;
-    const uint32_t batches = cdiv(N, rpw), resident = 256u * 16u;  // persistent beyond 16 waves per CU
-    hipLaunchKernelGGL(k_march_train, dim3(batches < resident ? batches : resident), dim3(kWave), 0, as_stream(stream),
-                       rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs, dirs, deltas, rays,
-                       counter, noises, rpw);
+    const MarchTrainPlan p = march_train_plan(N);
+    hipLaunchKernelGGL(k_march_train, dim3(p.workgroups), dim3(kWave), 0, as_stream(stream), rays_o, rays_d, grid, bound,
+                       dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs, dirs, deltas, rays, counter, noises, p.rpw);
     return launch_status();
+}
+
+int mi3d_march_train_plan(uint32_t N, uint32_t *out) {
+    if (out == nullptr) return (int)hipErrorInvalidValue;
+    const MarchTrainPlan p = N != 0 ? march_train_plan(N) : MarchTrainPlan{0, 0, 0};
+    out[0] = p.rpw; out[1] = p.batches; out[2] = p.workgroups;
+    return 0;
 }
 
 int mi3d_march_zero_tail(const int32_t *counter, uint32_t align, uint32_t M, float *xyzs, float *dirs, float *deltas,

@@ -24,6 +24,7 @@ _SIGNATURES = {
     "mi3d_morton3D_invert": [vp, u32, vp, vp],
     "mi3d_packbits": [vp, u32, f32, vp, vp],
     "mi3d_march_rays_train": [vp, vp, vp, f32, f32, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "mi3d_march_train_plan": [u32, vp],                                             # host-side query
     "mi3d_march_zero_tail": [vp, u32, u32, vp, vp, vp, vp],
     "mi3d_composite_rays_train_forward": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, vp],
     "mi3d_composite_rays_train_backward": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, vp, vp],

@@ -305,6 +305,172 @@ def test_inference_march_composite_loop(cuda, oracle):
     np.testing.assert_allclose(dep.cpu().numpy(), dep_r, rtol=RTOL, atol=1e-5)
 
 
+def test_inference_march_composite_sdf_loop(cuda, oracle):
+    """The same loop through composite_sdf_rays (C ABI mi3d_composite_sdf_rays: alpha = sigma, no normals), round after
+    round until nobody is alive.  The three ways a ray leaves a round are told apart from the oracle's data and each must
+    occur: stopped by T < T_thresh (it died although none of its rows has a zero delta), stopped on the zero-delta
+    sentinel (it died with weights_sum < 1 - T_thresh, so no step of it ever saw T < T_thresh), survived (rays_t written
+    back).  The alive flags and rays_t are exact: alpha is an input, and t only ever adds deltas in the same order."""
+    import raymarching
+    rng = np.random.default_rng(30)
+    N, H, T_thresh = 600, 128, 1e-2
+    o, d = make_rays(rng, N)
+    aabb = np.array([-1, -1, -1, 1, 1, 1], np.float32)
+    nears, fars = oracle.near_far_from_aabb(o, d, aabb)
+    bits = sphere_bitfield(oracle, 1, H, 0.5)
+
+    def field(x):  # the toy field of the density loop, its sigma in [0, 40] mapped into [0, 0.95] as alpha
+        a = (40 * np.exp(-np.sum(x * x, 1) / 0.05) * (0.95 / 40)).astype(np.float32)
+        c = (0.5 + 0.5 * np.sin(x * 7)).astype(np.float32)
+        return a, c
+
+    ws_r, dep_r, img_r = np.zeros(N, np.float32), np.zeros(N, np.float32), np.zeros((N, 3), np.float32)
+    alive_r, t_r = np.arange(N, dtype=np.int32), nears.copy()
+    ws, dep, img = torch.zeros(N, device=cuda), torch.zeros(N, device=cuda), torch.zeros(N, 3, device=cuda)
+    alive, t = torch.arange(N, dtype=torch.int32, device=cuda), T(nears, cuda).clone()
+    by_thresh = by_thresh_multi = by_sentinel = survived = rounds = 0
+    while True:
+        n_alive = alive_r.shape[0]
+        assert alive.shape[0] == n_alive
+        if n_alive == 0:
+            break
+        n_step = max(min(N // n_alive, 8), 1)
+        xr, dr, lr = oracle.march_rays(n_alive, n_step, alive_r, t_r, o, d, 1.0, bits, 1, H, nears, fars, align=128,
+                                       max_steps=256)
+        x, dd, l = raymarching.march_rays(n_alive, n_step, alive, t, T(o, cuda), T(d, cuda), 1.0, T(bits, cuda), 1,
+                                          H, T(nears, cuda), T(fars, cuda), 128, False, 0, 256)
+        assert np.array_equal(x.cpu().numpy(), xr) and np.array_equal(l.cpu().numpy(), lr)
+        a, c = field(xr)
+        assert 0 <= a.min() and a.max() <= 0.95
+        ids, t_before = alive_r.copy(), t_r.copy()
+        oracle.composite_sdf_rays(n_alive, n_step, alive_r, t_r, a, c, lr, ws_r, dep_r, img_r, T_thresh)
+        raymarching.composite_sdf_rays(n_alive, n_step, alive, t, T(a, cuda), T(c, cuda), l, ws, dep, img, T_thresh)
+        assert np.array_equal(alive.cpu().numpy() >= 0, alive_r >= 0)
+        assert np.array_equal(t.cpu().numpy(), t_r)
+        died = alive_r < 0
+        full = (lr[:n_alive * n_step, 0].reshape(n_alive, n_step) != 0).all(1)
+        by_thresh += int((died & full).sum())
+        by_thresh_multi += int((died & full).sum()) if n_step > 1 else 0
+        by_sentinel += int((died & ~full & (ws_r[ids] < 1 - T_thresh)).sum())
+        survived += int((~died).sum())
+        assert (~died <= full).all() and (t_r[ids[~died]] > t_before[ids[~died]]).all()   # a survivor took n_step steps
+        assert np.array_equal(t_r[ids[died]], t_before[ids[died]])                       # rays_t of a dead ray stays
+        alive_r = alive_r[alive_r >= 0]
+        alive = alive[alive >= 0]
+        rounds += 1
+        assert rounds < 300
+    print(f"{rounds} rounds: {by_thresh} rays stopped by T < T_thresh ({by_thresh_multi} in rounds of several steps), "
+          f"{by_sentinel} on the zero-delta sentinel, {survived} survivals")
+    assert by_thresh > 0 and by_thresh_multi > 0 and by_sentinel > 0 and survived > 0
+    assert by_thresh + by_sentinel <= N
+    np.testing.assert_allclose(ws.cpu().numpy(), ws_r, rtol=RTOL, atol=1e-6)
+    np.testing.assert_allclose(img.cpu().numpy(), img_r, rtol=RTOL, atol=1e-6)
+    np.testing.assert_allclose(dep.cpu().numpy(), dep_r, rtol=RTOL, atol=1e-5)
+    assert float(ws_r.max()) > 1 - T_thresh and float(ws_r.min()) == 0
+
+
+# the chunk-edge ladder of tests/test_depth_grad_gpu.py on the SDF compositor: one slab per (length, scale) pair ...
+SDF_STEPS = (0, 1, 2, 63, 64, 65, 127, 128, 129, 192, 200, 256)
+SDF_SCALES = (3.0, 60.0, 400.0, 0.0)
+# ... five rays of 256 samples and one constant alpha each, chosen so that the ray stops AT this sample (the last lane of
+# the first chunk, the first lane and the inside and the last lane of the second, the first lane of the third) ...
+SDF_STOPS = (63, 64, 100, 127, 128)
+# ... and a ray whose slab overflows M.  (T_thresh, seed): seeds chosen on the CPU so that no transmittance of the input
+# lies within 3.5 % and 1.7 % of T_thresh (the placed stop at sample 128 is itself 1.8 % from 1e-2; 1 % is asserted
+# below): both sides then stop every ray at the same sample
+SDF_LADDER_CASES = [(1e-4, 2), (1e-2, 0)]
+SDF_MARGIN = 1e-2
+
+
+def sdf_ladder_case(seed, T_thresh):
+    rng = np.random.default_rng(seed)
+    ladder = [(k, n, sc) for k, (sc, n) in enumerate((sc, n) for sc in SDF_SCALES for n in SDF_STEPS)]
+    placed = [(len(ladder) + j, 256, ("stop", s)) for j, s in enumerate(SDF_STOPS)]
+    # slabs: the scale-400 block last, so that the in-bounds rows of the overflowing ray are rows past the stop sample of
+    # the last ray (256 samples that stop within the first few): they keep a zero gradient only if that ray is skipped
+    layout = [r for r in ladder if r[2] != 400.0] + placed + [r for r in ladder if r[2] == 400.0]
+    n_rays = len(ladder) + len(placed) + 1
+    M = sum(n for _, n, _ in layout)
+    alpha, first, rows, off = np.zeros(M, np.float32), [], np.zeros((n_rays, 3), np.int32), 0
+    for k, n, sc in layout:
+        rows[k] = (k, off, n)
+        if isinstance(sc, tuple):      # (1 - alpha)^(s + 1) < T_thresh < (1 - alpha)^s, T_thresh half a sample from both
+            alpha[off:off + n] = 1 - T_thresh ** (1 / (sc[1] + 0.5))
+        else:                          # sigma mapped to alpha as test_composite_train_forward_backward does
+            alpha[off:off + n] = np.clip(rng.exponential(1.0, n) * sc * 0.01, 0, 0.95)
+        if n:
+            first.append(off)
+        off += n
+    rows[n_rays - 1] = (n_rays - 1, M - 32, 64)
+    d0 = rng.uniform(0.003, 0.02, M).astype(np.float32)
+    d1 = d0.copy()
+    d1[first] = 0
+    rgb = rng.random((M, 3)).astype(np.float32)
+    rays = rows[rng.permutation(n_rays)]
+    assert (rays[:, 0] != np.arange(n_rays)).any()
+    g = dict(ws=rng.normal(size=n_rays).astype(np.float32), d=rng.normal(size=n_rays).astype(np.float32),
+             img=rng.normal(size=(n_rays, 3)).astype(np.float32))
+    return alpha, rgb, np.stack([d0, d1], 1), rays, g
+
+
+def sdf_ladder_stops(alpha, rays, T_thresh):
+    """From the transmittances T_i = prod_{j <= i} (1 - alpha_j) in binary64, per ray that fits: the stop sample (the
+    first with T_i < T_thresh, which is still accumulated; the last sample otherwise), whether it stopped early, the rows
+    up to the stop sample, and the smallest |T_i / T_thresh - 1|."""
+    M = alpha.shape[0]
+    stops, live, margin = {}, np.zeros(M, bool), np.inf
+    for index, offset, count in rays.tolist():
+        if count == 0 or offset + count > M:
+            continue
+        T_incl = np.cumprod(1 - alpha[offset:offset + count].astype(np.float64))
+        below = np.nonzero(T_incl < T_thresh)[0]
+        stop = int(below[0]) if len(below) else count - 1
+        stops[index] = (stop, bool(len(below)) and stop < count - 1)
+        live[offset:offset + stop + 1] = True
+        margin = min(margin, float(np.abs(T_incl / T_thresh - 1).min()))
+    return stops, live, margin
+
+
+@pytest.mark.parametrize("T_thresh,seed", SDF_LADDER_CASES)
+def test_composite_sdf_train_chunk_edges(cuda, oracle, T_thresh, seed):
+    """composite_sdf_rays_train forward and backward against the oracle on ray lengths at every chunk edge of the
+    wave-per-ray kernels (64 samples per trip), with stops in the first lane, the last lane and the second chunk."""
+    import raymarching
+    alpha, rgb, deltas, rays, g = sdf_ladder_case(seed, T_thresh)
+    n_rays, M = rays.shape[0], alpha.shape[0]
+    over = n_rays - 1
+    stops, live, margin = sdf_ladder_stops(alpha, rays, T_thresh)
+    early = sorted(s for s, e in stops.values() if e)
+    print(f"T_thresh {T_thresh}: {len(early)} early-stopped rays at samples {early}, margin {margin:.3g}")
+    assert margin >= SDF_MARGIN and 0 <= alpha.min() and alpha.max() <= 0.95
+    base = len(SDF_STEPS) * len(SDF_SCALES)
+    assert [stops[base + j] for j in range(len(SDF_STOPS))] == [(s, True) for s in SDF_STOPS]     # placed where meant
+    assert any(s > 0 and s % 64 == 0 for s in early) and any(s % 64 == 63 for s in early)         # first lane, last lane
+    assert any(64 <= s < 128 for s in early) and any(s < 63 for s in early)                       # second chunk, first
+    assert over not in stops and not live[M - 32:].any()
+
+    ws_r, dep_r, img_r = oracle.composite_rays_train(alpha, rgb, deltas, rays, T_thresh, sdf=True)
+    s_t, c_t = T(alpha, cuda).requires_grad_(True), T(rgb, cuda).requires_grad_(True)
+    ws, dep, img = raymarching.composite_sdf_rays_train(s_t, c_t, T(deltas, cuda), T(rays, cuda), T_thresh)
+    np.testing.assert_allclose(ws.detach().cpu().numpy(), ws_r, rtol=RTOL, atol=1e-6)
+    np.testing.assert_allclose(img.detach().cpu().numpy(), img_r, rtol=RTOL, atol=1e-6)
+    np.testing.assert_allclose(dep.detach().cpu().numpy(), dep_r, rtol=RTOL, atol=1e-5)
+    assert ws_r[over] == 0 and float(ws.detach()[over]) == 0 and float(img.detach()[over].abs().max()) == 0
+
+    torch.autograd.backward([ws, dep, img], [T(g["ws"], cuda), T(g["d"], cuda), T(g["img"], cuda)])   # g["d"]: ignored
+    gs_r, gc_r = oracle.composite_rays_train_backward(g["ws"], g["img"], alpha, rgb, deltas, rays, ws_r, img_r, T_thresh,
+                                                      sdf=True)
+    gs, gc = s_t.grad.cpu().numpy(), c_t.grad.cpu().numpy()
+    np.testing.assert_allclose(gc, gc_r, rtol=RTOL, atol=1e-6)
+    scale = np.abs(gs_r).max() + 1e-12
+    print(f"grad_sigmas err {np.abs(gs - gs_r).max() / scale:.3g} x scale, grad_rgbs max abs err {np.abs(gc - gc_r).max():.3g}")
+    assert np.abs(gs - gs_r).max() <= 2e-4 * scale
+    assert np.mean((gs_r == 0) != (gs == 0)) < 2e-3
+    # rows past a ray's stop sample, and the in-bounds rows of the overflowing ray, keep exactly zero gradient
+    assert (gs[~live] == 0).all() and (gc[~live] == 0).all() and (gs_r[~live] == 0).all() and (gc_r[~live] == 0).all()
+    assert (gs_r[live] != 0).mean() > 0.5
+
+
 COMPACT_ROUND = 1024     # rays per round of k_compact_alive_ctl's single workgroup (its `i0 += 1024`, launch_bounds 1024)
 
 
