@@ -37,7 +37,7 @@ extern "C" {
  * (marching cubes), Part 9 (texture baking), Part 10 (GroupNorm), Part 12 (the Canny detector), Part 1's
  * mi3d_composite_rays_train_backward_depth and mi3d_march_train_plan and the hash grid's input gradients (mi3d_hashgrid_backward_input of Part 2,
  * mi3d_grid_points_backward_input of Part 3) and their second-order passes (mi3d_hashgrid_backward_input_backward,
- * mi3d_grid_points_backward_input_backward) and Parts 11 and 13 to 15 were added under 5: new symbols only, nothing
+ * mi3d_grid_points_backward_input_backward) and Parts 11 and 13 to 16 were added under 5: new symbols only, nothing
  * existing changed. */
 int mi3d_abi_version(void);
 const char *mi3d_last_error_string(int err);
@@ -942,6 +942,76 @@ int mi3d_texture_project(const float *xyz, const int32_t *owner, const float *ve
                          const float *views, uint32_t V, uint32_t H, uint32_t W, const float *depth, const float *images,
                          const uint8_t *masks, const float *weights, uint32_t power, float min_cos2, float depth_tol,
                          const float *base, float *colour, uint8_t *hits, void *stream);
+
+/* ------------------------------------------------------------------ Part 16: Taubin smoothing (mesh export) */
+
+/* Taubin's lambda | mu smoothing of the vertices of an indexed triangle mesh: every iteration moves each vertex towards
+ * the mean of its umbrella by the factor lambda, then by the factor mu (negative: back out), which removes the
+ * voxel-scale bumps of a marching-cubes surface and the stair steps of Part 14 without the shrinkage of plain Laplacian
+ * smoothing.  The neighbour sums are fixed-point integers, so the result does not depend on the order in which a row
+ * of neighbours is stored or walked: two runs give byte-identical buffers, and a NumPy restatement gives the same
+ * bytes.  Projects of this family smooth through pymeshlab, which is on no machine this project builds on: the
+ * semantics below are this project's own contract - PARITY UNPINNED, the standing of Parts 13 and 14.  Added under
+ * ABI version 5: new symbols only.  (Declared ahead of the point-cloud part, like Parts 12 to 15.)
+ *
+ * vertices float[nv][3], triangles int32[nt][3]; nv <= 2^31 - 1, nt <= 2^30 (a row offset is a uint32 below 3 nt).
+ * iterations in [1, 1000]; lambda and mu binary64, finite, in [-1, 1]; pin_border a flag; max_move binary32, >= 0,
+ * +infinity for "no clamp"; e = fraction_bits in [0, 40].
+ *   - USABLE TRIANGLES: a triangle is usable iff its three indices lie in [0, nv), are pairwise distinct and name
+ *     vertices whose three coordinates are finite IN THE INPUT.  The others are never dereferenced past the index check;
+ *     they are COUNTED in counts[0] and take no part in anything below.
+ *   - UMBRELLA of vertex i: for every usable triangle that cites i, the positions of its two other corners, each with
+ *     weight 1 - a neighbour across an interior edge of a manifold enters twice, once per triangle, which on a closed
+ *     manifold is the uniform umbrella.  deg(i) = the number of usable triangles that cite i; w = 2 deg(i).  No edge
+ *     table is built.
+ *   - EXACT SUMS: a neighbour's coordinate p enters as the integer q: with x = (double)p * 2^e (exact), q = 2^40 if
+ *     x >= 2^40, -2^40 if x <= -2^40, 0 if x is NaN, else llrint(x) (to nearest, ties to even).  S (per axis) = the sum
+ *     of q over the umbrella and w are 64-bit integers.  |S| <= 2 deg 2^40, so neither can overflow for any degree
+ *     below 2^22.  The limit that applies is lower, MI3D_SMOOTH_MAX_DEGREE = 1024, because the border rule below costs
+ *     deg^2 comparisons: a vertex with deg > 1024 is PINNED whatever pin_border says, its row is never walked, and it
+ *     is COUNTED in counts[4].  (Marching cubes gives degrees up to about 12, clustering a few dozen; one thread took about
+ *     2.8 s for the border rule of a vertex of degree 4096 on an MI355X, hence 1024: a sixteenth of that.)
+ *   - ONE PASS with factor k, per vertex and axis: m = ((double)S / (double)w) * 2^-e, then
+ *     p' = (float)((double)p + k * (m - (double)p)): a division, a multiplication by a power of two, a subtraction, a
+ *     multiplication and an addition, every one a separately rounded binary64 operation (no fused multiply-add), and
+ *     ONE final rounding to binary32.  Every vertex of a pass reads the positions from BEFORE the pass (Jacobi: two
+ *     buffers, plain stores).  A vertex with w = 0 stays where it is, bit for bit, and so does a pinned one and one
+ *     that is not finite in the input.  A pass with k == 0 is not launched.
+ *   - ONE ITERATION: a pass with lambda, then a pass with mu.  lambda = mu = 0 copies the input.
+ *   - BORDER: with pin_border != 0 a vertex is pinned iff it shares exactly ONE usable triangle with some neighbour -
+ *     it lies on an open edge.  An edge with three or more triangles (clustering produces them) pins nothing.  The
+ *     flags are computed once, from the connectivity alone.
+ *   - MAX_MOVE: after every pass each coordinate p' of a vertex that moved is clamped to [lo, hi], lo = p0 - max_move
+ *     and hi = p0 + max_move, p0 the INPUT coordinate, both binary32 operations: lo if p' < lo, else hi if p' > hi,
+ *     else p'.  A box: no sqrt.  It keeps the smoothed surface within a stated distance of the isosurface.
+ *   - OUTPUT: out_vertices float[nv][3]; the triangles are not touched.  out_vertices must not alias vertices.
+ *   - counts (device uint64[8], 8-byte aligned, zeroed in-stream): [0] unusable triangles, [1] non-finite vertices,
+ *     [2] vertices no usable triangle cites (w = 0; every non-finite vertex is one), [3] vertices pinned as border (0
+ *     without pin_border), [4] vertices above the degree limit, [5] vertices of which the clamp changed a coordinate
+ *     in the LAST pass launched, [6] row slots that could not be placed - an inconsistency: non-zero means the result
+ *     is invalid, an error for the caller to raise - [7] 0.
+ *   - HOW: the vertex -> triangle incidence is built ONCE: the degree of every vertex by int32 atomics (thread =
+ *     triangle), an exclusive scan (per-workgroup sums, one workgroup scans them, an offsets pass), and a fill in which
+ *     a triangle claims a slot of each corner's row by an atomic cursor and stores the pair of its other corners.  The
+ *     order inside a row depends on scheduling; nothing above does.  Then the border flags (thread = vertex: for each
+ *     entry of the row, the number of entries that name the same neighbour) and 2 x iterations passes (thread =
+ *     vertex) without any atomic.  Every loop is bounded by a row length; no thread waits for another.
+ *
+ *   mi3d_mesh_smooth_workspace  host only: bytes of device scratch for a mesh of this size (0 for nv = 0 and for sizes
+ *                          out of range): the cursors, the row offsets, the scan's block sums, the flags, the second
+ *                          vertex buffer and 3 nt rows of two int32.
+ *   mi3d_mesh_smooth       everything above on `stream`.  The caller MAY read counts afterwards; nothing needs to be read.
+ * No entry point allocates or synchronises.  nv = 0 launches nothing and succeeds (counts is not touched).  Sizes,
+ * iterations or fraction_bits out of range, a lambda or mu that is not finite or outside [-1, 1], a max_move that is
+ * negative or NaN, out_vertices == vertices, a workspace that is too small or not 8-byte aligned, a counts that is not
+ * 8-byte aligned and every NULL pointer that would be dereferenced are refused (hipErrorInvalidValue) and launch
+ * nothing. */
+#define MI3D_SMOOTH_MAX_DEGREE 1024
+size_t mi3d_mesh_smooth_workspace(unsigned long long nv, unsigned long long nt);
+int mi3d_mesh_smooth(const float *vertices, unsigned long long nv, const int32_t *triangles, unsigned long long nt,
+                     uint32_t iterations, double lambda, double mu, int pin_border, float max_move,
+                     uint32_t fraction_bits, void *ws, size_t ws_bytes, float *out_vertices, unsigned long long *counts,
+                     void *stream);
 
 /* ------------------------------------------------------------------ Part 11: the refine stage's point cloud */
 

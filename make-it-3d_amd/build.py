@@ -24,6 +24,7 @@ UNITS = [
     ("mesh.hip", ["-ffp-contract=off"]),
     ("meshclean.hip", ["-ffp-contract=off"]),
     ("meshsimplify.hip", ["-ffp-contract=off"]),
+    ("meshsmooth.hip", ["-ffp-contract=off"]),
     ("texture.hip", ["-ffp-contract=off"]),
     ("textureviews.hip", ["-ffp-contract=off"]),
     ("groupnorm.hip", []),

@@ -121,6 +121,9 @@ _SIGNATURES = {
     "mi3d_mesh_depth": [vp, C.c_uint64, vp, C.c_uint64, vp, u32, u32, u32, vp, vp, vp],
     "mi3d_texture_project": [vp, vp, vp, C.c_uint64, vp, C.c_uint64, u32, u32, u32, vp, u32, u32, u32, vp, vp, vp, vp, u32,
                              f32, f32, vp, vp, vp, vp],
+    # Part 16 -----------------------------------------------------------------------------------------
+    "mi3d_mesh_smooth": [vp, C.c_uint64, vp, C.c_uint64, u32, C.c_double, C.c_double, C.c_int, f32, u32, vp, C.c_size_t,
+                         vp, vp, vp],
 }
 
 # host-only queries whose return value is not a hipError_t: (argtypes, restype), bound in lib() like the block below
@@ -134,6 +137,7 @@ _LATE_SIGNATURES = {
     "mi3d_pc_unproject_workspace": ([u32, u32], C.c_size_t),
     "mi3d_mesh_components_workspace": ([C.c_uint64, C.c_uint64], C.c_size_t),
     "mi3d_mesh_simplify_workspace": ([C.c_uint64, C.c_uint64, C.c_int], C.c_size_t),
+    "mi3d_mesh_smooth_workspace": ([C.c_uint64, C.c_uint64], C.c_size_t),
 }
 
 

@@ -13,6 +13,8 @@
   simplify         the kernels of csrc/meshsimplify.hip (include/mi3d.h Part 14): vertex clustering on a uniform lattice -
                    one vertex per occupied cell, degenerate and duplicate triangles dropped; the host reads the counts
                    once to size the outputs
+  smooth           the kernels of csrc/meshsmooth.hip (include/mi3d.h Part 16): Taubin's lambda | mu smoothing of the
+                   vertices - the incidence built once, then passes without atomics over exact fixed-point sums
   bake_texture     the kernels of csrc/texture.hip (include/mi3d.h Part 9): a texel patch per triangle, the field's albedo
                    at every texel's surface point, packed to 8-bit RGB on the device
   render_depth     the depth maps of a mesh from V pinhole cameras (csrc/textureviews.hip, include/mi3d.h Part 15)
@@ -319,6 +321,113 @@ def _decimate(vertices, triangles, R, decimate, target_faces):
         raise Mi3dError(f"export_mesh: nothing survives decimate={d:g}: the {nv} vertices fall into {host[5]} clusters, "
                         f"{host[6]} of the {nt} triangles are degenerate and {host[7]} duplicates")
     return _simplify_emit(vertices, triangles, state, host)[:2]
+
+
+# Taubin's published pair (G. Taubin, "A signal processing approach to fair surface design", SIGGRAPH 1995: lambda = 0.5,
+# mu = -0.53, a pass band just above 0.1).  Nobody has measured them against alternatives on this project's meshes.
+SMOOTH_LAMBDA, SMOOTH_MU = 0.5, -0.53
+SMOOTH_MAX_ITERATIONS, SMOOTH_MAX_FRACTION_BITS = 1000, 40
+SMOOTH_COUNTS = ("unusable_triangles", "non_finite_vertices", "isolated_vertices", "border_vertices",
+                 "over_degree_vertices", "clamped_vertices", "errors")   # counts[0 .. 6] of include/mi3d.h Part 16
+SMOOTH_KEYS = ("iterations", "lam", "mu", "pin_border", "max_move")
+
+
+def _check_smooth(iterations, lam=SMOOTH_LAMBDA, mu=SMOOTH_MU, pin_border=True, max_move=None):
+    """The arguments of smooth() that need no tensor: (iterations, lam, mu, pin_border, max_move as a float or None)."""
+    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)):
+        raise Mi3dError(f"iterations must be an integer (got {iterations!r})")
+    if not 1 <= int(iterations) <= SMOOTH_MAX_ITERATIONS:
+        raise Mi3dError(f"iterations must lie in [1, {SMOOTH_MAX_ITERATIONS}] (got {iterations})")
+    for name, k in (("lam", lam), ("mu", mu)):
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, float, np.integer, np.floating)):
+            raise Mi3dError(f"{name} must be a number (got {k!r})")
+        if not -1.0 <= float(k) <= 1.0:                         # false for NaN
+            raise Mi3dError(f"{name} must be finite and lie in [-1, 1] (got {k!r})")
+    lam, mu = float(lam), float(mu)                             # binary64, as the kernels take them
+    if not isinstance(pin_border, (bool, np.bool_)):
+        raise Mi3dError(f"pin_border must be a bool (got {pin_border!r})")
+    if max_move is not None:
+        if isinstance(max_move, (bool, np.bool_)) or not isinstance(max_move, (int, float, np.integer, np.floating)):
+            raise Mi3dError(f"max_move must be a number or None (got {max_move!r})")
+        if not float(max_move) >= 0.0:                          # false for NaN
+            raise Mi3dError(f"max_move must be >= 0 and not NaN (got {max_move!r})")
+        max_move = float(max_move)
+    return int(iterations), lam, mu, bool(pin_border), max_move
+
+
+def smooth_fraction_bits(extent):
+    """The fraction bits e of include/mi3d.h Part 16 for coordinates up to `extent` in magnitude: the largest e <= 40
+    with extent * 2^e <= 2^38, so that a coordinate may grow fourfold before its fixed-point image saturates."""
+    if isinstance(extent, (bool, np.bool_)) or not isinstance(extent, (int, float, np.integer, np.floating)):
+        raise Mi3dError(f"extent must be a number (got {extent!r})")
+    extent = float(extent)
+    if not (np.isfinite(extent) and extent >= 0.0):
+        raise Mi3dError(f"extent must be finite and >= 0 (got {extent!r})")
+    exponent = int(np.frexp(extent)[1]) if extent > 0.0 else -SMOOTH_MAX_FRACTION_BITS   # extent <= 2^exponent
+    return min(max(38 - exponent, 0), SMOOTH_MAX_FRACTION_BITS)
+
+
+def smooth(vertices, triangles, iterations, lam=SMOOTH_LAMBDA, mu=SMOOTH_MU, pin_border=True, max_move=None, extent=None,
+           return_stats=False):
+    """Taubin smoothing by the contract of include/mi3d.h Part 16: `iterations` times a pass that moves every vertex
+    towards the mean of its umbrella by `lam`, then one by `mu` (negative: the pass that undoes the shrinkage; mu=0:
+    plain Laplacian smoothing, which shrinks).  vertices float32 [nv, 3], triangles int32 [nt, 3] on the GPU.
+    `pin_border=True` keeps the vertices on an open edge where they are; `max_move` (a number >= 0, None: no limit) keeps
+    every coordinate within that distance of its input value.  `extent` (finite, >= 0) bounds |coordinate| and fixes the
+    fixed-point scale of the neighbour sums (smooth_fraction_bits); None reads `|vertices|.amax()` of the finite
+    coordinates from the device - the one host read; with `extent` given nothing is read.  Returns the new vertices
+    float32 [nv, 3] on the same device and, with `return_stats=True` (one more host read), a dict of the counts named in
+    SMOOTH_COUNTS; a non-zero `errors` raises Mi3dError then.  Triangles with an index outside [0, nv), a repeated index
+    or a non-finite vertex take no part (they are counted, not refused); vertices no usable triangle cites, and those
+    with more than 1024 triangles, stay where they are.  The defaults lam=0.5, mu=-0.53 are Taubin's published pair, not
+    measured on this project's meshes.  The arguments are checked first, on any device."""
+    iterations, lam, mu, pin_border, max_move = _check_smooth(iterations, lam, mu, pin_border, max_move)
+    e = None if extent is None else smooth_fraction_bits(extent)
+    vertices, triangles = _check_mesh(vertices, triangles)
+    nv, nt, dev = int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
+    out = torch.empty_like(vertices)
+    if nv == 0:
+        return (out, dict(zip(SMOOTH_COUNTS, [0] * len(SMOOTH_COUNTS)))) if return_stats else out
+    if e is None:
+        mag = torch.where(torch.isfinite(vertices), vertices.abs(), torch.zeros_like(vertices)).amax()
+        e = smooth_fraction_bits(float(mag))                    # the one host read
+    ws_bytes = int(_lib.lib().mi3d_mesh_smooth_workspace(nv, nt))
+    if ws_bytes == 0:
+        raise Mi3dError(f"{nt} triangles are more than a smoothing takes (2^30)")
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    _lib.launch("mi3d_mesh_smooth", vertices, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, iterations, lam, mu,
+                int(pin_border), float("inf") if max_move is None else max_move, e, _lib.ptr(ws), ws_bytes, _lib.ptr(out),
+                _lib.ptr(counts))
+    if not return_stats:
+        return out
+    stats = dict(zip(SMOOTH_COUNTS, counts.tolist()))
+    if stats["errors"] != 0:
+        raise Mi3dError(f"mesh smooth: {stats['errors']} row slots could not be placed (the result is invalid: a bug, or "
+                        f"the buffers changed during the call)")
+    return out, stats
+
+
+def _check_smooth_option(smooth):
+    """export's `smooth`: None, an iteration count, or a dict of SMOOTH_KEYS -> the tuple _check_smooth returns."""
+    if smooth is None:
+        return None
+    if isinstance(smooth, dict):
+        unknown = sorted(set(smooth) - set(SMOOTH_KEYS))
+        if unknown or "iterations" not in smooth:
+            raise Mi3dError(f"smooth: unknown keys {unknown}; it takes {SMOOTH_KEYS}, and iterations is required")
+        return _check_smooth(**smooth)
+    return _check_smooth(smooth)
+
+
+def _smooth_export(vertices, triangles, smoothing, h):
+    """export's smoothing step: the vertices lie in [-1, 1]^3 (extent 1: nothing is read for the scale), `max_move` counts
+    grid steps h; the counts are read once, so that an inconsistency raises."""
+    iterations, lam, mu, pin_border, max_move = smoothing
+    if max_move is not None:
+        max_move = float(np.float32(max_move * h))
+    return smooth(vertices, triangles, iterations, lam=lam, mu=mu, pin_border=pin_border, max_move=max_move, extent=1.0,
+                  return_stats=True)[0]
 
 
 def _chunks(n):
@@ -736,9 +845,10 @@ def vertex_normals(model, vertices):
 
 
 def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False, min_faces=None,
-           min_diagonal=None, largest=False, decimate=None, target_faces=None, views=None):
+           min_diagonal=None, largest=False, decimate=None, target_faces=None, views=None, smooth=None):
     """What NeRFRenderer.export_mesh does (see there).  `S` only sizes the reference's chunks and is ignored."""
     del S
+    smoothing = _check_smooth_option(smooth)                    # before any work
     if views is not None:                                       # before any work
         if texture_size is None:
             raise Mi3dError("export_mesh: views colour the texture: give texture_size too")
@@ -773,6 +883,8 @@ def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, norma
                                 f"{counts[4] >> 32} triangles ({nv0} vertices, {nt0} triangles in all)")
         if decimate is not None or target_faces is not None:    # after the floater filter, which sees the original mesh
             vertices, triangles = _decimate(vertices, triangles, R, decimate, target_faces)
+        if smoothing is not None:                               # before the atlas check, the colours, the bakes, the normals
+            vertices = _smooth_export(vertices, triangles, smoothing, h)
         if texture_size is not None:
             _fitting_cell(triangles.shape[0], texture_size)     # refuse before the field is evaluated anywhere
         albedo = vertex_albedo(model, vertices)

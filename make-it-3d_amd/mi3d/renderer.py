@@ -118,7 +118,7 @@ class NeRFRenderer(nn.Module):
 
     @torch.no_grad()
     def export_mesh(self, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False, min_faces=None,
-                    min_diagonal=None, largest=False, decimate=None, target_faces=None, views=None):
+                    min_diagonal=None, largest=False, decimate=None, target_faces=None, views=None, smooth=None):
         """renderer.py:157-191 + the file writing of :300-328, reached through main.py's `--save_mesh`: sigma on the
         `resolution`^3 lattice of [-1, 1]^3 (default grid_size), marching cubes at min(mean_density, density_thresh)
         (density_thresh without cuda_ray) on the GPU (mi3d.mesh), `<path>/mesh.obj` + `mesh.mtl`.  By default
@@ -151,11 +151,19 @@ class NeRFRenderer(nn.Module):
         colour, every other keeps the field's albedo; what refine.render_views returns plugs in.  It needs
         `texture_size` (without it: Mi3dError before any work), runs after the floater filter and the decimation and
         writes the same three files.  With `views=None` nothing of this runs and the files are byte for byte what they
-        were without the argument."""
+        were without the argument.  `smooth=n` (an integer in [1, 1000]) or `smooth=dict(iterations=, lam=, mu=,
+        pin_border=, max_move=)` runs n iterations of Taubin's lambda | mu smoothing over the vertices (mesh.smooth,
+        include/mi3d.h Part 16) after the floater filter and the decimation and before the atlas check, the
+        colours, the texture bake (field or views) and the normals, which therefore all see the smoothed vertices; the
+        faces are not touched.  `lam` and `mu` default to Taubin's published 0.5 and -0.53 (not measured on this
+        project's meshes), `pin_border` to True; `max_move` (None: no limit) is in grid steps of the extraction lattice
+        and keeps every coordinate within that distance of the extracted surface.  `normals=True` stays the FIELD's
+        analytic normal, now evaluated at the moved vertex: it is not the normal of the smoothed triangles.  With
+        `smooth=None` nothing of this runs and the files are byte for byte what they were without the argument."""
         from . import mesh
         return mesh.export(self, path, resolution, S, texture_size=texture_size, ssaa=ssaa, normals=normals,
                            min_faces=min_faces, min_diagonal=min_diagonal, largest=largest, decimate=decimate,
-                           target_faces=target_faces, views=views)
+                           target_faces=target_faces, views=views, smooth=smooth)
 
     @torch.no_grad()
     def export_point_cloud(self, outputdir, poses, ref_rgb, fov, H, W, **kwargs):
