@@ -37,7 +37,7 @@ extern "C" {
  * (marching cubes), Part 9 (texture baking), Part 10 (GroupNorm), Part 12 (the Canny detector), Part 1's
  * mi3d_composite_rays_train_backward_depth and mi3d_march_train_plan and the hash grid's input gradients (mi3d_hashgrid_backward_input of Part 2,
  * mi3d_grid_points_backward_input of Part 3) and their second-order passes (mi3d_hashgrid_backward_input_backward,
- * mi3d_grid_points_backward_input_backward) and Parts 11 and 13 to 16 were added under 5: new symbols only, nothing
+ * mi3d_grid_points_backward_input_backward) and Parts 11 and 13 to 17 were added under 5: new symbols only, nothing
  * existing changed. */
 int mi3d_abi_version(void);
 const char *mi3d_last_error_string(int err);
@@ -1012,6 +1012,67 @@ int mi3d_mesh_smooth(const float *vertices, unsigned long long nv, const int32_t
                      uint32_t iterations, double lambda, double mu, int pin_border, float max_move,
                      uint32_t fraction_bits, void *ws, size_t ws_bytes, float *out_vertices, unsigned long long *counts,
                      void *stream);
+
+/* ------------------------------------------------------------------ Part 17: rendering the mesh (mesh export) */
+
+/* A rasteriser for the exported mesh: per view the nearest triangle at every pixel centre (a visibility buffer), and a
+ * shading pass that turns it into an image from vertex colours or from Part 9's atlas and its 8-bit texture - the
+ * forward half of what nvdiffrast does for the reference's export, there in UV space only (nerf/renderer.py:193-299);
+ * what an external viewer shows of mesh.obj, mesh.mtl and albedo.png.  This contract is this project's own - PARITY
+ * UNPINNED, the standing of Parts 8, 9 and 13 to 16.  Added under ABI version 5: new symbols only.  (Declared ahead of
+ * the point-cloud part, like Parts 12 to 16.)
+ *
+ * ARITHMETIC: Part 15's rules - binary32, every operation rounded separately, three-term sums ((t0 + t1) + t2), no
+ * sqrt, no transcendental function; a NumPy float32 restatement gives the same bits.  Part 15's VIEWS records,
+ * PROJECTION, pixel centres, bounding-box walk, EDGE FUNCTION, coverage test and DEPTH d are used as they stand there
+ * (one definition in the source, shared with mi3d_mesh_depth).
+ *
+ * VISIBILITY (mi3d_mesh_visibility): vis uint64[V][H][W], 8-byte aligned; counts uint64[2] as mi3d_mesh_depth's ([0]
+ * triangles with an index outside [0, nv), once; [1] (triangle, view) pairs left out for a z <= 0 or a non-finite
+ * value), zeroed in-stream.  One fill launch writes all-ones; one launch with thread = (triangle, view) does, for
+ * exactly the pixels and the d that mi3d_mesh_depth would write, an unsigned 64-bit atomicMin with the key
+ * (bits(d) << 32) | triangle_index, its result unused.  0 < d < inf, so the upper word orders like the depth and never
+ * is all-ones; EQUAL DEPTHS RESOLVE TO THE SMALLER TRIANGLE INDEX - a rule, not an accident.  Order-independent: two
+ * runs give identical bytes.  The upper word of a key equals the bits mi3d_mesh_depth writes at that pixel.  nt <=
+ * 2^31 - 1 (the index is also an int32 output below).
+ *
+ * SHADING (mi3d_mesh_shade): thread = pixel of [V][H][W]; no atomics: two runs give identical bytes.
+ *   - A pixel whose key is all-ones gets image = background (HOST float[3], read when the call is made), alpha 0,
+ *     depth +inf, tri -1, bary 0 0 0, normal 0 0 0.  So does a key whose triangle index is not below nt or whose
+ *     triangle has a vertex index outside [0, nv): no pass above writes one, and it is never dereferenced.
+ *   - Otherwise the triangle's three vertices are projected again and w0, w1, w2, s recomputed at the pixel centre - the
+ *     operations of the visibility pass, so s != 0.  b_k = w_k / s, r_k = b_k / z_k, S = (r0 + r1) + r2, d = 1 / S (the
+ *     bits of the key's upper word), lambda_k = r_k d: the perspective-correct weights.  An attribute a with the values
+ *     a0, a1, a2 at the corners is ((lambda0 a0 + lambda1 a1) + lambda2 a2).
+ *   - COLOUR, exactly one source: (a) colors float[nv][3], interpolated; (b) vt float[3 nt][2] (Part 9's unshared
+ *     corners, vt index 3 i + k) with texture uint8[T][T][3] (row 0 the top row), T in [64, 16384]: (u, v) interpolated,
+ *     gx = u T - 0.5, gy = (1 - v) T - 0.5 (the inverse of Part 9's vt = ((X + 0.5) / T, 1 - (Y + 0.5) / T)),
+ *     i0 = min(max(floor(gx), 0), T - 2), fx = min(max(gx - i0, 0), 1) (a NaN gives 0 in both), the same in y (j0, fy);
+ *     the taps c_ab at texel (i0 + a, j0 + b) converted to float; hx = 1 - fx, hy = 1 - fy, top = c00 hx + c10 fx,
+ *     bot = c01 hx + c11 fx, c = top hy + bot fy (Part 15's blend); colour = c / 255.  No mip-mapping.
+ *   - OUTPUTS: image float[V][H][W][3]; and, each written only if its pointer is not NULL, normal float[V][H][W][3] (vn
+ *     float[nv][3] interpolated, NOT normalised; needs vn), depth float[V][H][W] (d), tri int32[V][H][W], bary
+ *     float[V][H][W][3] (lambda), alpha uint8[V][H][W] (1 where a triangle is drawn).
+ *
+ * ERROR AGAINST EXACT ARITHMETIC (what tests/test_mesh_render_cpu.py counts; u = 2^-24), by Part 15's method: on top of
+ * the bounds of w_k, s and d there, b_k has the relative error of w_k and s plus one rounding, r_k that of z_k plus one
+ * more, lambda_k that of d plus one more; an interpolated attribute adds 3 u sum |lambda_k a_k| to
+ * sum |a_k| E(lambda_k).  Out of scope: clipping at a near plane (Part 15's rule stands: a triangle with a corner at
+ * z <= 0 is left out of the view), splitting a large triangle across threads, mip-mapping, gradients.
+ *
+ * Neither entry point allocates or synchronises.  V, H, W outside Part 15's ranges, a T outside Part 9's with a texture,
+ * nv or nt above 2^31 - 1, a vis or counts that is NULL or not 8-byte aligned, a NULL views, background or image, both
+ * colour sources or neither, one of vt and texture without the other, a normal without vn, and NULL triangles (with
+ * nt > 0) or vertices (with nt > 0 and nv > 0) are refused (hipErrorInvalidValue) and launch nothing.  nt = 0 is
+ * accepted: the fill alone, and the background everywhere. */
+int mi3d_mesh_visibility(const float *vertices, unsigned long long nv, const int32_t *triangles, unsigned long long nt,
+                         const float *views, uint32_t V, uint32_t H, uint32_t W, unsigned long long *vis,
+                         unsigned long long *counts, void *stream);
+int mi3d_mesh_shade(const float *vertices, unsigned long long nv, const int32_t *triangles, unsigned long long nt,
+                    const float *views, uint32_t V, uint32_t H, uint32_t W, const unsigned long long *vis,
+                    const float *colors, const float *vt, const uint8_t *texture, uint32_t T, const float *vn,
+                    const float *background, float *image, float *normal, float *depth, int32_t *tri, float *bary,
+                    uint8_t *alpha, void *stream);
 
 /* ------------------------------------------------------------------ Part 11: the refine stage's point cloud */
 

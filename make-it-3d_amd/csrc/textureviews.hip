@@ -16,34 +16,17 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mi3d.h"
+#include "mi3d_meshraster.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr uint32_t kMinT = 64, kMaxT = 16384, kMinSide = 2, kMaxSide = 16384, kMaxViews = 64;
-constexpr int kView = 24;  // floats per view record: R[3][3], t[3], K[3][3], centre[3]
+constexpr uint32_t kMinT = 64, kMaxT = 16384;
+
+// the view record, the projection, the watertight edge function and the bounding-box walk: shared with meshrender.hip
+using namespace mi3d_meshraster;
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
-struct Projected {
-    float x, y, z;
-};
-
-// cam = R p + t, q = K cam, sums in index order; x = q0 / q2, y = q1 / q2, z = q2
-__device__ __forceinline__ Projected project(const float *__restrict__ view, float p0, float p1, float p2) {
-    float cam[3], q[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) cam[r] = ((view[3 * r] * p0 + view[3 * r + 1] * p1) + view[3 * r + 2] * p2) + view[9 + r];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) q[r] = (view[12 + 3 * r] * cam[0] + view[12 + 3 * r + 1] * cam[1]) + view[12 + 3 * r + 2] * cam[2];
-    Projected o;
-    o.x = q[0] / q[2];
-    o.y = q[1] / q[2];
-    o.z = q[2];
-    return o;
-}
-
-__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) < __builtin_inff(); }  // false for NaN
 
 __global__ __launch_bounds__(kBlock) void k_depth_fill(float *__restrict__ depth, size_t n,
                                                        unsigned long long *__restrict__ counts) {
@@ -55,63 +38,15 @@ __global__ __launch_bounds__(kBlock) void k_depth_fill(float *__restrict__ depth
     if (i < n) depth[i] = __builtin_inff();
 }
 
-// the edge function of the directed edge a -> b at (px, py), evaluated on the endpoints in ascending vertex-index order
-// and negated for the other direction: two triangles that share an edge by index see exactly opposite values
-__device__ __forceinline__ float edge_fn(int32_t ia, const Projected &a, int32_t ib, const Projected &b, float px, float py) {
-    const bool fwd = ia <= ib;
-    const Projected &lo = fwd ? a : b, &hi = fwd ? b : a;
-    const float e = (hi.x - lo.x) * (py - lo.y) - (hi.y - lo.y) * (px - lo.x);
-    return fwd ? e : -e;
-}
-
 __global__ __launch_bounds__(kBlock) void k_mesh_depth(const float *__restrict__ vertices, uint32_t nv,
                                                        const int32_t *__restrict__ triangles, uint32_t nt,
                                                        const float *__restrict__ views, uint32_t H, uint32_t W,
                                                        float *__restrict__ depth, unsigned long long *__restrict__ counts) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x, v = blockIdx.y;
     if (i >= nt) return;
-    const int32_t *t = triangles + (size_t)i * 3;
-    const int32_t id[3] = {t[0], t[1], t[2]};
-    if (!((uint32_t)id[0] < nv && (uint32_t)id[1] < nv && (uint32_t)id[2] < nv)) {
-        if (v == 0) atomicAdd(counts, 1ull);  // a bad triangle is counted once, not once per view
-        return;
-    }
-    const float *view = views + (size_t)v * kView;
-    Projected P[3];
-    bool drawn = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float *p = vertices + (size_t)id[k] * 3;
-        P[k] = project(view, p[0], p[1], p[2]);
-        drawn = drawn && P[k].z > 0.0f && finite_f(P[k].z) && finite_f(P[k].x) && finite_f(P[k].y);
-    }
-    if (!drawn) {
-        atomicAdd(counts + 1, 1ull);
-        return;
-    }
-    // pixel (i, j) has its centre at (i + 0.5, j + 0.5): the centres inside the bounding box, clipped to the image
-    const float xlo = fmaxf(ceilf(fminf(fminf(P[0].x, P[1].x), P[2].x) - 0.5f), 0.0f);
-    const float xhi = fminf(floorf(fmaxf(fmaxf(P[0].x, P[1].x), P[2].x) - 0.5f), (float)(W - 1));
-    const float ylo = fmaxf(ceilf(fminf(fminf(P[0].y, P[1].y), P[2].y) - 0.5f), 0.0f);
-    const float yhi = fminf(floorf(fmaxf(fmaxf(P[0].y, P[1].y), P[2].y) - 0.5f), (float)(H - 1));
-    if (!(xlo <= xhi && ylo <= yhi)) return;
-    const uint32_t i0 = (uint32_t)xlo, i1 = (uint32_t)xhi, j0 = (uint32_t)ylo, j1 = (uint32_t)yhi;  // within [0, W) x [0, H)
     uint32_t *out = reinterpret_cast<uint32_t *>(depth) + (size_t)v * H * W;
-    for (uint32_t j = j0; j <= j1; ++j) {         // at most H * W iterations in all: the box lies in the image
-        const float py = (float)j + 0.5f;
-        for (uint32_t ii = i0; ii <= i1; ++ii) {
-            const float px = (float)ii + 0.5f;
-            const float w0 = edge_fn(id[1], P[1], id[2], P[2], px, py);
-            const float w1 = edge_fn(id[2], P[2], id[0], P[0], px, py);
-            const float w2 = edge_fn(id[0], P[0], id[1], P[1], px, py);
-            const bool covered = (w0 >= 0.0f && w1 >= 0.0f && w2 >= 0.0f) || (w0 <= 0.0f && w1 <= 0.0f && w2 <= 0.0f);
-            const float s = (w0 + w1) + w2;
-            if (!covered || !(s != 0.0f)) continue;  // s == 0 or NaN: no area
-            const float d = 1.0f / (((w0 / s) / P[0].z + (w1 / s) / P[1].z) + (w2 / s) / P[2].z);
-            if (!(d > 0.0f) || !finite_f(d)) continue;
-            atomicMin(out + (size_t)j * W + ii, __float_as_uint(d));
-        }
-    }
+    raster_triangle(vertices, nv, triangles, i, v, views, H, W, counts,
+                    [out](size_t at, float d) { atomicMin(out + at, __float_as_uint(d)); });
 }
 
 struct ProjectArgs {
@@ -198,10 +133,6 @@ __global__ __launch_bounds__(kBlock) void k_texture_project(ProjectArgs a) {
         for (int d = 0; d < 3; ++d) o[d] = seen ? sc[d] / sw : b[d];
         a.hits[sample] = (uint8_t)hits;
     }
-}
-
-bool views_ok(uint32_t V, uint32_t H, uint32_t W) {
-    return V >= 1 && V <= kMaxViews && H >= kMinSide && H <= kMaxSide && W >= kMinSide && W <= kMaxSide;
 }
 
 }  // namespace

@@ -124,6 +124,10 @@ _SIGNATURES = {
     # Part 16 -----------------------------------------------------------------------------------------
     "mi3d_mesh_smooth": [vp, C.c_uint64, vp, C.c_uint64, u32, C.c_double, C.c_double, C.c_int, f32, u32, vp, C.c_size_t,
                          vp, vp, vp],
+    # Part 17 -----------------------------------------------------------------------------------------
+    "mi3d_mesh_visibility": [vp, C.c_uint64, vp, C.c_uint64, vp, u32, u32, u32, vp, vp, vp],
+    "mi3d_mesh_shade": [vp, C.c_uint64, vp, C.c_uint64, vp, u32, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp,
+                        vp, vp],
 }
 
 # host-only queries whose return value is not a hipError_t: (argtypes, restype), bound in lib() like the block below

@@ -20,6 +20,10 @@
   render_depth     the depth maps of a mesh from V pinhole cameras (csrc/textureviews.hip, include/mi3d.h Part 15)
   bake_views       the same atlas coloured from views by projection: per sample the visibility-tested, angle-weighted
                    mean of the views that see it, the field's albedo where none does (Part 15)
+  render           images of a mesh from V pinhole cameras (csrc/meshrender.hip, include/mi3d.h Part 17): a visibility buffer
+                   per view, then per pixel the perspective-correct vertex colour or atlas texture, normals, depth,
+                   triangle index and barycentrics; the field's shadings composed in torch
+  fidelity         PSNR over the union and the intersection of two renders' masks and the masks' IoU, per view and overall
   export           volume -> surface -> per-vertex albedo (-> texture) -> files; what `NeRFRenderer.export_mesh` calls
   write_obj        vertex-coloured OBJ (`v x y z r g b`) + the reference's `mat0` material; with UVs `v` / `vt` /
                    `f v/vt` and `map_Kd`; with normals `vn` lines and `f v//vn` / `f v/vt/vn`
@@ -742,6 +746,284 @@ def bake_views(model_or_base, vertices, triangles, texture_size, images, c2w, K,
     return image, vt, owner, hits
 
 
+SHADINGS = ("albedo", "lambertian", "textureless", "normal")
+PREVIEW_KEYS = ("c2w", "K", "H", "W", "shading", "ssaa", "fidelity")
+
+
+def _check_shading(shading, ssaa):
+    if not isinstance(shading, str) or shading not in SHADINGS:
+        raise Mi3dError(f"shading must be one of {SHADINGS} (got {shading!r})")
+    if isinstance(ssaa, (bool, np.bool_)) or not isinstance(ssaa, (int, np.integer)) or ssaa not in SSAA:
+        raise Mi3dError(f"ssaa must be one of {SSAA} (got {ssaa!r})")
+    return shading, int(ssaa)
+
+
+def _check_render_options(ambient_ratio, bg_color, light_d, V):
+    """The arguments of render() that need no tensor: (ambient, background float32 [3], light [V, 3] float32 or None)."""
+    ambient = _number(ambient_ratio, "ambient_ratio", 0.0, 1.0)
+    bg = np.asarray(bg_color, dtype=np.float64).reshape(-1)
+    if bg.size not in (1, 3) or not np.isfinite(bg).all():
+        raise Mi3dError(f"bg_color must be one finite number or three (got {bg_color!r})")
+    bg = np.broadcast_to(bg, (3,)).astype(np.float32)
+    if light_d is not None:
+        light_d = _host64(light_d)
+        if light_d.shape not in ((3,), (V, 3)) or not np.isfinite(light_d).all() or not (light_d * light_d).sum(-1).all():
+            raise Mi3dError(f"light_d must be 3 finite numbers or [{V}, 3], none of them a zero vector (got {light_d.shape})")
+        light_d = np.broadcast_to(light_d / np.linalg.norm(light_d, axis=-1, keepdims=True), (V, 3)).astype(np.float32)
+    return ambient, bg, light_d
+
+
+def _render_buffers(vertices, triangles, records, H, W, colors=None, uvs=None, texture=None, normals=None,
+                    bg=(1.0, 1.0, 1.0)):
+    """mi3d_mesh_visibility and mi3d_mesh_shade on the current stream, nothing read back: a dict of vis int64 [V, H, W]
+    (the uint64 keys), counts int64 [2], image float32 [V, H, W, 3], alpha uint8 [V, H, W], depth, tri int32, bary and
+    normal (None without `normals`).  `records` float32 [V, 24] on the mesh's device; the arguments are checked by the
+    callers."""
+    dev, V = vertices.device, int(records.shape[0])
+    nv, nt = int(vertices.shape[0]), int(triangles.shape[0])
+    vis = torch.empty(V, H, W, dtype=torch.int64, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    _lib.launch("mi3d_mesh_visibility", vertices, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, _lib.ptr(records), V, H,
+                W, _lib.ptr(vis), _lib.ptr(counts))
+    out = dict(vis=vis, counts=counts,
+               image=torch.empty(V, H, W, 3, dtype=torch.float32, device=dev),
+               alpha=torch.empty(V, H, W, dtype=torch.uint8, device=dev),
+               depth=torch.empty(V, H, W, dtype=torch.float32, device=dev),
+               tri=torch.empty(V, H, W, dtype=torch.int32, device=dev),
+               bary=torch.empty(V, H, W, 3, dtype=torch.float32, device=dev),
+               normal=None if normals is None else torch.empty(V, H, W, 3, dtype=torch.float32, device=dev))
+    T = 0 if texture is None else int(texture.shape[0])
+    background = (C.c_float * 3)(*[float(b) for b in bg])
+    _lib.launch("mi3d_mesh_shade", vertices, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, _lib.ptr(records), V, H, W,
+                _lib.ptr(vis), _lib.ptr(colors), _lib.ptr(uvs), _lib.ptr(texture), T, _lib.ptr(normals), background,
+                _lib.ptr(out["image"]), _lib.ptr(out["normal"]), _lib.ptr(out["depth"]), _lib.ptr(out["tri"]),
+                _lib.ptr(out["bary"]), _lib.ptr(out["alpha"]))
+    return out
+
+
+def box_average(x, ssaa):
+    """[V, ssaa H, ssaa W, ...] -> [V, H, W, ...]: the float32 sum of a pixel's ssaa^2 sub-pixels, rows first and columns
+    within a row, times 1 / ssaa^2 (Part 9's order for a texel's samples); ssaa = 1 returns x."""
+    if ssaa == 1:
+        return x
+    V, H, W = x.shape[0], x.shape[1] // ssaa, x.shape[2] // ssaa
+    x = x.reshape(V, H, ssaa, W, ssaa, *x.shape[3:])
+    s = x[:, :, 0, :, 0]
+    for k in range(1, ssaa * ssaa):
+        s = s + x[:, :, k // ssaa, :, k % ssaa]
+    return s * (1.0 / (ssaa * ssaa))
+
+
+def render(vertices, triangles, c2w, K, H, W, colors=None, uvs=None, texture=None, normals=None, shading="albedo",
+           light_d=None, ambient_ratio=0.1, bg_color=1.0, ssaa=1, return_buffers=False):
+    """Images of an indexed mesh from V pinhole cameras (include/mi3d.h Part 17): vertices float32 [nv, 3], triangles
+    int32 [nt, 3] on the GPU; c2w [V, 4, 4], K [3, 3], H, W as render_depth takes them.  The colour comes from exactly one
+    of `colors` float32 [nv, 3] (per vertex, interpolated perspective-correctly) and `uvs` float32 [3 nt, 2] with
+    `texture` uint8 [T, T, 3] (what bake_texture and bake_views return: bilinear taps, row 0 the top row); all on the
+    mesh's device.  `normals` float32 [nv, 3] are interpolated too and needed by every shading but "albedo".
+
+    `shading` as the field's (the reference's nerf/network_tcnn.py:159-168), composed in torch from the kernel's albedo
+    and normal buffers, n the normalised interpolated normal and l `light_d` (3 numbers or [V, 3], normalised here;
+    None: from the origin towards each camera): "albedo" the colour as it is (bit for bit the kernel's image),
+    "lambertian" the colour times ambient_ratio + (1 - ambient_ratio) clamp(n . l, min=0.1), "textureless" that factor
+    alone, "normal" (n + 1) / 2.  A pixel no triangle covers is `bg_color` (a number or three).  `ssaa` in {1, 2, 4}
+    renders ssaa H x ssaa W pixels with K scaled and box-averages them (box_average).
+
+    Returns (image float32 [V, H, W, 3], alpha float32 [V, H, W]: the covered share of the pixel, 0 or 1 without
+    supersampling); with `return_buffers=True` also a dict of depth float32 (+inf where nothing is drawn), tri int32
+    (-1 there), bary float32 [.., 3] and normal (un-normalised; None without `normals`), at the ssaa H x ssaa W the
+    kernels ran at.  Nothing is clipped: a triangle with a vertex at z <= 0 is left out of that view.  A triangle index
+    outside [0, nv) raises Mi3dError.  Every argument is checked before anything is launched."""
+    shading, ssaa = _check_shading(shading, ssaa)
+    H, W = int(H), int(W)
+    Ks = _host64(K)
+    if Ks.shape == (3, 3):
+        Ks = Ks * np.array([[ssaa], [ssaa], [1.0]])             # the first two rows; exact: a power of two
+    records = view_records(c2w, Ks)
+    V = int(records.shape[0])
+    _check_view_size(V, H, W)
+    ambient, bg, light = _check_render_options(ambient_ratio, bg_color, light_d, V)
+    _check_view_size(V, ssaa * H, ssaa * W)
+    vertices, triangles = _check_mesh(vertices, triangles)
+    nv, nt, dev = int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
+    if (colors is None) == (uvs is None and texture is None):
+        raise Mi3dError("render takes exactly one colour source: colors, or uvs with texture")
+    if colors is not None:
+        colors = _lib.dev_f32(colors, "colors", 3)
+        if tuple(colors.shape) != (nv, 3) or colors.device != dev:
+            raise Mi3dError(f"colors must be [{nv}, 3] on the mesh's device (got {tuple(colors.shape)} on {colors.device})")
+    else:
+        if uvs is None or texture is None:
+            raise Mi3dError("uvs and texture go together")
+        uvs = _lib.dev_f32(uvs, "uvs", 2)
+        if not isinstance(texture, torch.Tensor):
+            raise TypeError("texture must be a torch.Tensor")
+        texture = _lib.dev_typed(texture, "texture", torch.uint8)
+        if tuple(uvs.shape) != (3 * nt, 2) or uvs.device != dev:
+            raise Mi3dError(f"uvs must be [{3 * nt}, 2] on the mesh's device (got {tuple(uvs.shape)} on {uvs.device})")
+        if texture.dim() != 3 or texture.shape[0] != texture.shape[1] or texture.shape[2] != 3 or texture.device != dev or \
+                not MIN_TEXTURE <= texture.shape[0] <= MAX_TEXTURE:
+            raise Mi3dError(f"texture must be [T, T, 3] with T in [{MIN_TEXTURE}, {MAX_TEXTURE}] on the mesh's device (got "
+                            f"{tuple(texture.shape)} on {texture.device})")
+    if normals is not None:
+        normals = _lib.dev_f32(normals, "normals", 3)
+        if tuple(normals.shape) != (nv, 3) or normals.device != dev:
+            raise Mi3dError(f"normals must be [{nv}, 3] on the mesh's device (got {tuple(normals.shape)} on {normals.device})")
+    elif shading != "albedo":
+        raise Mi3dError(f"shading={shading!r} needs normals")
+    buf = _render_buffers(vertices, triangles, torch.from_numpy(records).to(dev), ssaa * H, ssaa * W, colors, uvs, texture,
+                          normals, bg)
+    bad = int(buf["counts"][0])                                 # the one host read
+    if bad != 0:
+        raise Mi3dError(f"{bad} of the {nt} triangles hold a vertex index outside [0, {nv})")
+    image, covered = buf["image"], buf["alpha"] != 0
+    if shading != "albedo":
+        n = buf["normal"]
+        n = n / torch.sqrt(torch.clamp((n * n).sum(-1, keepdim=True), min=1e-20))
+        if light is None:
+            light = records[:, 21:24].astype(np.float64)
+            norm = np.linalg.norm(light, axis=-1, keepdims=True)
+            light = np.where(norm > 0, light / np.where(norm > 0, norm, 1.0), [0.0, 0.0, 1.0]).astype(np.float32)
+        l = torch.from_numpy(np.ascontiguousarray(light)).to(dev)[:, None, None, :]
+        lambertian = ambient + (1.0 - ambient) * (n * l).sum(-1, keepdim=True).clamp(min=0.1)
+        shaded = {"lambertian": image * lambertian, "textureless": lambertian.expand_as(image), "normal": (n + 1.0) / 2.0}
+        image = torch.where(covered[..., None], shaded[shading], torch.from_numpy(bg).to(dev))
+    image, alpha = box_average(image, ssaa), box_average(covered.float(), ssaa)
+    if return_buffers:
+        return image, alpha, {k: buf[k] for k in ("depth", "tri", "bary", "normal")}
+    return image, alpha
+
+
+def fidelity(image_a, alpha_a, image_b, alpha_b):
+    """How far two sets of renders from the same cameras are apart: images [V, H, W, 3] in [0, 1] and alphas [V, H, W]
+    (a pixel belongs to a render's mask iff its alpha > 0.5), tensors or NumPy arrays.  Returns a dict of floats:
+    `psnr_union` = 10 log10(1 / mse) with the mean over the three channels of the pixels in EITHER mask (what differs in
+    silhouette counts), `psnr_intersection` the same over the pixels in BOTH (colour alone), `iou` = |both| / |either|
+    of the masks; and `views`, a list of the same three per view.  The overall figures pool the pixels of all views.
+    Equal images give +inf; an empty set of pixels gives nan.  Plain torch in float64."""
+    def t(a):
+        a = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+        return a.detach().to(torch.float64)
+    image_a = t(image_a)
+    image_b, alpha_a, alpha_b = (t(a).to(image_a.device) for a in (image_b, alpha_a, alpha_b))
+    if image_a.dim() != 4 or image_a.shape[3] != 3 or image_b.shape != image_a.shape or \
+            alpha_a.shape != image_a.shape[:3] or alpha_b.shape != image_a.shape[:3]:
+        raise Mi3dError(f"fidelity takes images [V, H, W, 3] and alphas [V, H, W] of one size (got {tuple(image_a.shape)}, "
+                        f"{tuple(alpha_a.shape)}, {tuple(image_b.shape)}, {tuple(alpha_b.shape)})")
+    ma, mb = alpha_a > 0.5, alpha_b > 0.5
+    se = ((image_a - image_b) ** 2).sum(-1)                     # per pixel, the three channels summed
+
+    def figures(se, either, both):
+        def psnr(m):
+            n = int(m.sum())
+            if n == 0:
+                return float("nan")
+            mse = float(se[m].sum()) / (3 * n)
+            return float("inf") if mse == 0.0 else float(10.0 * np.log10(1.0 / mse))
+        ne = int(either.sum())
+        return {"psnr_union": psnr(either), "psnr_intersection": psnr(both),
+                "iou": float("nan") if ne == 0 else int(both.sum()) / ne}
+
+    out = figures(se, ma | mb, ma & mb)
+    out["views"] = [figures(se[v], (ma | mb)[v], (ma & mb)[v]) for v in range(image_a.shape[0])]
+    return out
+
+
+def quantise(image):
+    """Part 9's quantisation of a float image in [0, 1] to uint8: min(255, floor(a * 255)) in float32, 0 for a negative
+    value or a NaN - what write_png is given for the previews."""
+    a = torch.nan_to_num(image.float() * 255.0, nan=0.0, posinf=255.0, neginf=0.0)
+    return a.floor().clamp(0.0, 255.0).to(torch.uint8)
+
+
+def camera_rays(c2w, K, H, W, device):
+    """Rays through the pixel centres of pinhole cameras: a point at depth z along the ray of pixel (i, j) projects, by
+    Part 15's PROJECTION with these c2w and K, to (i + 0.5, j + 0.5).  Returns (origins, unit directions) float32
+    [V, H W, 3] on `device`; the directions are K^-1 (i + 0.5, j + 0.5, 1) rotated by c2w, computed in binary64 and
+    rounded once."""
+    c2w, K = _host64(c2w), _host64(K)
+    j, i = np.meshgrid(np.arange(H) + 0.5, np.arange(W) + 0.5, indexing="ij")
+    cam = np.stack([i.ravel(), j.ravel(), np.ones(H * W)], -1) @ np.linalg.inv(K).T
+    d = cam @ c2w[:, :3, :3].transpose(0, 2, 1)
+    d = d / np.linalg.norm(d, axis=-1, keepdims=True)
+    o = np.broadcast_to(c2w[:, None, :3, 3], d.shape)
+    return (torch.from_numpy(np.ascontiguousarray(o, dtype=np.float32)).to(device),
+            torch.from_numpy(d.astype(np.float32)).to(device))
+
+
+def render_field(model, c2w, K, H, W):
+    """The field's own renders from the cameras render() takes: the eval route (no perturbation, all rays, albedo) over
+    a white background, rays by camera_rays.  Returns (image float32 [V, H, W, 3], alpha float32 [V, H, W]: the rays'
+    accumulated opacity) on the model's device."""
+    dev = model.aabb_train.device
+    ro, rd = camera_rays(c2w, K, H, W, dev)
+    was_training = model.training
+    model.eval()
+    images, alphas = [], []
+    try:
+        with torch.no_grad():
+            for v in range(ro.shape[0]):
+                out = model.render(ro[v:v + 1], rd[v:v + 1], staged=True, perturb=False, force_all_rays=True,
+                                   bg_color=torch.ones(3, device=dev), shading="albedo", ambient_ratio=1.0)
+                images.append(out["image"].reshape(H, W, 3).float())
+                alphas.append(out["weights_sum"].reshape(H, W).float())
+    finally:
+        model.train(was_training)
+    return torch.stack(images), torch.stack(alphas)
+
+
+def _check_preview(preview):
+    """export's `preview`: a dict of PREVIEW_KEYS, checked on the host; returns it with the defaults filled in."""
+    if not isinstance(preview, dict):
+        raise Mi3dError(f"preview must be a dict with the keys {PREVIEW_KEYS[:4]} and optionally {PREVIEW_KEYS[4:]} (got "
+                        f"{type(preview).__name__})")
+    unknown = sorted(set(preview) - set(PREVIEW_KEYS))
+    missing = [k for k in PREVIEW_KEYS[:4] if k not in preview]
+    if unknown or missing:
+        raise Mi3dError(f"preview: unknown keys {unknown}, missing keys {missing}; it takes {PREVIEW_KEYS}")
+    p = dict(shading="albedo", ssaa=1, fidelity=False)
+    p.update(preview)
+    for k in ("H", "W"):
+        if isinstance(p[k], (bool, np.bool_)) or not isinstance(p[k], (int, np.integer)):
+            raise Mi3dError(f"preview: {k} must be an integer (got {p[k]!r})")
+    V = view_records(p["c2w"], p["K"]).shape[0]
+    _check_view_size(V, int(p["H"]), int(p["W"]))
+    p["shading"], p["ssaa"] = _check_shading(p["shading"], p["ssaa"])
+    _check_view_size(V, p["ssaa"] * int(p["H"]), p["ssaa"] * int(p["W"]))
+    if not isinstance(p["fidelity"], (bool, np.bool_)):
+        raise Mi3dError(f"preview: fidelity must be a bool (got {p['fidelity']!r})")
+    if p["fidelity"] and p["shading"] != "albedo":
+        raise Mi3dError("preview: fidelity compares albedo renders: give shading='albedo' with it")
+    return p
+
+
+def _json_number(x):
+    return x if np.isfinite(x) else None                       # JSON has no inf and no nan
+
+
+def _write_preview(path, model, p, vertices, triangles, albedo, vt, image, vn):
+    """export's preview step: the final mesh rendered as it is written - with its texture, or its vertex colours -
+    to `preview_000.png` ...; with fidelity also the field's renders from the same cameras and `preview.json`."""
+    import json
+    if p["shading"] != "albedo" and vn is None:
+        vn = vertex_normals(model, vertices).contiguous()
+    source = dict(colors=albedo.contiguous()) if image is None else dict(uvs=vt, texture=image)
+    rendered, alpha = render(vertices, triangles, p["c2w"], p["K"], p["H"], p["W"], normals=vn, shading=p["shading"],
+                             ssaa=p["ssaa"], **source)
+    os.makedirs(path, exist_ok=True)
+    for v, img in enumerate(quantise(rendered).cpu().numpy()):
+        write_png(os.path.join(path, f"preview_{v:03d}.png"), img)
+    if p["fidelity"]:
+        field, field_alpha = render_field(model, p["c2w"], p["K"], int(p["H"]), int(p["W"]))
+        report = fidelity(rendered, alpha, field, field_alpha)
+        report = {k: [{a: _json_number(b) for a, b in r.items()} for r in x] if k == "views" else _json_number(x)
+                  for k, x in report.items()}
+        report.update(H=int(p["H"]), W=int(p["W"]), ssaa=int(p["ssaa"]), a="mesh", b="field")
+        with open(os.path.join(path, "preview.json"), "w") as fp:
+            json.dump(report, fp, indent=1)
+            fp.write("\n")
+
+
 MTL = ("newmtl mat0 \n"
        "Ka 1.000000 1.000000 1.000000 \n"
        "Kd 1.000000 1.000000 1.000000 \n"
@@ -845,10 +1127,12 @@ def vertex_normals(model, vertices):
 
 
 def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False, min_faces=None,
-           min_diagonal=None, largest=False, decimate=None, target_faces=None, views=None, smooth=None):
+           min_diagonal=None, largest=False, decimate=None, target_faces=None, views=None, smooth=None, preview=None):
     """What NeRFRenderer.export_mesh does (see there).  `S` only sizes the reference's chunks and is ignored."""
     del S
     smoothing = _check_smooth_option(smooth)                    # before any work
+    if preview is not None:                                     # before any work
+        preview = _check_preview(preview)
     if views is not None:                                       # before any work
         if texture_size is None:
             raise Mi3dError("export_mesh: views colour the texture: give texture_size too")
@@ -893,6 +1177,10 @@ def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, norma
         elif texture_size is not None:
             image, vt, _ = bake_texture(model, vertices, triangles, texture_size, ssaa)
         vn = vertex_normals(model, vertices).cpu().numpy() if normals else None
+        if preview is not None:                                 # the mesh as it is written: after the bake
+            textured = texture_size is not None
+            _write_preview(path, model, preview, vertices, triangles, albedo, vt if textured else None,
+                           image if textured else None, None if vn is None else torch.from_numpy(vn).to(vertices.device))
     v, f, c = vertices.cpu().numpy(), triangles.cpu().numpy(), albedo.cpu().numpy()
     last = () if vn is None else (vn,)
     if texture_size is None:

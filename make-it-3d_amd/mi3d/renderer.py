@@ -118,7 +118,8 @@ class NeRFRenderer(nn.Module):
 
     @torch.no_grad()
     def export_mesh(self, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False, min_faces=None,
-                    min_diagonal=None, largest=False, decimate=None, target_faces=None, views=None, smooth=None):
+                    min_diagonal=None, largest=False, decimate=None, target_faces=None, views=None, smooth=None,
+                    preview=None):
         """renderer.py:157-191 + the file writing of :300-328, reached through main.py's `--save_mesh`: sigma on the
         `resolution`^3 lattice of [-1, 1]^3 (default grid_size), marching cubes at min(mean_density, density_thresh)
         (density_thresh without cuda_ray) on the GPU (mi3d.mesh), `<path>/mesh.obj` + `mesh.mtl`.  By default
@@ -159,11 +160,21 @@ class NeRFRenderer(nn.Module):
         project's meshes), `pin_border` to True; `max_move` (None: no limit) is in grid steps of the extraction lattice
         and keeps every coordinate within that distance of the extracted surface.  `normals=True` stays the FIELD's
         analytic normal, now evaluated at the moved vertex: it is not the normal of the smoothed triangles.  With
-        `smooth=None` nothing of this runs and the files are byte for byte what they were without the argument."""
+        `smooth=None` nothing of this runs and the files are byte for byte what they were without the argument.
+        `preview=dict(c2w=, K=, H=, W=, shading="albedo", ssaa=1, fidelity=False)` renders the final mesh as it is
+        written - with its texture, or with its vertex colours when `texture_size` is None - from those pinhole cameras
+        (mesh.render, include/mi3d.h Part 17; c2w [V, 4, 4] and K [3, 3] as `views` takes them) and writes
+        `preview_000.png` ... beside the mesh; `ssaa` in {1, 2, 4} supersamples, `shading` is mesh.render's (every one
+        but "albedo" evaluates the field's analytic normals).  With `fidelity=True` the field itself is rendered from
+        the same cameras (eval route, white background, rays through the pixel centres K names) and `preview.json` holds
+        mesh.fidelity's figures for the pair: PSNR over the union and over the intersection of the two masks and the
+        masks' IoU, per view and overall (a figure that is not finite is written as null).  The option is checked before
+        any work; the return value does not change.  With `preview=None` nothing of this runs and the files are byte
+        for byte what they were without the argument."""
         from . import mesh
         return mesh.export(self, path, resolution, S, texture_size=texture_size, ssaa=ssaa, normals=normals,
                            min_faces=min_faces, min_diagonal=min_diagonal, largest=largest, decimate=decimate,
-                           target_faces=target_faces, views=views, smooth=smooth)
+                           target_faces=target_faces, views=views, smooth=smooth, preview=preview)
 
     @torch.no_grad()
     def export_point_cloud(self, outputdir, poses, ref_rgb, fov, H, W, **kwargs):
