@@ -10,7 +10,8 @@
 // wave reads 64 consecutive floats and its +y / +x neighbours are two more contiguous rows that the caches serve):
 //   k_mc_count     per point: the 3-bit mask of the crossing edges it OWNS (towards +x, +y, +z) and, where it is the min
 //                  corner of a cell, the triangle count of its case; block sums of both -> workspace
-//   k_mc_scan      one workgroup: exclusive scan of the block sums in place, totals -> counts
+//   k_mc_scan      one workgroup: exclusive scan of the block sums in place (scan_row of mi3d_scan.h, once per row),
+//                  totals -> counts
 //   k_mc_vertices  masks again, block scan, vertex `block base + rank` written, first vertex id of every point -> workspace
 //   k_mc_triangles cases again, block scan, triangles written; a corner on cube edge e is vertex
 //                  first_id[owner] + popcount(mask[owner] & ((1 << axis) - 1)), the owner's lower mask bits recomputed
@@ -20,8 +21,11 @@
 
 #include "../../include/mi3d.h"
 #include "mi3d_mc_tables.h"
+#include "mi3d_scan.h"
 
 namespace {
+
+using namespace mi3d_scan;
 
 constexpr int kBlock = 256, kWaves = kBlock / 64;
 constexpr uint32_t kMinDim = 2, kMaxDim = 1024;
@@ -32,8 +36,6 @@ __constant__ uint8_t d_corners[8][3] = MI3D_MC_CORNERS_INIT;
 __constant__ uint8_t d_edges[12][2] = MI3D_MC_EDGES_INIT;
 const int8_t h_tri[256][16] = MI3D_MC_TRI_INIT;
 const uint8_t h_ntri[256] = MI3D_MC_NTRI_INIT;
-
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 struct McDims {
     uint32_t Rx, Ry, Rz, n;  // n = Rx Ry Rz <= 2^30
@@ -93,28 +95,6 @@ __device__ __forceinline__ void split(McDims d, uint32_t p, uint32_t &i, uint32_
     i = r / d.Ry;
 }
 
-// exclusive scan over the workgroup (kBlock threads); returns the thread's rank, `total` the block sum
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t *wave_sum, uint32_t &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        before += w < wave ? wave_sum[w] : 0u;
-        total += wave_sum[w];
-    }
-    __syncthreads();  // wave_sum may be reused by a second scan
-    return before + incl - v;
-}
-
 __global__ __launch_bounds__(kBlock) void k_mc_count(const float *__restrict__ vol, McDims d, float iso, McWorkspace w) {
     __shared__ uint32_t wave_sum[kWaves];
     const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
@@ -126,50 +106,24 @@ __global__ __launch_bounds__(kBlock) void k_mc_count(const float *__restrict__ v
         if (i + 1 < d.Rx && j + 1 < d.Ry && k + 1 < d.Rz) nt = d_ntri[cell_case(vol, d, p, iso)];
     }
     uint32_t tv, tt;
-    block_scan(nv, wave_sum, tv);
-    block_scan(nt, wave_sum, tt);
+    block_scan<kWaves>(nv, wave_sum, tv);
+    block_scan<kWaves>(nt, wave_sum, tt);
     if (threadIdx.x == 0) {
         w.block_v[blockIdx.x] = tv;
         w.block_t[blockIdx.x] = tt;
     }
 }
 
-// exclusive scan of the block sums in place (at most 4 M of them: one workgroup looping); counts = {vertices,
-// triangles, 0 (elements emit could not place), 0}
-__global__ __launch_bounds__(1024) void k_mc_scan(McWorkspace w, uint32_t nb, unsigned long long *__restrict__ counts) {
-    __shared__ unsigned long long wave_v[16], wave_t[16];
-    __shared__ unsigned long long base_v, base_t;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) { base_v = 0; base_t = 0; }
-    __syncthreads();
-    for (uint32_t b0 = 0; b0 < nb; b0 += 1024) {
-        const uint32_t b = b0 + threadIdx.x;
-        const unsigned long long cv = b < nb ? w.block_v[b] : 0ull, ct = b < nb ? w.block_t[b] : 0ull;
-        unsigned long long iv = cv, it = ct;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned long long uv = __shfl_up(iv, off, 64), ut = __shfl_up(it, off, 64);
-            if (lane >= off) { iv += uv; it += ut; }
-        }
-        if (lane == 63) { wave_v[wave] = iv; wave_t[wave] = it; }
-        __syncthreads();
-        unsigned long long bv = 0, bt = 0, sv = 0, st = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            bv += q < wave ? wave_v[q] : 0ull; bt += q < wave ? wave_t[q] : 0ull;
-            sv += wave_v[q]; st += wave_t[q];
-        }
-        const unsigned long long ov = base_v + bv + iv - cv, ot = base_t + bt + it - ct;
-        if (b < nb) {
-            // vertex ids are int32 in the triangles: an offset past that range can never be placed (emit's cap is below it)
-            w.block_v[b] = ov > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)ov;
-            w.block_t[b] = ot;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) { base_v += sv; base_t += st; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { counts[0] = base_v; counts[1] = base_t; counts[2] = 0; counts[3] = 0; }
+// exclusive scan of both rows of block sums in place (at most 4 M sums each); counts = {vertices, triangles, 0
+// (elements emit could not place), 0}.  The vertex offsets fit 32 bits without a clamp: a grid point owns at most 3
+// edges and n <= 2^30 (kMaxDim), so they end at 3 * 2^30 < 2^32 at most.  Triangles: up to 5 per cell, 64 bits.
+__global__ __launch_bounds__(kRowThreads) void k_mc_scan(McWorkspace w, uint32_t nb,
+                                                         unsigned long long *__restrict__ counts) {
+    __shared__ uint32_t wave_v[kRowWaves], base_v;
+    __shared__ unsigned long long wave_t[kRowWaves], base_t;
+    const uint32_t nv = scan_row(w.block_v, nb, wave_v, &base_v);
+    const unsigned long long nt = scan_row(w.block_t, nb, wave_t, &base_t);
+    if (threadIdx.x == 0) { counts[0] = nv; counts[1] = nt; counts[2] = 0; counts[3] = 0; }
 }
 
 struct McFrame {
@@ -187,12 +141,10 @@ __global__ __launch_bounds__(kBlock) void k_mc_vertices(const float *__restrict_
         mask = owned_mask(vol, d, p, i, j, k, iso);
     }
     uint32_t total;
-    const uint32_t rank = block_scan(__popc(mask), wave_sum, total);
+    const uint32_t rank = block_scan<kWaves>(__popc(mask), wave_sum, total);
     if (p >= d.n) return;
-    const uint32_t base = w.block_v[blockIdx.x];
-    // 64-bit: the scan saturates an offset past 2^32 - 1; such ids lie beyond every cap (int32 ids) and are never placed
-    unsigned long long id = (unsigned long long)base + rank;
-    w.first_id[p] = id > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)id;
+    uint32_t id = w.block_v[blockIdx.x] + rank;  // at most 3 * 2^30 (see k_mc_scan): the three steps below fit too
+    w.first_id[p] = id;
     if (mask == 0) return;
     const float va = vol[p];
     const uint32_t stride[3] = {d.Ry * d.Rz, d.Rz, 1u};
@@ -229,7 +181,7 @@ __global__ __launch_bounds__(kBlock) void k_mc_triangles(const float *__restrict
         }
     }
     uint32_t total;
-    const uint32_t rank = block_scan(nt, wave_sum, total);
+    const uint32_t rank = block_scan<kWaves>(nt, wave_sum, total);
     if (nt == 0) return;
     const unsigned long long first = w.block_t[blockIdx.x] + rank;
     uint32_t dropped = 0;
@@ -263,7 +215,7 @@ bool mc_dims(uint32_t Rx, uint32_t Ry, uint32_t Rz, McDims &d) {
 bool mc_args(const void *vol, uint32_t Rx, uint32_t Ry, uint32_t Rz, const void *ws, size_t ws_bytes, const void *counts,
              McDims &d) {
     if (!mc_dims(Rx, Ry, Rz, d) || vol == nullptr || ws == nullptr || counts == nullptr) return false;
-    if ((reinterpret_cast<uintptr_t>(ws) & 7u) != 0 || (reinterpret_cast<uintptr_t>(counts) & 7u) != 0) return false;
+    if (!aligned8(ws) || !aligned8(counts)) return false;
     return ws_bytes >= mc_workspace_bytes(d.n);
 }
 
@@ -294,7 +246,8 @@ int mi3d_mc_scan(uint32_t Rx, uint32_t Ry, uint32_t Rz, void *ws, size_t ws_byte
                  void *stream) {
     McDims d;
     if (!mc_args(ws /* no volume here */, Rx, Ry, Rz, ws, ws_bytes, counts, d)) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, as_stream(stream), mc_carve(ws, d.n), mc_blocks(d.n), counts);
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(kRowThreads), 0, as_stream(stream), mc_carve(ws, d.n), mc_blocks(d.n),
+                       counts);
     return (int)hipGetLastError();
 }
 

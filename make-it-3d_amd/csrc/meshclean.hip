@@ -37,20 +37,20 @@
 //   k_cl_flags      per vertex: the keep rule at label rows -> flag (workspace)
 //   k_cl_count_v/_t kept vertices / triangles per workgroup -> workspace
 //   k_cl_scan       one workgroup: exclusive scan of both rows of block sums in place; totals -> counts[0], counts[1]
+//                   (scan_row of mi3d_scan.h, which also holds block_scan)
 //   k_cl_emit_v     kept again, block scan, vertex row copied to `block base + rank`, vertex_map written
 //   k_cl_emit_t     kept again, block scan, triangle written with its indices mapped
 #include <hip/hip_runtime.h>
 
 #include "../../include/mi3d.h"
+#include "mi3d_scan.h"
 
 namespace {
 
+using namespace mi3d_scan;
+
 constexpr int kBlock = 256, kWaves = kBlock / 64;
 constexpr unsigned long long kMaxCount = 0x7FFFFFFFull;  // nv, nt <= 2^31 - 1: indices are int32
-
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
-inline uint32_t blocks_of(uint32_t n) { return (n + kBlock - 1) / kBlock; }
 
 // counts (device uint64[8]): 0 kept vertices, 1 kept triangles, 2 triangles with an index outside [0, nv), 3 threads
 // that gave up, 4 (faces << 32) | ~label of the largest component, 5 components with a face, 6 elements emit could not
@@ -64,19 +64,17 @@ struct CleanWorkspace {
     uint8_t *flag;
 };
 
-inline size_t pad8(size_t b) { return (b + 7) / 8 * 8; }
-
 inline size_t clean_workspace_bytes(uint32_t nv, uint32_t nt) {
-    return pad8((size_t)blocks_of(nv) * 4) + pad8((size_t)blocks_of(nt) * 4) + pad8(nv);
+    return pad8((size_t)blocks_of(nv, kBlock) * 4) + pad8((size_t)blocks_of(nt, kBlock) * 4) + pad8(nv);
 }
 
 inline CleanWorkspace clean_carve(void *ws, uint32_t nv, uint32_t nt) {
     char *p = reinterpret_cast<char *>(ws);
     CleanWorkspace w;
     w.block_v = reinterpret_cast<uint32_t *>(p);
-    p += pad8((size_t)blocks_of(nv) * 4);
+    p += pad8((size_t)blocks_of(nv, kBlock) * 4);
     w.block_t = reinterpret_cast<uint32_t *>(p);
-    p += pad8((size_t)blocks_of(nt) * 4);
+    p += pad8((size_t)blocks_of(nt, kBlock) * 4);
     w.flag = reinterpret_cast<uint8_t *>(p);
     return w;
 }
@@ -93,8 +91,6 @@ __device__ __forceinline__ float key_float(uint32_t k) {
 }
 
 constexpr uint32_t kNoMin = 0xFFFFFFFFu, kNoMax = 0u;
-
-__device__ __forceinline__ bool in_range(int32_t i, uint32_t nv) { return i >= 0 && (uint32_t)i < nv; }
 
 __device__ __forceinline__ bool valid_triangle(const int32_t *__restrict__ tri, uint32_t t, uint32_t nv, int32_t &a,
                                                int32_t &b, int32_t &c) {
@@ -381,28 +377,6 @@ __global__ __launch_bounds__(kBlock) void k_cl_flags(uint32_t nv, const int32_t 
     flag[v] = keep ? 1 : 0;
 }
 
-// exclusive scan over the workgroup (kBlock threads); returns the thread's rank, `total` the block sum
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t *wave_sum, uint32_t &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        before += w < wave ? wave_sum[w] : 0u;
-        total += wave_sum[w];
-    }
-    __syncthreads();
-    return before + incl - v;
-}
-
 __device__ __forceinline__ uint32_t kept_vertex(uint32_t v, uint32_t nv, const int32_t *__restrict__ label,
                                                 const uint8_t *__restrict__ flag) {
     return v < nv ? flag[label[v]] : 0u;
@@ -417,7 +391,7 @@ __device__ __forceinline__ uint32_t kept_triangle(const int32_t *__restrict__ tr
 __global__ __launch_bounds__(kBlock) void k_cl_count_v(uint32_t nv, const int32_t *__restrict__ label, CleanWorkspace w) {
     __shared__ uint32_t wave_sum[kWaves];
     uint32_t total;
-    block_scan(kept_vertex(blockIdx.x * kBlock + threadIdx.x, nv, label, w.flag), wave_sum, total);
+    block_scan<kWaves>(kept_vertex(blockIdx.x * kBlock + threadIdx.x, nv, label, w.flag), wave_sum, total);
     if (threadIdx.x == 0) w.block_v[blockIdx.x] = total;
 }
 
@@ -426,44 +400,16 @@ __global__ __launch_bounds__(kBlock) void k_cl_count_t(const int32_t *__restrict
     __shared__ uint32_t wave_sum[kWaves];
     int32_t a, b, c;
     uint32_t total;
-    block_scan(kept_triangle(tri, blockIdx.x * kBlock + threadIdx.x, nt, nv, label, w.flag, a, b, c), wave_sum, total);
+    block_scan<kWaves>(kept_triangle(tri, blockIdx.x * kBlock + threadIdx.x, nt, nv, label, w.flag, a, b, c), wave_sum,
+                       total);
     if (threadIdx.x == 0) w.block_t[blockIdx.x] = total;
 }
 
-// exclusive scan of one row of block sums in place (at most 8 M of them: one workgroup looping); returns the total to
-// every thread.  Sums are at most 2^31 - 1: 32 bits hold every offset.
-__device__ uint32_t scan_row(uint32_t *row, uint32_t nb, uint32_t *wave_sum, uint32_t *base) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) *base = 0;
-    __syncthreads();
-    for (uint32_t b0 = 0; b0 < nb; b0 += 1024) {
-        const uint32_t b = b0 + threadIdx.x;
-        const uint32_t cnt = b < nb ? row[b] : 0u;
-        uint32_t incl = cnt;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t up = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += up;
-        }
-        if (lane == 63) wave_sum[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, sum = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            before += q < wave ? wave_sum[q] : 0u;
-            sum += wave_sum[q];
-        }
-        if (b < nb) row[b] = *base + before + incl - cnt;
-        __syncthreads();
-        if (threadIdx.x == 0) *base += sum;
-        __syncthreads();
-    }
-    return *base;
-}
-
-__global__ __launch_bounds__(1024) void k_cl_scan(CleanWorkspace w, uint32_t nbv, uint32_t nbt,
+// both rows of block sums scanned in place (at most 8 M sums each).  Sums are at most 2^31 - 1: 32 bits hold every
+// offset.
+__global__ __launch_bounds__(kRowThreads) void k_cl_scan(CleanWorkspace w, uint32_t nbv, uint32_t nbt,
                                                   unsigned long long *__restrict__ counts) {
-    __shared__ uint32_t wave_sum[16];
+    __shared__ uint32_t wave_sum[kRowWaves];
     __shared__ uint32_t base;
     const uint32_t kv = scan_row(w.block_v, nbv, wave_sum, &base);
     __syncthreads();
@@ -480,7 +426,7 @@ __global__ __launch_bounds__(kBlock) void k_cl_emit_v(const float *__restrict__ 
     const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
     const uint32_t kept = kept_vertex(v, nv, label, w.flag);
     uint32_t total;
-    const uint32_t rank = block_scan(kept, wave_sum, total);
+    const uint32_t rank = block_scan<kWaves>(kept, wave_sum, total);
     if (v >= nv) return;
     const uint32_t id = w.block_v[blockIdx.x] + rank;
     vertex_map[v] = kept ? (int32_t)id : -1;
@@ -502,7 +448,7 @@ __global__ __launch_bounds__(kBlock) void k_cl_emit_t(const int32_t *__restrict_
     int32_t a = 0, b = 0, c = 0;
     const uint32_t kept = kept_triangle(tri, t, nt, nv, label, w.flag, a, b, c);
     uint32_t total;
-    const uint32_t rank = block_scan(kept, wave_sum, total);
+    const uint32_t rank = block_scan<kWaves>(kept, wave_sum, total);
     if (!kept) return;
     const uint32_t id = w.block_t[blockIdx.x] + rank;
     if (id >= nt_cap) { atomicAdd(&counts[kLost], 1ull); return; }
@@ -511,8 +457,6 @@ __global__ __launch_bounds__(kBlock) void k_cl_emit_t(const int32_t *__restrict_
     o[1] = vertex_map[b];
     o[2] = vertex_map[c];
 }
-
-bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 bool sizes_ok(unsigned long long nv, unsigned long long nt) { return nv <= kMaxCount && nt <= kMaxCount; }
 
@@ -533,19 +477,20 @@ int mi3d_mesh_components(const float *vertices, unsigned long long nv, const int
         (nv > 0 && (vertices == nullptr || label == nullptr || faces == nullptr || box_min == nullptr || box_max == nullptr)))
         return (int)hipErrorInvalidValue;
     const uint32_t n = (uint32_t)nv, m = (uint32_t)nt;
+    const uint32_t nbv = blocks_of(n, kBlock), nbt = blocks_of(m, kBlock);
     const hipStream_t st = as_stream(stream);
     uint32_t *kmin = reinterpret_cast<uint32_t *>(box_min), *kmax = reinterpret_cast<uint32_t *>(box_max);
     hipLaunchKernelGGL(k_cc_zero, dim3(1), dim3(64), 0, st, counts);
-    if (n) hipLaunchKernelGGL(k_cc_init, dim3(blocks_of(n)), dim3(kBlock), 0, st, n, label, faces, kmin, kmax);
-    if (m) hipLaunchKernelGGL(k_cc_hook, dim3(blocks_of(m)), dim3(kBlock), 0, st, triangles, m, n, label, counts);
-    if (n) hipLaunchKernelGGL(k_cc_flatten, dim3(blocks_of(n)), dim3(kBlock), 0, st, n, label, counts);
+    if (n) hipLaunchKernelGGL(k_cc_init, dim3(nbv), dim3(kBlock), 0, st, n, label, faces, kmin, kmax);
+    if (m) hipLaunchKernelGGL(k_cc_hook, dim3(nbt), dim3(kBlock), 0, st, triangles, m, n, label, counts);
+    if (n) hipLaunchKernelGGL(k_cc_flatten, dim3(nbv), dim3(kBlock), 0, st, n, label, counts);
     if (m && n)
-        hipLaunchKernelGGL(k_cc_faces, dim3(min(blocks_of(m), kStatBlocks)), dim3(kBlock), 0, st, triangles, m, n, label,
+        hipLaunchKernelGGL(k_cc_faces, dim3(min(nbt, kStatBlocks)), dim3(kBlock), 0, st, triangles, m, n, label,
                            faces);
     if (n) {
-        hipLaunchKernelGGL(k_cc_boxes, dim3(min(blocks_of(n), kStatBlocks)), dim3(kBlock), 0, st, vertices, n, label, kmin,
+        hipLaunchKernelGGL(k_cc_boxes, dim3(min(nbv, kStatBlocks)), dim3(kBlock), 0, st, vertices, n, label, kmin,
                            kmax);
-        hipLaunchKernelGGL(k_cc_finish, dim3(min(blocks_of(n), kStatBlocks)), dim3(kBlock), 0, st, n, label, faces, kmin,
+        hipLaunchKernelGGL(k_cc_finish, dim3(min(nbv, kStatBlocks)), dim3(kBlock), 0, st, n, label, faces, kmin,
                            kmax, counts);
     }
     return (int)hipGetLastError();
@@ -562,17 +507,18 @@ int mi3d_mesh_clean_count(const int32_t *triangles, unsigned long long nv, unsig
         (nv > 0 && (label == nullptr || faces == nullptr || box_min == nullptr || box_max == nullptr)))
         return (int)hipErrorInvalidValue;
     const uint32_t n = (uint32_t)nv, m = (uint32_t)nt;
+    const uint32_t nbv = blocks_of(n, kBlock), nbt = blocks_of(m, kBlock);
     const hipStream_t st = as_stream(stream);
     const CleanWorkspace w = clean_carve(ws, n, m);
     const KeepRule rule = {min_faces, min_diagonal * min_diagonal, largest != 0};
     if (n) {
-        hipLaunchKernelGGL(k_cl_flags, dim3(blocks_of(n)), dim3(kBlock), 0, st, n, label, faces, box_min, box_max, rule,
+        hipLaunchKernelGGL(k_cl_flags, dim3(nbv), dim3(kBlock), 0, st, n, label, faces, box_min, box_max, rule,
                            counts, w.flag);
-        hipLaunchKernelGGL(k_cl_count_v, dim3(blocks_of(n)), dim3(kBlock), 0, st, n, label, w);
+        hipLaunchKernelGGL(k_cl_count_v, dim3(nbv), dim3(kBlock), 0, st, n, label, w);
     }
-    if (m && n) hipLaunchKernelGGL(k_cl_count_t, dim3(blocks_of(m)), dim3(kBlock), 0, st, triangles, m, n, label, w);
+    if (m && n) hipLaunchKernelGGL(k_cl_count_t, dim3(nbt), dim3(kBlock), 0, st, triangles, m, n, label, w);
     // without vertices no triangle is valid: its row of block sums is not scanned (and never read)
-    hipLaunchKernelGGL(k_cl_scan, dim3(1), dim3(1024), 0, st, w, blocks_of(n), n ? blocks_of(m) : 0u, counts);
+    hipLaunchKernelGGL(k_cl_scan, dim3(1), dim3(kRowThreads), 0, st, w, nbv, n ? nbt : 0u, counts);
     return (int)hipGetLastError();
 }
 
@@ -588,13 +534,14 @@ int mi3d_mesh_clean_emit(const float *vertices, unsigned long long nv, const int
         (nt_cap > 0 && out_triangles == nullptr))
         return (int)hipErrorInvalidValue;
     const uint32_t n = (uint32_t)nv, m = (uint32_t)nt;
+    const uint32_t nbv = blocks_of(n, kBlock), nbt = blocks_of(m, kBlock);
     const uint32_t vcap = nv_cap > kMaxCount ? (uint32_t)kMaxCount : (uint32_t)nv_cap;
     const uint32_t tcap = nt_cap > kMaxCount ? (uint32_t)kMaxCount : (uint32_t)nt_cap;
     const hipStream_t st = as_stream(stream);
     const CleanWorkspace w = clean_carve(ws, n, m);
-    hipLaunchKernelGGL(k_cl_emit_v, dim3(blocks_of(n)), dim3(kBlock), 0, st, vertices, n, label, w, out_vertices, vcap,
+    hipLaunchKernelGGL(k_cl_emit_v, dim3(nbv), dim3(kBlock), 0, st, vertices, n, label, w, out_vertices, vcap,
                        vertex_map, counts);
-    if (m) hipLaunchKernelGGL(k_cl_emit_t, dim3(blocks_of(m)), dim3(kBlock), 0, st, triangles, m, n, label, w, vertex_map,
+    if (m) hipLaunchKernelGGL(k_cl_emit_t, dim3(nbt), dim3(kBlock), 0, st, triangles, m, n, label, w, vertex_map,
                               out_triangles, tcap, counts);
     return (int)hipGetLastError();
 }

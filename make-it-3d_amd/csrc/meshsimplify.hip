@@ -36,23 +36,23 @@
 //   k_sp_emit_t    survivors: block scan, corners through vertex_map
 // The common events (leaders, degenerate, duplicate) are counted per workgroup and summed by k_sp_scan: one atomic per
 // wave on a single address retires at under 100 per microsecond, which was 9 of the first version's 16 ms on the 256^3
-// noise surface.  The rare ones (counts[2], [3], [4]) are one atomic per wave that has any.
+// noise surface.  The rare ones (counts[2], [3], [4]) are one atomic per wave that has any.  The scans
+// (block_scan, scan_row) and wave_count are those of mi3d_scan.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "../../include/mi3d.h"
+#include "mi3d_scan.h"
 
 namespace {
+
+using namespace mi3d_scan;
 
 constexpr int kBlock = 256, kWaves = kBlock / 64;
 constexpr unsigned long long kMaxCount = 0x7FFFFFFFull;  // nv, nt <= 2^31 - 1: indices are int32
 constexpr unsigned long long kMaxCapacity = 1ull << 31;  // slots are int32 too
 constexpr uint32_t kInitBlocks = 2048;
-
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
-inline uint32_t blocks_of(uint32_t n) { return (n + kBlock - 1) / kBlock; }
 
 // counts (device uint64[8]): 0 emitted vertices, 1 surviving triangles, 2 triangles with an index outside [0, nv) or a
 // corner without a cluster, 3 threads that gave up, 4 non-finite vertices, 5 clusters, 6 degenerate triangles,
@@ -81,8 +81,6 @@ struct SimplifyWorkspace {
     unsigned long long zero_words;  // 8-byte words of the zeroed region behind it
 };
 
-inline size_t pad8(size_t b) { return (b + 7) / 8 * 8; }
-
 // the smallest power of two above n, shifted by `shift`, at most 2^31
 inline unsigned long long capacity_of(unsigned long long n, int shift) {
     unsigned long long p = 1;
@@ -97,7 +95,7 @@ inline size_t table_bytes(uint32_t nv, uint32_t nt, int shift) {
 
 inline size_t fixed_bytes(uint32_t nv, uint32_t nt) {
     return pad8((size_t)nv * 32) + pad8(nv) + pad8((size_t)nv * 4) + pad8((size_t)nt * 4) +
-           2 * pad8((size_t)blocks_of(nv) * 4) + 3 * pad8((size_t)blocks_of(nt) * 4);
+           2 * pad8((size_t)blocks_of(nv, kBlock) * 4) + 3 * pad8((size_t)blocks_of(nt, kBlock) * 4);
 }
 
 inline size_t simplify_workspace_bytes(uint32_t nv, uint32_t nt, int tight) {
@@ -126,23 +124,15 @@ inline SimplifyWorkspace simplify_carve(void *ws, size_t ws_bytes, uint32_t nv, 
     w.tslot = reinterpret_cast<int32_t *>(p);
     p += pad8((size_t)nt * 4);
     w.block_v = reinterpret_cast<uint32_t *>(p);
-    p += pad8((size_t)blocks_of(nv) * 4);
+    p += pad8((size_t)blocks_of(nv, kBlock) * 4);
     w.block_t = reinterpret_cast<uint32_t *>(p);
-    p += pad8((size_t)blocks_of(nt) * 4);
+    p += pad8((size_t)blocks_of(nt, kBlock) * 4);
     w.clusters_v = reinterpret_cast<uint32_t *>(p);
-    p += pad8((size_t)blocks_of(nv) * 4);
+    p += pad8((size_t)blocks_of(nv, kBlock) * 4);
     w.degenerate_t = reinterpret_cast<uint32_t *>(p);
-    p += pad8((size_t)blocks_of(nt) * 4);
+    p += pad8((size_t)blocks_of(nt, kBlock) * 4);
     w.duplicate_t = reinterpret_cast<uint32_t *>(p);
     return w;
-}
-
-__device__ __forceinline__ bool in_range(int32_t i, uint32_t nv) { return i >= 0 && (uint32_t)i < nv; }
-
-// one atomic per wave; reached by every lane of the wave (no lane has returned)
-__device__ __forceinline__ void wave_count(bool pred, unsigned long long *counter) {
-    const unsigned long long m = __ballot(pred);
-    if ((threadIdx.x & 63) == 0 && m != 0) atomicAdd(counter, (unsigned long long)__popcll(m));
 }
 
 // relaxed, agent scope: past the CU's L1
@@ -167,7 +157,7 @@ __device__ __forceinline__ bool cluster_of(const float *__restrict__ vertices, u
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float x = vertices[(size_t)v * 3 + k];
-        finite = finite && fabsf(x) <= 3.402823466e+38f;  // false for NaN and the infinities
+        finite = finite && is_finite(x);
         const float d = x - L.o[k];
         const float g = d / L.cell;
         const float fl = floorf(g);
@@ -176,29 +166,6 @@ __device__ __forceinline__ bool cluster_of(const float *__restrict__ vertices, u
         f[k] = fminf(fmaxf(fr, 0.f), 1.f);  // moves nothing unless c was clamped
     }
     return finite;
-}
-
-// exclusive scan over the workgroup (kBlock threads); returns the thread's rank, `total` the block sum.  A copy of the
-// helper in meshclean.hip.
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t *wave_sum, uint32_t &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        before += w < wave ? wave_sum[w] : 0u;
-        total += wave_sum[w];
-    }
-    __syncthreads();
-    return before + incl - v;
 }
 
 // ------------------------------------------------------------------------------------------------ the count phase
@@ -318,7 +285,8 @@ __global__ __launch_bounds__(kBlock) void k_sp_insert_t(const int32_t *__restric
     wave_count(gave_up, &counts[kGaveUp]);
     __shared__ uint32_t wave_sum[kWaves];
     uint32_t total;
-    block_scan(degenerate ? 1u : 0u, wave_sum, total);  // most triangles are: a row of block sums, not one hot address
+    // most triangles are degenerate: a row of block sums, not one hot address
+    block_scan<kWaves>(degenerate ? 1u : 0u, wave_sum, total);
     if (threadIdx.x == 0) w.degenerate_t[blockIdx.x] = total;
 }
 
@@ -333,7 +301,7 @@ __global__ __launch_bounds__(kBlock) void k_sp_flag_t(const int32_t *__restrict_
         for (int k = 0; k < 3; ++k) w.ref[w.lead[tri[(size_t)t * 3 + k]]] = 1;
     }
     uint32_t total;  // two counts of at most 256 in one scan: survivors low, duplicates high
-    block_scan((survives ? 1u : 0u) | (s >= 0 && !survives ? 1u << 16 : 0u), wave_sum, total);
+    block_scan<kWaves>((survives ? 1u : 0u) | (s >= 0 && !survives ? 1u << 16 : 0u), wave_sum, total);
     if (threadIdx.x == 0) {
         w.block_t[blockIdx.x] = total & 0xFFFFu;
         w.duplicate_t[blockIdx.x] = total >> 16;
@@ -349,7 +317,7 @@ __global__ __launch_bounds__(kBlock) void k_sp_count_v(uint32_t nv, SimplifyWork
     const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
     const bool leader = is_leader(w, v, nv);
     uint32_t total;  // emitted leaders low, all leaders high
-    block_scan((leader && w.ref[v] ? 1u : 0u) | (leader ? 1u << 16 : 0u), wave_sum, total);
+    block_scan<kWaves>((leader && w.ref[v] ? 1u : 0u) | (leader ? 1u << 16 : 0u), wave_sum, total);
     if (threadIdx.x == 0) {
         w.block_v[blockIdx.x] = total & 0xFFFFu;
         w.clusters_v[blockIdx.x] = total >> 16;
@@ -359,7 +327,7 @@ __global__ __launch_bounds__(kBlock) void k_sp_count_v(uint32_t nv, SimplifyWork
 // the sum of a row of per-workgroup counts, to every thread (one workgroup of 1024)
 __device__ unsigned long long sum_row(const uint32_t *row, uint32_t nb, unsigned long long *wave_total) {
     unsigned long long s = 0;
-    for (uint32_t b = threadIdx.x; b < nb; b += 1024) s += row[b];
+    for (uint32_t b = threadIdx.x; b < nb; b += kRowThreads) s += row[b];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
     __syncthreads();
@@ -367,49 +335,18 @@ __device__ unsigned long long sum_row(const uint32_t *row, uint32_t nb, unsigned
     __syncthreads();
     unsigned long long sum = 0;
 #pragma unroll
-    for (int q = 0; q < 16; ++q) sum += wave_total[q];
+    for (int q = 0; q < kRowWaves; ++q) sum += wave_total[q];
     return sum;
 }
 
-// exclusive scan of one row of block sums in place (one workgroup of 1024 looping); returns the total to every thread.
-// A copy of the helper in meshclean.hip.
-__device__ uint32_t scan_row(uint32_t *row, uint32_t nb, uint32_t *wave_sum, uint32_t *base) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) *base = 0;
-    __syncthreads();
-    for (uint32_t b0 = 0; b0 < nb; b0 += 1024) {
-        const uint32_t b = b0 + threadIdx.x;
-        const uint32_t cnt = b < nb ? row[b] : 0u;
-        uint32_t incl = cnt;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t up = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += up;
-        }
-        if (lane == 63) wave_sum[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, sum = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            before += q < wave ? wave_sum[q] : 0u;
-            sum += wave_sum[q];
-        }
-        if (b < nb) row[b] = *base + before + incl - cnt;
-        __syncthreads();
-        if (threadIdx.x == 0) *base += sum;
-        __syncthreads();
-    }
-    return *base;
-}
-
-__global__ __launch_bounds__(1024) void k_sp_scan(SimplifyWorkspace w, uint32_t nbv, uint32_t nbt,
+__global__ __launch_bounds__(kRowThreads) void k_sp_scan(SimplifyWorkspace w, uint32_t nbv, uint32_t nbt,
                                                   unsigned long long *__restrict__ counts) {
-    __shared__ uint32_t wave_sum[16];
+    __shared__ uint32_t wave_sum[kRowWaves];
     __shared__ uint32_t base;
     const uint32_t kv = scan_row(w.block_v, nbv, wave_sum, &base);
     __syncthreads();
     const uint32_t kt = scan_row(w.block_t, nbt, wave_sum, &base);
-    __shared__ unsigned long long wave_total[16];
+    __shared__ unsigned long long wave_total[kRowWaves];
     const unsigned long long clusters = sum_row(w.clusters_v, nbv, wave_total);
     const unsigned long long degenerate = sum_row(w.degenerate_t, nbt, wave_total);
     const unsigned long long duplicate = sum_row(w.duplicate_t, nbt, wave_total);
@@ -437,7 +374,7 @@ __global__ __launch_bounds__(kBlock) void k_sp_emit_v(const float *__restrict__ 
     const bool leader = is_leader(w, v, nv);
     const uint32_t emitted = leader && w.ref[v] ? 1u : 0u;
     uint32_t total;
-    const uint32_t rank = block_scan(emitted, wave_sum, total);
+    const uint32_t rank = block_scan<kWaves>(emitted, wave_sum, total);
     if (!leader) return;  // the others: k_sp_map
     const uint32_t id = w.block_v[blockIdx.x] + rank;
     vertex_map[v] = emitted ? (int32_t)id : -1;
@@ -474,15 +411,13 @@ __global__ __launch_bounds__(kBlock) void k_sp_emit_t(const int32_t *__restrict_
     const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
     const uint32_t survives = t < nt && w.tslot[t] >= 0 ? 1u : 0u;
     uint32_t total;
-    const uint32_t rank = block_scan(survives, wave_sum, total);
+    const uint32_t rank = block_scan<kWaves>(survives, wave_sum, total);
     if (!survives) return;
     const uint32_t id = w.block_t[blockIdx.x] + rank;
     if (id >= nt_cap) { atomicAdd(lost, 1ull); return; }
 #pragma unroll
     for (int k = 0; k < 3; ++k) out[(size_t)id * 3 + k] = vertex_map[tri[(size_t)t * 3 + k]];  // a survivor's indices are valid
 }
-
-bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 bool sizes_ok(unsigned long long nv, unsigned long long nt) { return nv <= kMaxCount && nt <= kMaxCount; }
 
@@ -510,6 +445,7 @@ int mi3d_mesh_simplify_count(const float *vertices, unsigned long long nv, const
         (nv > 0 && vertices == nullptr))
         return (int)hipErrorInvalidValue;
     const uint32_t n = (uint32_t)nv, m = (uint32_t)nt;
+    const uint32_t nbv = blocks_of(n, kBlock), nbt = blocks_of(m, kBlock);
     const hipStream_t st = as_stream(stream);
     const SimplifyWorkspace w = simplify_carve(ws, ws_bytes, n, m);
     const Lattice L = {{origin_host[0], origin_host[1], origin_host[2]}, cell};
@@ -519,15 +455,15 @@ int mi3d_mesh_simplify_count(const float *vertices, unsigned long long nv, const
     hipLaunchKernelGGL(k_sp_init, dim3(init_blocks), dim3(kBlock), 0, st, reinterpret_cast<unsigned long long *>(ws),
                        w.fill_words, w.zero_words, counts);
     if (n) {
-        hipLaunchKernelGGL(k_sp_insert_v, dim3(blocks_of(n)), dim3(kBlock), 0, st, vertices, n, L, w, counts);
-        hipLaunchKernelGGL(k_sp_accum, dim3(blocks_of(n)), dim3(kBlock), 0, st, vertices, n, L, w);
+        hipLaunchKernelGGL(k_sp_insert_v, dim3(nbv), dim3(kBlock), 0, st, vertices, n, L, w, counts);
+        hipLaunchKernelGGL(k_sp_accum, dim3(nbv), dim3(kBlock), 0, st, vertices, n, L, w);
     }
     if (m) {
-        hipLaunchKernelGGL(k_sp_insert_t, dim3(blocks_of(m)), dim3(kBlock), 0, st, triangles, m, n, w, counts);
-        hipLaunchKernelGGL(k_sp_flag_t, dim3(blocks_of(m)), dim3(kBlock), 0, st, triangles, m, w);
+        hipLaunchKernelGGL(k_sp_insert_t, dim3(nbt), dim3(kBlock), 0, st, triangles, m, n, w, counts);
+        hipLaunchKernelGGL(k_sp_flag_t, dim3(nbt), dim3(kBlock), 0, st, triangles, m, w);
     }
-    if (n) hipLaunchKernelGGL(k_sp_count_v, dim3(blocks_of(n)), dim3(kBlock), 0, st, n, w);
-    hipLaunchKernelGGL(k_sp_scan, dim3(1), dim3(1024), 0, st, w, blocks_of(n), blocks_of(m), counts);
+    if (n) hipLaunchKernelGGL(k_sp_count_v, dim3(nbv), dim3(kBlock), 0, st, n, w);
+    hipLaunchKernelGGL(k_sp_scan, dim3(1), dim3(kRowThreads), 0, st, w, nbv, nbt, counts);
     return (int)hipGetLastError();
 }
 
@@ -543,16 +479,17 @@ int mi3d_mesh_simplify_emit(const float *vertices, unsigned long long nv, const 
         (nt_cap > 0 && out_triangles == nullptr))
         return (int)hipErrorInvalidValue;
     const uint32_t n = (uint32_t)nv, m = (uint32_t)nt;
+    const uint32_t nbv = blocks_of(n, kBlock), nbt = blocks_of(m, kBlock);
     const uint32_t vcap = nv_cap > kMaxCount ? (uint32_t)kMaxCount : (uint32_t)nv_cap;
     const uint32_t tcap = nt_cap > kMaxCount ? (uint32_t)kMaxCount : (uint32_t)nt_cap;
     const hipStream_t st = as_stream(stream);
     const SimplifyWorkspace w = simplify_carve(ws, ws_bytes, n, m);
     const Lattice L = {{origin_host[0], origin_host[1], origin_host[2]}, cell};
     hipLaunchKernelGGL(k_sp_zero_lost, dim3(1), dim3(64), 0, st, lost);
-    hipLaunchKernelGGL(k_sp_emit_v, dim3(blocks_of(n)), dim3(kBlock), 0, st, vertices, n, L, w, out_vertices, vcap,
+    hipLaunchKernelGGL(k_sp_emit_v, dim3(nbv), dim3(kBlock), 0, st, vertices, n, L, w, out_vertices, vcap,
                        vertex_map, lost);
-    hipLaunchKernelGGL(k_sp_map, dim3(blocks_of(n)), dim3(kBlock), 0, st, n, w, vertex_map);
-    if (m) hipLaunchKernelGGL(k_sp_emit_t, dim3(blocks_of(m)), dim3(kBlock), 0, st, triangles, m, w, vertex_map,
+    hipLaunchKernelGGL(k_sp_map, dim3(nbv), dim3(kBlock), 0, st, n, w, vertex_map);
+    if (m) hipLaunchKernelGGL(k_sp_emit_t, dim3(nbt), dim3(kBlock), 0, st, triangles, m, w, vertex_map,
                               out_triangles, tcap, lost);
     return (int)hipGetLastError();
 }

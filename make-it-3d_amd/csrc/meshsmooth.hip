@@ -13,7 +13,8 @@
 //   k_sm_init       cursors = 0 (grid stride); counts = 0
 //   k_sm_degree     per triangle: usable (else counts[0]) -> one int32 atomic per corner: the degrees
 //   k_sm_block_sums per vertex: the degrees of a workgroup summed -> block[b]
-//   k_sm_scan       one workgroup: exclusive scan of the block sums in place (rounds of 1024); the total -> offs[nv]
+//   k_sm_scan       one workgroup: exclusive scan of the block sums in place (scan_row of mi3d_scan.h); the total ->
+//                   offs[nv]
 //   k_sm_offsets    per vertex: block scan of the degrees + block[b] -> offs[v]; the cursor back to 0
 //   k_sm_fill       per usable triangle and corner: slot = cursor++ (atomic); inside the row: the pair of the other two
 //                   corners -> pairs[offs + slot]; outside: counts[6], nothing stored
@@ -28,8 +29,11 @@
 #include <cmath>
 
 #include "../../include/mi3d.h"
+#include "mi3d_scan.h"
 
 namespace {
+
+using namespace mi3d_scan;
 
 constexpr int kBlock = 256, kWaves = kBlock / 64;
 constexpr unsigned long long kMaxVertices = 0x7FFFFFFFull;  // indices are int32
@@ -42,12 +46,6 @@ constexpr double kSaturate = 1099511627776.0;  // 2^40
 // counts (device uint64[8]): see Part 16
 enum { kUnusable = 0, kNonFinite = 1, kIsolated = 2, kBorder = 3, kOverDegree = 4, kClamped = 5, kErrors = 6 };
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
-inline uint32_t blocks_of(uint32_t n) { return (n + kBlock - 1) / kBlock; }
-
-inline size_t pad8(size_t b) { return (b + 7) / 8 * 8; }
-
 // workspace: [cursor / degree: i32 x nv][offs: u32 x (nv + 1)][block sums / offsets: u32 x nbv][moves: u8 x nv]
 //            [second vertex buffer: f32 x 3 nv][pairs: i32 x 2 x 3 nt]; every array padded to 8 bytes
 struct SmoothWorkspace {
@@ -59,7 +57,7 @@ struct SmoothWorkspace {
 };
 
 inline size_t smooth_workspace_bytes(uint32_t nv, uint32_t nt) {
-    return pad8((size_t)nv * 4) + pad8(((size_t)nv + 1) * 4) + pad8((size_t)blocks_of(nv) * 4) + pad8(nv) +
+    return pad8((size_t)nv * 4) + pad8(((size_t)nv + 1) * 4) + pad8((size_t)blocks_of(nv, kBlock) * 4) + pad8(nv) +
            pad8((size_t)nv * 12) + (size_t)nt * 24;
 }
 
@@ -71,28 +69,13 @@ inline SmoothWorkspace smooth_carve(void *ws, uint32_t nv) {
     w.offs = reinterpret_cast<uint32_t *>(p);
     p += pad8(((size_t)nv + 1) * 4);
     w.block = reinterpret_cast<uint32_t *>(p);
-    p += pad8((size_t)blocks_of(nv) * 4);
+    p += pad8((size_t)blocks_of(nv, kBlock) * 4);
     w.moves = reinterpret_cast<uint8_t *>(p);
     p += pad8(nv);
     w.tmp = reinterpret_cast<float *>(p);
     p += pad8((size_t)nv * 12);
     w.pairs = reinterpret_cast<int2 *>(p);
     return w;
-}
-
-__device__ __forceinline__ bool in_range(int32_t i, uint32_t nv) { return i >= 0 && (uint32_t)i < nv; }
-
-__device__ __forceinline__ bool finite3(const float *__restrict__ vertices, uint32_t v) {
-    bool finite = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) finite = finite && fabsf(vertices[(size_t)v * 3 + k]) <= 3.402823466e+38f;  // false for NaN
-    return finite;
-}
-
-// one atomic per wave; reached by every lane of the wave (no lane has returned)
-__device__ __forceinline__ void wave_count(bool pred, unsigned long long *counter) {
-    const unsigned long long m = __ballot(pred);
-    if ((threadIdx.x & 63) == 0 && m != 0) atomicAdd(counter, (unsigned long long)__popcll(m));
 }
 
 // The corners of triangle t if it is usable (Part 16): indices in range, pairwise distinct, three finite vertices of the
@@ -103,30 +86,9 @@ __device__ __forceinline__ bool usable(const float *__restrict__ vertices, uint3
     for (int k = 0; k < 3; ++k) c[k] = tri[(size_t)t * 3 + k];
     if (!(in_range(c[0], nv) && in_range(c[1], nv) && in_range(c[2], nv))) return false;
     if (c[0] == c[1] || c[1] == c[2] || c[0] == c[2]) return false;
-    return finite3(vertices, (uint32_t)c[0]) && finite3(vertices, (uint32_t)c[1]) && finite3(vertices, (uint32_t)c[2]);
-}
-
-// exclusive scan over the workgroup (kBlock threads); returns the thread's rank, `total` the block sum.  A copy of the
-// helper in meshclean.hip.
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t *wave_sum, uint32_t &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        before += w < wave ? wave_sum[w] : 0u;
-        total += wave_sum[w];
-    }
-    __syncthreads();
-    return before + incl - v;
+    for (int k = 0; k < 3; ++k)
+        if (!finite3(vertices + (size_t)c[k] * 3)) return false;
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------ the incidence, once
@@ -155,48 +117,23 @@ __global__ __launch_bounds__(kBlock) void k_sm_block_sums(uint32_t nv, SmoothWor
     __shared__ uint32_t wave_sum[kWaves];
     const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
     uint32_t total;
-    block_scan(v < nv ? (uint32_t)w.cur[v] : 0u, wave_sum, total);
+    block_scan<kWaves>(v < nv ? (uint32_t)w.cur[v] : 0u, wave_sum, total);
     if (threadIdx.x == 0) w.block[blockIdx.x] = total;
 }
 
-// exclusive scan of the row of block sums in place (one workgroup of 1024 looping); the total -> offs[nv].  The loop of
-// scan_row in meshclean.hip.
-__global__ __launch_bounds__(1024) void k_sm_scan(SmoothWorkspace w, uint32_t nv, uint32_t nb) {
-    __shared__ uint32_t wave_sum[16];
+// exclusive scan of the row of block sums in place; the total -> offs[nv]
+__global__ __launch_bounds__(kRowThreads) void k_sm_scan(SmoothWorkspace w, uint32_t nv, uint32_t nb) {
+    __shared__ uint32_t wave_sum[kRowWaves];
     __shared__ uint32_t base;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) base = 0;
-    __syncthreads();
-    for (uint32_t b0 = 0; b0 < nb; b0 += 1024) {
-        const uint32_t b = b0 + threadIdx.x;
-        const uint32_t cnt = b < nb ? w.block[b] : 0u;
-        uint32_t incl = cnt;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t up = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += up;
-        }
-        if (lane == 63) wave_sum[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, sum = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            before += q < wave ? wave_sum[q] : 0u;
-            sum += wave_sum[q];
-        }
-        if (b < nb) w.block[b] = base + before + incl - cnt;
-        __syncthreads();
-        if (threadIdx.x == 0) base += sum;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) w.offs[nv] = base;
+    const uint32_t total = scan_row(w.block, nb, wave_sum, &base);
+    if (threadIdx.x == 0) w.offs[nv] = total;
 }
 
 __global__ __launch_bounds__(kBlock) void k_sm_offsets(uint32_t nv, SmoothWorkspace w) {
     __shared__ uint32_t wave_sum[kWaves];
     const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
     uint32_t total;
-    const uint32_t rank = block_scan(v < nv ? (uint32_t)w.cur[v] : 0u, wave_sum, total);
+    const uint32_t rank = block_scan<kWaves>(v < nv ? (uint32_t)w.cur[v] : 0u, wave_sum, total);
     if (v >= nv) return;
     w.offs[v] = w.block[blockIdx.x] + rank;
     w.cur[v] = 0;  // from here on the cursor of the row
@@ -228,7 +165,7 @@ __global__ __launch_bounds__(kBlock) void k_sm_flags(const float *__restrict__ v
     const bool live = v < nv;
     bool finite = false, isolated = false, over = false, border = false;
     if (live) {
-        finite = finite3(vertices, v);
+        finite = finite3(vertices + (size_t)v * 3);
         const uint32_t begin = w.offs[v], deg = w.offs[v + 1] - begin;
         isolated = deg == 0;
         over = deg > kMaxDegree;
@@ -310,8 +247,6 @@ __global__ __launch_bounds__(kBlock) void k_sm_copy(const float *__restrict__ sr
     if (i < n) dst[i] = src[i];
 }
 
-bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
 bool sizes_ok(unsigned long long nv, unsigned long long nt) { return nv <= kMaxVertices && nt <= kMaxTriangles; }
 
 bool factor_ok(double k) { return std::isfinite(k) && k >= -1.0 && k <= 1.0; }
@@ -337,15 +272,15 @@ int mi3d_mesh_smooth(const float *vertices, unsigned long long nv, const int32_t
         !aligned8(counts) || ws == nullptr || !aligned8(ws) ||
         ws_bytes < smooth_workspace_bytes((uint32_t)nv, (uint32_t)nt) || (nt > 0 && triangles == nullptr))
         return (int)hipErrorInvalidValue;
-    const uint32_t n = (uint32_t)nv, m = (uint32_t)nt, nb = blocks_of(n);
+    const uint32_t n = (uint32_t)nv, m = (uint32_t)nt, nb = blocks_of(n, kBlock), nbt = blocks_of(m, kBlock);
     const hipStream_t st = as_stream(stream);
     const SmoothWorkspace w = smooth_carve(ws, n);
     hipLaunchKernelGGL(k_sm_init, dim3(nb < kInitBlocks ? nb : kInitBlocks), dim3(kBlock), 0, st, w.cur, n, counts);
-    if (m) hipLaunchKernelGGL(k_sm_degree, dim3(blocks_of(m)), dim3(kBlock), 0, st, vertices, n, triangles, m, w.cur, counts);
+    if (m) hipLaunchKernelGGL(k_sm_degree, dim3(nbt), dim3(kBlock), 0, st, vertices, n, triangles, m, w.cur, counts);
     hipLaunchKernelGGL(k_sm_block_sums, dim3(nb), dim3(kBlock), 0, st, n, w);
-    hipLaunchKernelGGL(k_sm_scan, dim3(1), dim3(1024), 0, st, w, n, nb);
+    hipLaunchKernelGGL(k_sm_scan, dim3(1), dim3(kRowThreads), 0, st, w, n, nb);
     hipLaunchKernelGGL(k_sm_offsets, dim3(nb), dim3(kBlock), 0, st, n, w);
-    if (m) hipLaunchKernelGGL(k_sm_fill, dim3(blocks_of(m)), dim3(kBlock), 0, st, vertices, n, triangles, m, w, counts);
+    if (m) hipLaunchKernelGGL(k_sm_fill, dim3(nbt), dim3(kBlock), 0, st, vertices, n, triangles, m, w, counts);
     hipLaunchKernelGGL(k_sm_flags, dim3(nb), dim3(kBlock), 0, st, vertices, n, w, pin_border ? 1 : 0, counts);
 
     const double factor[2] = {lambda, mu};

@@ -10,7 +10,7 @@
 // Kernels (thread = pixel or point; no host synchronisation, no allocation, no atomic appends):
 //   k_pc_count / k_pc_scan / k_pc_unproject   kept pixels per workgroup (wave ballot + popcount), exclusive scan of the
 //                  workgroup sums by one workgroup, then pixel -> world point written at `base + rank`: row-major pixel
-//                  order, the scheme of k_mc_count / k_mc_scan / k_mc_vertices in mesh.hip
+//                  order, the scheme of k_mc_count / k_mc_scan / k_mc_vertices in mesh.hip (scan_row of mi3d_scan.h)
 //   k_pc_fill / k_pc_zmin / k_pc_visible      [H, W] buffer of order-preserving 64-bit keys of the depth, one atomicMin
 //                  per in-bounds point; then z - zmin[pixel] <= 1 / H per point
 //   k_box_morph    rows then columns of a kh x kw box minimum / maximum through an LDS tile with its halo, one launch
@@ -18,8 +18,12 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mi3d.h"
+#include "mi3d_scan.h"
 
 namespace {
+
+using mi3d_scan::kRowThreads;
+using mi3d_scan::kRowWaves;
 
 constexpr int kBlock = 256, kWaves = kBlock / 64;
 constexpr uint32_t kMaxSide = 16384;           // H, W: H * W <= 2^28 pixels, every pixel index fits 32 bits
@@ -117,37 +121,13 @@ __global__ __launch_bounds__(kBlock) void k_pc_count(const uint8_t *__restrict__
     }
 }
 
-// exclusive scan of the workgroup sums in place (at most 2^20 of them: one workgroup looping), the total -> *count
-__global__ __launch_bounds__(1024) void k_pc_scan(uint32_t *__restrict__ block_sum, uint32_t nb,
-                                                  unsigned long long *__restrict__ count) {
-    __shared__ uint32_t wave_sum[16];
+// exclusive scan of the workgroup sums in place (at most 2^20 of them), the total -> *count
+__global__ __launch_bounds__(kRowThreads) void k_pc_scan(uint32_t *__restrict__ block_sum, uint32_t nb,
+                                                         unsigned long long *__restrict__ count) {
+    __shared__ uint32_t wave_sum[kRowWaves];
     __shared__ uint32_t base;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) base = 0;
-    __syncthreads();
-    for (uint32_t b0 = 0; b0 < nb; b0 += 1024) {
-        const uint32_t b = b0 + threadIdx.x;
-        const uint32_t v = b < nb ? block_sum[b] : 0u;
-        uint32_t incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t up = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += up;
-        }
-        if (lane == 63) wave_sum[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            before += q < wave ? wave_sum[q] : 0u;
-            total += wave_sum[q];
-        }
-        if (b < nb) block_sum[b] = base + before + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 0) base += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *count = base;
+    const uint32_t total = mi3d_scan::scan_row(block_sum, nb, wave_sum, &base);
+    if (threadIdx.x == 0) *count = total;
 }
 
 // refine_utils.py:131-139: v = Kinv . (x, y, 1), v *= D[y, x], p = v . R^T + t; consecutive lanes take consecutive x
@@ -326,7 +306,7 @@ int mi3d_pc_unproject(const double *depth, const uint8_t *mask, uint32_t H, uint
     uint32_t *sums = reinterpret_cast<uint32_t *>(ws);
     const hipStream_t st = as_stream(stream);
     hipLaunchKernelGGL(k_pc_count, dim3(nb), dim3(kBlock), 0, st, mask, n, sums);
-    hipLaunchKernelGGL(k_pc_scan, dim3(1), dim3(1024), 0, st, sums, nb, count);
+    hipLaunchKernelGGL(k_pc_scan, dim3(1), dim3(kRowThreads), 0, st, sums, nb, count);
     hipLaunchKernelGGL(k_pc_unproject, dim3(nb), dim3(kBlock), 0, st, depth, mask, n, W, u, sums, points, cap);
     return (int)hipGetLastError();
 }

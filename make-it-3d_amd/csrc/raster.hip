@@ -8,7 +8,8 @@
 //
 // Pipeline (no host synchronisation, no allocation: the caller provides the tile lists' storage):
 //   k_raster_count / k_raster_scan / k_raster_fill   points -> per-tile index lists (16 x 16 pixel tiles; a point goes
-//       to every tile its radius-disc's bounding box overlaps).  Plain global atomics: a few per point.
+//       to every tile its radius-disc's bounding box overlaps).  Plain global atomics: a few per point.  The scan is
+//       scan_row of mi3d_scan.h with a put that clamps to the caller's capacity.
 //   k_raster_tiles   one 256-thread workgroup per tile, thread = pixel; the tile's points stream through LDS 256 at a
 //       time and every pixel keeps its K nearest covering points sorted by (z, point index) in registers - the index
 //       tie-break makes the result independent of the (atomic) order of the tile lists.
@@ -21,8 +22,12 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mi3d.h"
+#include "mi3d_scan.h"
 
 namespace {
+
+using mi3d_scan::kRowThreads;
+using mi3d_scan::kRowWaves;
 
 constexpr int kTilePx = 16, kTileThreads = kTilePx * kTilePx, kMaxK = 8, kMaxC = 32;
 
@@ -75,40 +80,17 @@ __global__ void k_raster_count(const float *__restrict__ ndc, uint32_t P, Raster
         for (int tx = x0 / kTilePx; tx <= x1 / kTilePx; ++tx) atomicAdd(&counts[ty * g.tiles_x + tx], 1u);
 }
 
-// exclusive scan of the tile counts (a few thousand tiles: one workgroup), cursors reset for the fill pass
-__global__ __launch_bounds__(1024) void k_raster_scan(const uint32_t *__restrict__ counts, uint32_t n_tiles,
-                                                      uint32_t capacity, uint32_t *__restrict__ offsets,
-                                                      uint32_t *__restrict__ cursors) {
-    __shared__ uint32_t wave_sum[16];
-    __shared__ uint32_t base_s;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) base_s = 0;
-    __syncthreads();
-    for (uint32_t i0 = 0; i0 < n_tiles; i0 += 1024) {
-        const uint32_t i = i0 + threadIdx.x;
-        const uint32_t c = i < n_tiles ? counts[i] : 0u;
-        uint32_t incl = c;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t up = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += up;
-        }
-        if (lane == 63) wave_sum[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) { before += w < wave ? wave_sum[w] : 0u; total += wave_sum[w]; }
-        const uint32_t base = base_s;
-        if (i < n_tiles) {
-            uint32_t o = base + before + incl - c;
-            offsets[i] = o < capacity ? o : capacity;  // a list that would overrun the caller's storage is cut
-            cursors[i] = 0;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) base_s = base + total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) offsets[n_tiles] = base_s < capacity ? base_s : capacity;
+// exclusive scan of the tile counts (a few thousand tiles) into `offsets`, cursors reset for the fill pass
+__global__ __launch_bounds__(kRowThreads) void k_raster_scan(const uint32_t *__restrict__ counts, uint32_t n_tiles,
+                                                             uint32_t capacity, uint32_t *__restrict__ offsets,
+                                                             uint32_t *__restrict__ cursors) {
+    __shared__ uint32_t wave_sum[kRowWaves];
+    __shared__ uint32_t base;
+    const uint32_t total = mi3d_scan::scan_row(counts, n_tiles, wave_sum, &base, [=](uint32_t i, uint32_t o) {
+        offsets[i] = o < capacity ? o : capacity;  // a list that would overrun the caller's storage is cut
+        cursors[i] = 0;
+    });
+    if (threadIdx.x == 0) offsets[n_tiles] = total < capacity ? total : capacity;
 }
 
 __global__ void k_raster_fill(const float *__restrict__ ndc, uint32_t P, RasterGeom g, const uint32_t *__restrict__ offsets,
@@ -338,7 +320,7 @@ int mi3d_points_rasterize(const float *points_ndc, uint32_t P, uint32_t H, uint3
     hipStream_t st = as_stream(stream);
     (void)hipMemsetAsync(counts, 0, n_tiles * sizeof(uint32_t), st);
     if (P > 0) hipLaunchKernelGGL(k_raster_count, dim3((P + 255) / 256), dim3(256), 0, st, points_ndc, P, g, counts);
-    hipLaunchKernelGGL(k_raster_scan, dim3(1), dim3(1024), 0, st, counts, n_tiles, capacity, offsets, cursors);
+    hipLaunchKernelGGL(k_raster_scan, dim3(1), dim3(kRowThreads), 0, st, counts, n_tiles, capacity, offsets, cursors);
     if (P > 0)
         hipLaunchKernelGGL(k_raster_fill, dim3((P + 255) / 256), dim3(256), 0, st, points_ndc, P, g, offsets, cursors,
                            capacity, list);

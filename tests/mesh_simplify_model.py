@@ -163,7 +163,7 @@ def lattices(R, vertices):
 
 SHEET = 600                                                           # vertices per side
 SHEET_CELLS = (2.5, 7.0)                                              # in lattice steps
-SCAN_ROUND = 1024 * 256                                               # elements one round of scan_row covers
+SCAN_ROUND = 1024 * 256                                               # elements per round of scan_row (csrc/mi3d_scan.h)
 
 
 def sheet(n=SHEET):

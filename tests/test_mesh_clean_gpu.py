@@ -314,7 +314,7 @@ def test_on_a_side_stream(cuda, inputs):
 CLEAN_BLOCK = 256                       # kBlock of csrc/meshclean.hip: elements per workgroup
 STAT_BLOCKS = 512                       # kStatBlocks: k_cc_faces / k_cc_boxes / k_cc_finish stride from at most this many
 STAT_SLOTS = 512                        # kSlots: labels a workgroup's LDS table holds (kProbes = 4 probes each)
-SCAN_ROUND = 1024                       # block sums per round of k_cl_scan's scan_row (its `b0 += 1024`)
+SCAN_ROUND = 1024                       # block sums per round of k_cl_scan: kRowThreads of scan_row in csrc/mi3d_scan.h
 STAT_PASS, SCAN_PASS = STAT_BLOCKS * CLEAN_BLOCK, SCAN_ROUND * CLEAN_BLOCK       # 131 072 and 262 144 elements
 SINGLES, LONG_STRIP = 150_000, 300_000
 

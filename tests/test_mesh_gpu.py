@@ -74,7 +74,7 @@ def vol_h(rest):
 
 
 MC_BLOCK = 256                # kBlock of csrc/mesh.hip: grid points per workgroup of k_mc_count / k_mc_vertices / k_mc_triangles
-MC_SCAN_ROUND = 1024          # block sums per round of k_mc_scan (its `b0 += 1024`, launch_bounds 1024)
+MC_SCAN_ROUND = 1024          # block sums per round of k_mc_scan: kRowThreads of scan_row in csrc/mi3d_scan.h
 FIRST_ROUND = MC_SCAN_ROUND * MC_BLOCK       # grid points whose block offsets the scan's first round makes
 
 

@@ -125,7 +125,7 @@ def test_depth2point_matches_the_reference(cuda, case_b):
 
 # ---------------------------------------------------------------------------------------------------------- compaction
 PC_BLOCK = 256                          # kBlock of csrc/pointcloud.hip: pixels per workgroup of k_pc_count / k_pc_unproject
-PC_SCAN_ROUND = 1024                    # workgroup sums per round of k_pc_scan (its `b0 += 1024`, launch_bounds 1024)
+PC_SCAN_ROUND = 1024                    # workgroup sums per round of k_pc_scan: kRowThreads of scan_row in csrc/mi3d_scan.h
 SMALL, LARGE = (70, 67), (520, 513)     # 19 workgroups; 266 760 pixels = 1043 workgroups: a second, ragged scan round
 KINDS = ["random", "zero", "one", "last"]
 COMPACT_CASES = ([pytest.param(*SMALL, k, id=k) for k in KINDS] + [pytest.param(*LARGE, k, id=f"520x513-{k}") for k in KINDS]

@@ -72,7 +72,7 @@ def test_rasterize_and_composite_match_the_oracle(cuda, H, W, K):
 
 
 TILE_PX = 16             # kTilePx of csrc/raster.hip: a tile is 16 x 16 pixels, one workgroup of k_raster_tiles
-SCAN_ROUND = 1024        # tiles per round of k_raster_scan's single workgroup (its `i0 += 1024`, launch_bounds 1024)
+SCAN_ROUND = 1024        # tiles per round of k_raster_scan's single workgroup: kRowThreads of scan_row in csrc/mi3d_scan.h
 TILE_CHUNK = 256         # kTileThreads: points of a tile's list k_raster_tiles stages in LDS per round
 
 
