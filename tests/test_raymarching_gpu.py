@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import infer_march_cases as IM
 from conftest import make_rays, random_bitfield, sphere_bitfield
 
 pytestmark = pytest.mark.gpu
@@ -13,7 +14,8 @@ RTOL = 1e-4  # north_star: "within 1e-4 relative fp32"
 
 
 def T(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)   # (shared case arrays are read-only)
 
 
 def test_loads_native_library(cuda):
@@ -369,6 +371,171 @@ def test_inference_march_composite_sdf_loop(cuda, oracle):
     assert float(ws_r.max()) > 1 - T_thresh and float(ws_r.min()) == 0
 
 
+# ---- the inference march away from C = 1, bound = 1, dt_gamma = 0: the cases of tests/infer_march_cases.py ----------------
+
+
+def _case_on_device(c, dev):
+    import types
+    return types.SimpleNamespace(o=T(c.o, dev), d=T(c.d, dev), bits=T(c.bits, dev), nears=T(c.nears, dev),
+                                 fars=T(c.fars, dev), noises=T(c.noises, dev))
+
+
+def _march_rays_abi(c, g, n_alive, n_step, alive, t, noises):
+    """mi3d_march_rays called directly, so that the test supplies `noises` (the wrapper draws them with torch.rand)."""
+    from mi3d import _lib as L
+    M = n_alive * n_step
+    M += IM.ALIGN - M % IM.ALIGN
+    xyzs, dirs = torch.zeros(M, 3, device=alive.device), torch.zeros(M, 3, device=alive.device)
+    deltas = torch.zeros(M, 2, device=alive.device)
+    assert alive.shape[0] >= n_alive and noises.shape[0] >= n_alive and t.shape[0] == c.N
+    L.call("mi3d_march_rays", n_alive, n_step, L.ptr(alive), L.ptr(t), L.ptr(g.o), L.ptr(g.d), float(c.bound),
+           float(c.dt_gamma), c.max_steps, c.C, c.H, L.ptr(g.bits), L.ptr(g.nears), L.ptr(g.fars), L.ptr(xyzs), L.ptr(dirs),
+           L.ptr(deltas), L.ptr(noises), L.stream())
+    return xyzs, dirs, deltas
+
+
+def _assert_accumulators(final, ws, dep, img, nrm):
+    np.testing.assert_allclose(ws.cpu().numpy(), final.weights_sum, rtol=RTOL, atol=1e-6)
+    np.testing.assert_allclose(img.cpu().numpy(), final.image, rtol=RTOL, atol=1e-6)
+    np.testing.assert_allclose(nrm.cpu().numpy(), final.normal, rtol=RTOL, atol=1e-6)
+    np.testing.assert_allclose(dep.cpu().numpy(), final.depth, rtol=RTOL, atol=1e-5)
+
+
+@pytest.mark.parametrize("perturb", [False, True])
+@pytest.mark.parametrize("name", IM.NAMES)
+def test_inference_march_cases_loop(cuda, oracle, name, perturb):
+    """k_march_infer + composite_rays through the reference's loop at cone steps, two and three cascades and bound > 1,
+    with the round-0 jitter supplied by the test: every round's xyzs / dirs / deltas bit-equal to the oracle's (the same
+    fused-multiply-add sites, as at C = 1), the same rays die, rays_t moves alike, the final accumulators at 1e-4."""
+    import raymarching
+    c, g = IM.case(name), _case_on_device(IM.case(name), cuda)
+    rounds, final = IM.reference_loop(name, perturb)
+    N = c.N
+    ws, dep = torch.zeros(N, device=cuda), torch.zeros(N, device=cuda)
+    img, nrm = torch.zeros(N, 3, device=cuda), torch.zeros(N, 3, device=cuda)
+    alive, t = torch.arange(N, dtype=torch.int32, device=cuda), g.nears.clone()
+    zeros = torch.zeros(N, device=cuda)
+    for k, r in enumerate(rounds):
+        assert np.array_equal(alive.cpu().numpy(), r.alive)
+        noises = g.noises if perturb and k == 0 else zeros
+        x, dd, l = _march_rays_abi(c, g, r.n_alive, r.n_step, alive, t, noises)
+        assert np.array_equal(x.cpu().numpy(), r.xyzs), (name, k)
+        assert np.array_equal(dd.cpu().numpy(), r.dirs), (name, k)
+        assert np.array_equal(l.cpu().numpy(), r.deltas), (name, k)
+        s, col, nm = c.field(r.xyzs)
+        raymarching.composite_rays(r.n_alive, r.n_step, alive, t, T(s, cuda), T(col, cuda), T(nm, cuda), l, ws, dep, img,
+                                   nrm, c.T_thresh)
+        assert np.array_equal(alive.cpu().numpy() >= 0, r.alive_after >= 0), (name, k)
+        assert np.array_equal(t.cpu().numpy(), r.t_after), (name, k)     # t only ever adds deltas[:, 1], in the same order
+        alive = alive[alive >= 0]
+    assert alive.numel() == 0
+    _assert_accumulators(final, ws, dep, img, nrm)
+
+
+@pytest.mark.parametrize("name", IM.NAMES)
+def test_march_rays_wrapper_draws_one_rand_per_alive_slot(cuda, oracle, name):
+    """raymarching.march_rays(perturb=True) draws exactly one torch.rand(n_alive) and hands noises[n] to alive SLOT n: after
+    the same seed its rows equal the oracle's on that draw - in round 0, and on the alive list of a later round (fewer
+    rays than N, slot != ray id, n_step > 1), where a jitter looked up by ray id or a draw of another shape would show."""
+    import raymarching
+    c, g = IM.case(name), _case_on_device(IM.case(name), cuda)
+    rounds, _ = IM.reference_loop(name, False)
+    later = next(r for r in rounds if r.n_step > 1 and r.n_alive > 32)
+    assert not np.array_equal(later.alive, np.arange(later.n_alive))
+    for seed, r in ((5, rounds[0]), (6, later)):
+        torch.manual_seed(seed)
+        noises = torch.rand(r.n_alive, dtype=torch.float32, device=cuda).cpu().numpy()
+        xr, dr, lr = oracle.march_rays(r.n_alive, r.n_step, r.alive, r.t, c.o, c.d, c.bound, c.bits, c.C, c.H, c.nears,
+                                       c.fars, align=IM.ALIGN, noises=noises, dt_gamma=c.dt_gamma, max_steps=c.max_steps)
+        assert not np.array_equal(xr, r.xyzs)                                    # the draw moves the rows
+        torch.manual_seed(seed)
+        x, dd, l = raymarching.march_rays(r.n_alive, r.n_step, T(r.alive, cuda), T(r.t, cuda), g.o, g.d, c.bound, g.bits,
+                                          c.C, c.H, g.nears, g.fars, IM.ALIGN, True, c.dt_gamma, c.max_steps)
+        assert np.array_equal(x.cpu().numpy(), xr) and np.array_equal(dd.cpu().numpy(), dr)
+        assert np.array_equal(l.cpu().numpy(), lr)
+        after = torch.rand(3, device=cuda)
+        torch.manual_seed(seed)
+        torch.rand(r.n_alive, dtype=torch.float32, device=cuda)
+        assert torch.equal(after, torch.rand(3, device=cuda))                    # and nothing else was drawn
+
+
+@pytest.mark.parametrize("perturb", [False, True])
+@pytest.mark.parametrize("name", IM.NAMES)
+def test_inference_ctl_loop_cases(cuda, oracle, name, perturb):
+    """infer_begin / march_rays_ctl / composite_rays_ctl / compact_alive_ctl (k_march_infer_ctl) through the same loop with
+    `noises` a device tensor of N values handed to EVERY round, as the renderer does: the kernel applies them while
+    ctl[4] == 0 only.  Per round: the plan in ctl, the rows [0, n_alive n_step) bit-equal to the oracle's (re-used buffers:
+    the rows a finished ray leaves are zeroed), the alignment rows up to ctl[2] zero, nothing written behind the largest round, the
+    compacted alive list and rays_t equal.  With perturb, round 1 matches the correct loop and so differs from the loop
+    that jitters every round; and one round 0 runs on the alive list in reverse order, where a jitter looked up by ray id
+    instead of alive slot lands on the wrong rays."""
+    import raymarching
+    c, g = IM.case(name), _case_on_device(IM.case(name), cuda)
+    rounds, final = IM.reference_loop(name, perturb)
+    N, FILL = c.N, 7.0
+    noises = g.noises if perturb else None
+    cap = N + 2 * IM.ALIGN                      # >= N + align rows, as march_rays_ctl asks
+    xyzs, dirs = torch.full((cap, 3), FILL, device=cuda), torch.full((cap, 3), FILL, device=cuda)
+    deltas = torch.full((cap, 2), FILL, device=cuda)
+
+    def march(ctl, alive, t):
+        raymarching.march_rays_ctl(ctl, N, alive, t, g.o, g.d, c.bound, g.bits, c.C, c.H, g.fars, xyzs, dirs, deltas,
+                                   noises, c.dt_gamma, c.max_steps)
+
+    high = [0]       # the most rows any round so far has had: the buffers are re-used, nothing is written behind that
+
+    def rows_equal(rows, xr, dr, lr, what):
+        assert rows == xr.shape[0] <= cap - 1, what
+        assert np.array_equal(xyzs[:rows].cpu().numpy(), xr), what
+        assert np.array_equal(dirs[:rows].cpu().numpy(), dr), what
+        assert np.array_equal(deltas[:rows].cpu().numpy(), lr), what
+        high[0] = max(high[0], rows)
+        assert bool((xyzs[high[0]:] == FILL).all()) and bool((dirs[high[0]:] == FILL).all()), what
+        assert bool((deltas[high[0]:] == FILL).all()), what
+
+    ws, dep = torch.zeros(N, device=cuda), torch.zeros(N, device=cuda)
+    img, nrm = torch.zeros(N, 3, device=cuda), torch.zeros(N, 3, device=cuda)
+    t = g.nears.clone()
+    ctl, alive = raymarching.infer_begin(N, cuda, IM.ALIGN)
+    spare = torch.full_like(alive, -7)
+    assert ctl.numel() == 8
+    for k, r in enumerate(rounds):
+        st = ctl.tolist()
+        assert (st[0], st[1], st[3], st[4]) == (r.n_alive, r.n_step, r.step, k), (st, k)
+        m = r.n_alive * r.n_step
+        assert st[2] == r.xyzs.shape[0] and not r.xyzs[m:].any() and not r.deltas[m:].any()   # the alignment rows: zero
+        assert np.array_equal(alive[:r.n_alive].cpu().numpy(), r.alive)
+        march(ctl, alive, t)
+        rows_equal(st[2], r.xyzs, r.dirs, r.deltas, (name, k))
+        if perturb and k == 1:
+            wrong = IM.reference_loop(name, True, jitter_every_round=True)[0][1]
+            assert wrong.n_alive == r.n_alive and not np.array_equal(xyzs[:m].cpu().numpy(), wrong.xyzs[:m])
+        s, col, nm = c.field(r.xyzs)
+        raymarching.composite_rays_ctl(ctl, N, alive, t, T(s, cuda), T(col, cuda), T(nm, cuda), deltas, ws, dep, img, nrm,
+                                       c.T_thresh)
+        assert np.array_equal(alive[:r.n_alive].cpu().numpy() >= 0, r.alive_after >= 0), (name, k)
+        assert np.array_equal(t.cpu().numpy(), r.t_after), (name, k)
+        raymarching.compact_alive_ctl(ctl, alive, spare, N, IM.ALIGN, c.max_steps)
+        alive, spare = spare, alive
+        left = r.alive_after[r.alive_after >= 0]
+        assert np.array_equal(alive[:left.shape[0]].cpu().numpy(), left), (name, k)
+    st = ctl.tolist()
+    assert (st[0], st[1], st[2], st[3], st[4]) == (0, 0, 0, final.step, len(rounds)), st
+    _assert_accumulators(final, ws, dep, img, nrm)
+
+    if perturb:   # a fresh loop's round 0 on the alive list in reverse order: noises[n] belongs to slot n
+        ctl, alive = raymarching.infer_begin(N, cuda, IM.ALIGN)
+        alive.copy_(torch.arange(N - 1, -1, -1, dtype=torch.int32, device=cuda))
+        rev = np.arange(N - 1, -1, -1, dtype=np.int32)
+        xr, dr, lr = oracle.march_rays(N, 1, rev, c.nears, c.o, c.d, c.bound, c.bits, c.C, c.H, c.nears, c.fars,
+                                       align=IM.ALIGN, noises=c.noises, dt_gamma=c.dt_gamma, max_steps=c.max_steps)
+        by_ray = oracle.march_rays(N, 1, rev, c.nears, c.o, c.d, c.bound, c.bits, c.C, c.H, c.nears, c.fars,
+                                   align=IM.ALIGN, noises=c.noises[::-1], dt_gamma=c.dt_gamma, max_steps=c.max_steps)[0]
+        assert not np.array_equal(xr, by_ray)
+        march(ctl, alive, g.nears.clone())
+        rows_equal(int(ctl[2]), xr, dr, lr, (name, "reversed"))
+
+
 # the chunk-edge ladder of tests/test_depth_grad_gpu.py on the SDF compositor: one slab per (length, scale) pair ...
 SDF_STEPS = (0, 1, 2, 63, 64, 65, 127, 128, 129, 192, 200, 256)
 SDF_SCALES = (3.0, 60.0, 400.0, 0.0)
@@ -474,8 +641,9 @@ def test_composite_sdf_train_chunk_edges(cuda, oracle, T_thresh, seed):
 COMPACT_ROUND = 1024     # rays per round of k_compact_alive_ctl's single workgroup (its `i0 += 1024`, launch_bounds 1024)
 
 
-@pytest.mark.parametrize("N", [600, 2600])
-def test_compact_budget_rounds_kernels_against_oracle(cuda, oracle, N):
+@pytest.mark.parametrize("N,case", [pytest.param(600, None, id="600"), pytest.param(2600, None, id="2600")]
+                         + [pytest.param(IM.CASES[name][0], name, id=f"{IM.CASES[name][0]}-{name}") for name in IM.NAMES])
+def test_compact_budget_rounds_kernels_against_oracle(cuda, oracle, N, case):
     """The four entry points of the budget loop (C ABI Part 1b, second half: mi3d_infer_begin2, mi3d_march_rays_compact_ctl,
     mi3d_composite_rays_compact_ctl, mi3d_compact_alive_ctl2) driven directly, round by round, against the CPU oracle's
     march_rays / composite_rays (raymarching.cu:906-1115 restated): the plan in the control block, the slab packing (one
@@ -483,21 +651,30 @@ def test_compact_budget_rounds_kernels_against_oracle(cuda, oracle, N):
     order-preserving compaction, the restart point (t_next = the march's own t, which the reference's running sum of
     deltas[:, 1] reproduces to float rounding) and the step cap (the only coverage used to be the
     end-to-end render comparison).  N = 2600 (the budget scaled with it): the compaction's workgroup goes round three
-    times, the last round ragged, and carries the count of the survivors so far from round to round."""
+    times, the last round ragged, and carries the count of the survivors so far from round to round.
+    case: the same at the cases of infer_march_cases (cone steps, two and three cascades, bound > 1) with budget = 4 N, and
+    one jittered round 0 on an alive list in another order (the renderer never runs this schedule with perturb: after a
+    jittered start the two restarts differ by design, so only that round is compared)."""
     import raymarching
     rng = np.random.default_rng(31)
-    H, max_steps, budget = 128, 96, 2500 * N // 600
-    carried = False          # a compaction of more than two rounds with rays dropped in the first and kept in the third
-    o, d = make_rays(rng, N)
-    aabb = np.array([-1, -1, -1, 1, 1, 1], np.float32)
-    nears, fars = oracle.near_far_from_aabb(o, d, aabb)
-    bits = sphere_bitfield(oracle, 1, H, 0.6)
+    if case is None:
+        H, max_steps, budget, C, bound, dt_gamma = 128, 96, 2500 * N // 600, 1, 1.0, 0.0
+        o, d = make_rays(rng, N)
+        aabb = np.array([-1, -1, -1, 1, 1, 1], np.float32)
+        nears, fars = oracle.near_far_from_aabb(o, d, aabb)
+        bits = sphere_bitfield(oracle, 1, H, 0.6)
 
-    def field(x):
-        s = (6 * np.exp(-np.sum(x * x, 1) / 0.08)).astype(np.float32)
-        c = (0.5 + 0.5 * np.sin(x * 7)).astype(np.float32)
-        nrm = (x / (np.linalg.norm(x, axis=1, keepdims=True) + 1e-6)).astype(np.float32)
-        return s, c, nrm
+        def field(x):
+            s = (6 * np.exp(-np.sum(x * x, 1) / 0.08)).astype(np.float32)
+            c = (0.5 + 0.5 * np.sin(x * 7)).astype(np.float32)
+            nrm = (x / (np.linalg.norm(x, axis=1, keepdims=True) + 1e-6)).astype(np.float32)
+            return s, c, nrm
+    else:
+        cs = IM.case(case)
+        assert cs.N == N
+        H, max_steps, budget, C, bound, dt_gamma = cs.H, cs.max_steps, 4 * N, cs.C, cs.bound, cs.dt_gamma
+        o, d, nears, fars, bits, field = cs.o, cs.d, cs.nears, cs.fars, cs.bits, cs.field
+    carried = False          # a compaction of more than two rounds with rays dropped in the first and kept in the third
 
     ws_r, dep_r = np.zeros(N, np.float32), np.zeros(N, np.float32)
     img_r, nrm_r = np.zeros((N, 3), np.float32), np.zeros((N, 3), np.float32)
@@ -521,11 +698,11 @@ def test_compact_budget_rounds_kernels_against_oracle(cuda, oracle, N):
         if n_alive == 0:
             break
         assert n_step == max(1, min(budget // n_alive, max_steps, max_steps - done)), (st, done)   # the plan, capped
-        raymarching.march_rays_compact_ctl(ctl, N, alive, t, od, dd, 1.0, bd, 1, H, fd, xyzs, dirs, deltas, slab, t_next,
-                                           None, 0, max_steps)
+        raymarching.march_rays_compact_ctl(ctl, N, alive, t, od, dd, bound, bd, C, H, fd, xyzs, dirs, deltas, slab, t_next,
+                                           None, dt_gamma, max_steps)
         rows = int(ctl[2])
-        xr, dr, lr = oracle.march_rays(n_alive, n_step, alive_r, t_r, o, d, 1.0, bits, 1, H, nears, fars, align=-1,
-                                       max_steps=max_steps)
+        xr, dr, lr = oracle.march_rays(n_alive, n_step, alive_r, t_r, o, d, bound, bits, C, H, nears, fars, align=-1,
+                                       dt_gamma=dt_gamma, max_steps=max_steps)
         cnt_r = (lr[:, 0].reshape(n_alive, n_step) != 0).sum(1)
         sl = slab[:n_alive].cpu().numpy()
         assert np.array_equal(sl[:, 1], cnt_r) and rows == int(cnt_r.sum())
@@ -552,9 +729,12 @@ def test_compact_budget_rounds_kernels_against_oracle(cuda, oracle, N):
         np.testing.assert_allclose(nrm.cpu().numpy(), nrm_r, rtol=RTOL, atol=1e-6)
         np.testing.assert_allclose(dep.cpu().numpy(), dep_r, rtol=RTOL, atol=1e-5)
         keep = alive_r >= 0
-        # the restart: the march's own t for a survivor; the reference's running sum agrees to float rounding
+        # the restart: the march's own t for a survivor; the reference's running sum agrees to float rounding - each of a
+        # ray's steps so far rounds at most twice (the march's t += dt, the sum's t += (t - last_t)) at the magnitude of t
         t_g = t.cpu().numpy()
-        np.testing.assert_allclose(t_g[alive_r[keep]], t_r[alive_r[keep]], rtol=0, atol=2e-5)
+        if keep.any():
+            bound_t = (done + n_step) * 2.0 ** -23 * float(fars[alive_r[keep]].max())
+            np.testing.assert_allclose(t_g[alive_r[keep]], t_r[alive_r[keep]], rtol=0, atol=bound_t)
         assert np.array_equal(t_g[alive_r[keep]], t_next[:n_alive].cpu().numpy()[keep])
         t_r[alive_r[keep]] = t_g[alive_r[keep]]     # (both sides start the next round from the same t)
         raymarching.compact_alive_ctl2(ctl, alive, spare, N, max_steps)
@@ -573,10 +753,35 @@ def test_compact_budget_rounds_kernels_against_oracle(cuda, oracle, N):
     # a sample buffer smaller than the round needs: the rows are COUNTED in ctl[8], not dropped silently
     ctl, alive = raymarching.infer_begin2(N, cuda, budget, 1, max_steps)
     small = 64
-    raymarching.march_rays_compact_ctl(ctl, N, alive, T(nears, cuda).clone(), od, dd, 1.0, bd, 1, H, fd, xyzs[:small],
-                                       dirs[:small], deltas[:small], slab, t_next, None, 0, max_steps)
+    raymarching.march_rays_compact_ctl(ctl, N, alive, T(nears, cuda).clone(), od, dd, bound, bd, C, H, fd, xyzs[:small],
+                                       dirs[:small], deltas[:small], slab, t_next, None, dt_gamma, max_steps)
     st = ctl.tolist()
     assert st[8] > 0 and st[8] + int(slab[:, 1].sum()) == st[2]
+
+    if case is None:
+        return
+    # round 0 with a jitter, on the alive list in reverse order: noises[n] belongs to alive SLOT n, whichever ray sits there
+    ctl, alive = raymarching.infer_begin2(N, cuda, budget, 1, max_steps)
+    alive.copy_(torch.arange(N - 1, -1, -1, dtype=torch.int32, device=cuda))
+    alive_r = np.arange(N - 1, -1, -1, dtype=np.int32)
+    n_step = int(ctl[1])
+    assert n_step == 4 and int(ctl[4]) == 0
+    raymarching.march_rays_compact_ctl(ctl, N, alive, T(nears, cuda).clone(), od, dd, bound, bd, C, H, fd, xyzs, dirs, deltas,
+                                       slab, t_next, T(cs.noises, cuda), dt_gamma, max_steps)
+    xr, dr, lr = oracle.march_rays(N, n_step, alive_r, nears, o, d, bound, bits, C, H, nears, fars, align=-1,
+                                   noises=cs.noises, dt_gamma=dt_gamma, max_steps=max_steps)
+    x0, _, l0 = oracle.march_rays(N, n_step, alive_r, nears, o, d, bound, bits, C, H, nears, fars, align=-1,
+                                  dt_gamma=dt_gamma, max_steps=max_steps)
+    assert not np.array_equal(xr, x0)                                                        # the jitter moves the rows
+    cnt_r = (lr[:, 0].reshape(N, n_step) != 0).sum(1)
+    sl, rows = slab[:N].cpu().numpy(), int(ctl[2])
+    assert np.array_equal(sl[:, 1], cnt_r) and rows == int(cnt_r.sum()) > 0 and int(ctl[8]) == 0
+    gather = np.concatenate([np.arange(i * n_step, i * n_step + c) for i, c in enumerate(cnt_r)]).astype(np.int64)
+    place = np.concatenate([np.arange(sl[i, 0], sl[i, 0] + c) for i, c in enumerate(cnt_r)]).astype(np.int64)
+    assert np.array_equal(np.sort(place), np.arange(rows))
+    assert np.array_equal(xyzs[:rows].cpu().numpy()[place], xr[gather])
+    assert np.array_equal(dirs[:rows].cpu().numpy()[place], dr[gather])
+    assert np.array_equal(deltas[:rows].cpu().numpy()[place], lr[gather])
 
 
 def test_rejects_bad_inputs(cuda):

@@ -52,13 +52,14 @@ def _close(a, b, rtol=1e-4, atol=1e-6, what=""):
     np.testing.assert_allclose(a, b, rtol=rtol, atol=atol, err_msg=what)
 
 
-def _render_train(model, ro, rd, ds, seed, max_steps, autocast=False):
+def _render_train(model, ro, rd, ds, seed, max_steps, autocast=False, dt_gamma=0):
     model.train()
     model.zero_grad()
     torch.manual_seed(seed)
     with torch.autocast("cuda", dtype=torch.float16, enabled=autocast):
         out = model.render(ro, rd, depth_scale=ds, bg_color=torch.full((3,), 0.7, device=ro.device), perturb=True,
-                           ambient_ratio=1.0, shading="albedo", force_all_rays=True, dt_gamma=0, max_steps=max_steps)
+                           ambient_ratio=1.0, shading="albedo", force_all_rays=True, dt_gamma=dt_gamma,
+                           max_steps=max_steps)
         loss = ((out["image"] ** 2).mean() + (out["weights_sum"] ** 2).mean() + 0.1 * out["loss_orient"]
                 + (out["loss_smooth"] if "loss_smooth" in out else 0))
     loss.backward()
@@ -221,6 +222,89 @@ def test_eval_render_matches_the_reference(ref, cuda):
         _close(b[k], a[k], what=k)
     # the normal map is a weighted sum of ratios of finite differences: compare in absolute terms
     _close(b["normal"], a["normal"], rtol=0, atol=2e-3, what="normal")
+
+
+def _pair_two_cascades(ref, cuda, oracle):
+    """bound = 2 (two cascades), max_steps = 256, the same analytic occupancy on both sides: a sphere of radius 1.6, so
+    that samples lie inside the unit box (cascade 0) and outside it."""
+    from conftest import sphere_bitfield
+    theirs, ours, opt = _pair(ref, cuda, lambda_smooth=0.0, bound=2.0, max_steps=256)
+    bits = torch.from_numpy(sphere_bitfield(oracle, 2, 128, 1.6)).to(cuda)
+    for m in (theirs, ours):
+        assert m.cascade == 2 and m.grid_size == 128 and m.density_bitfield.shape == bits.shape
+        m.density_bitfield.copy_(bits)
+    return theirs, ours
+
+
+def test_training_with_two_cascades_and_cone_steps(ref, cuda, oracle):
+    """run_cuda's training branch at bound = 2 and dt_gamma = 1/64 (every other training comparison here runs at
+    bound = 1, dt_gamma = 0): bound, dt_gamma and the cascade count reach march_rays_train through the renderer as the
+    reference passes them; outputs and every parameter gradient through _compare_training."""
+    from mi3d import rays as R
+    theirs, ours = _pair_two_cascades(ref, cuda, oracle)
+    ro, rd, ds = R.view_rays(32, 32, device=cuda)
+    a = _render_train(theirs, ro, rd, ds, 123, 256, dt_gamma=1 / 64)
+    b = _render_train(ours, ro, rd, ds, 123, 256, dt_gamma=1 / 64)
+    n = int(ours.step_counter[0, 0])
+    print(f"{n} samples")
+    assert n == int(theirs.step_counter[0, 0]) and n > 64 * 32
+    _compare_training(theirs, ours, a, b)
+
+
+# The eval jitter reaches one sample per ray: round 0 takes one step from near + dt * noise, and the composite's running t
+# restarts every later round from near + dt (renderer.py docstring of _infer_loop), so the rest of the ray is the
+# unperturbed one.  Under albedo shading the colour of that one sample hardly changes over a step of dt_min and the
+# image moves by 9.4e-5 - two tolerances, too little to tell a jitter from none.  Under lambertian shading the sample's
+# colour follows its normal, which varies at that scale: the image moves by 4.3e-3, eleven times the bar below
+# (measured on an MI355X; textureless 8.3e-3, normal 1.3e-2; all of them pass the comparisons with the reference).
+EVAL_JITTER_SHADING = dict(shading="lambertian", ambient_ratio=0.3)
+
+
+def _eval_two_cascades(ref, cuda, oracle, shading, ambient_ratio):
+    """The body of the test below for one shading; returns how far the jitter moved the product's image and the bar."""
+    from mi3d import rays as R
+    theirs, ours = _pair_two_cascades(ref, cuda, oracle)
+    ro, rd, ds = R.view_rays(48, 48, device=cuda)
+    light = torch.tensor([0.0, -0.6, 0.8], device=cuda)
+
+    def render(m, perturb, dt_gamma):
+        m.eval()
+        with torch.no_grad():
+            torch.manual_seed(11)
+            return m.render(ro, rd, depth_scale=ds, bg_color=torch.ones(3, device=cuda), perturb=perturb, light_d=light,
+                            ambient_ratio=ambient_ratio, shading=shading, dt_gamma=dt_gamma, max_steps=256)
+
+    def compare(a, b, what):
+        assert float(a["weights_sum"].max()) > 0.5
+        for k in ("image", "depth", "weights_sum"):
+            _close(b[k], a[k], what=f"{what}: {k}")
+        _close(b["normal"], a["normal"], rtol=0, atol=2e-3, what=f"{what}: normal")
+
+    compare(render(theirs, False, 1 / 64), render(ours, False, 1 / 64), "dt_gamma 1/64")
+    plain = render(ours, False, 0)
+    a, b = render(theirs, True, 0), render(ours, True, 0)
+    first = dict(ours.infer_stats)
+    assert first["schedule"] == "reference"
+    compare(a, b, "perturb")
+    moved = float((b["image"] - plain["image"]).abs().max())
+    bar = 10 * 1e-4 * float(plain["image"].abs().max())
+    print(f"{shading} {ambient_ratio}: the jitter moves the image by {moved:.3g} (ten times the tolerance: {bar:.3g})")
+    again = render(ours, True, 0)
+    assert ours.infer_stats["graphs_captured"] == 0 and ours.infer_stats["graph_replays"] >= 1
+    for k in ("image", "depth", "weights_sum", "normal"):
+        assert torch.equal(again[k], b[k]), k
+    return moved, bar
+
+
+def test_eval_render_with_two_cascades_cone_steps_and_jitter(ref, cuda, oracle):
+    """The inference branch at bound = 2: (1) dt_gamma = 1/64, no jitter; (2) perturb=True at dt_gamma = 0, which the
+    product runs on the reference's round structure with the jitter in round 0 only, drawn as the reference's march_rays
+    draws it (one torch.rand(N) after the seed).  Both against the reference's own loop with the comparisons of
+    test_eval_render_matches_the_reference; the jitter must be visible (more than ten times the tolerance away from the
+    unperturbed image), and a second perturbed render - through the graphs the first one captured - must repeat it bit
+    for bit after the same seed."""
+    moved, bar = _eval_two_cascades(ref, cuda, oracle, **EVAL_JITTER_SHADING)
+    assert moved > bar
 
 
 def test_main_py_import_line_trains_on_the_fused_field(ref, cuda):
