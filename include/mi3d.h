@@ -1058,7 +1058,8 @@ int mi3d_mesh_smooth(const float *vertices, unsigned long long nv, const int32_t
  * the bounds of w_k, s and d there, b_k has the relative error of w_k and s plus one rounding, r_k that of z_k plus one
  * more, lambda_k that of d plus one more; an interpolated attribute adds 3 u sum |lambda_k a_k| to
  * sum |a_k| E(lambda_k).  Out of scope: clipping at a near plane (Part 15's rule stands: a triangle with a corner at
- * z <= 0 is left out of the view), splitting a large triangle across threads, mip-mapping, gradients.
+ * z <= 0 is left out of the view), splitting a large triangle across threads, mip-mapping, gradients of positions and
+ * cameras (Part 18 has those of the two colour sources).
  *
  * Neither entry point allocates or synchronises.  V, H, W outside Part 15's ranges, a T outside Part 9's with a texture,
  * nv or nt above 2^31 - 1, a vis or counts that is NULL or not 8-byte aligned, a NULL views, background or image, both
@@ -1073,6 +1074,72 @@ int mi3d_mesh_shade(const float *vertices, unsigned long long nv, const int32_t 
                     const float *colors, const float *vt, const uint8_t *texture, uint32_t T, const float *vn,
                     const float *background, float *image, float *normal, float *depth, int32_t *tri, float *bary,
                     uint8_t *alpha, void *stream);
+
+/* ------------------------------------------------------------------ Part 18: gradients of the mesh render's colours */
+
+/* The shading pass of Part 17 with a float texture, and the adjoint of the shading pass in its colour source: what a
+ * texture or a set of vertex colours needs to be fitted to views through the renderer that will show them.  VISIBILITY
+ * AND GEOMETRY STAY FIXED: the keys of mi3d_mesh_visibility are an input, and nothing here differentiates the weights,
+ * the projection or the coverage.  This contract is this project's own - PARITY UNPINNED.  Added under ABI version 5: new
+ * symbols only.  (Declared ahead of the point-cloud part, like Parts 12 to 17.)
+ *
+ * FLOAT TEXTURE (mi3d_mesh_shade_f32): mi3d_mesh_shade with texture float[T][T][3]: the same kernel template, the same
+ * operations in the same order up to c = top hy + bot fy, and colour = c itself (no / 255).  Every other argument, output
+ * and refusal is Part 17's.
+ *
+ * THE PASS IS LINEAR IN ITS COLOUR SOURCE: image[p][ch] = sum_k w_k(p) source[a_k(p)][ch] for a drawn pixel p, with
+ *   (a) by vertex: a_k = the triangle's vertex k, w_k = lambda_k, k = 0, 1, 2;
+ *   (b) textured: the four taps (i0 + a, j0 + b), w00 = hx hy, w10 = fx hy, w01 = hx fy, w11 = fx fy, each product ONE
+ *       binary32 operation; lambda, i0, j0, fx, fy, hx = 1 - fx, hy = 1 - fy exactly the values of Part 17 (one
+ *       definition in the source, shared with the forward).  (The forward rounds top and bot before the last blend; the
+ *       adjoint is that of the weights above - what exact arithmetic makes of the forward.)
+ * So the adjoint needs no texture values, and one backward serves both texel types.
+ *
+ * BACKWARD (mi3d_mesh_shade_backward): dimage float[V][H][W][3] -> exactly one of grad_colors float[nv][3] and
+ * grad_texture float[T][T][3] (the latter with vt and T as Part 17 takes them), every element written.  N = V H W.  A
+ * fill (it zeroes the sums and the amax word) and three launches on `stream`:
+ *   1. amax = the largest bits(|g|) over the 3 N entries of dimage, one unsigned atomicMax per workgroup.  Positive
+ *      floats order like their bits, and a NaN's bits exceed infinity's: a non-finite entry wins by construction.
+ *   2. thread = pixel.  Part 17's key test: an all-ones key, a triangle index not below nt and a triangle with a vertex
+ *      index outside [0, nv) contribute nothing and are never dereferenced.  Otherwise, per weight w and channel ch:
+ *      t = w * g[ch] (one binary32 operation), x = (double)t * 2^-e (exact), saturated to [-2^(61 - L), 2^(61 - L)] and
+ *      0 for a NaN, q = llrint(x) (to nearest, ties to even); q is added to the int64 sum of element (a, ch) by a
+ *      no-return 64-bit integer atomicAdd (a zero q is not sent).  Integer sums are exact: arrival order cannot change a
+ *      bit, two runs give identical bytes, and a NumPy restatement gives the same bytes.
+ *   3. thread = element: grad = (float)((double)sum * 2^e): one rounding to binary64 (a sum can exceed 2^53), one to
+ *      binary32.
+ *   - THE EXPONENT e is the same for every thread: E = (bits(amax) >> 23) - 127, so that 2^(E + 1) > amax (denormals
+ *     included); L = the smallest integer with 2^L >= N; e = (E + 1) + L - 60.  HEADROOM: a weight is at most 1 plus a few
+ *     ulp, so |x| < 2^(60 - L) (1 + 2^-20), far inside the saturation bound, which therefore never acts on keys a
+ *     visibility pass of this mesh wrote; a pixel adds to one sum at most 3 times (a triangle that names a vertex
+ *     thrice), so |sum| <= 3 N 2^(61 - L) <= 3 x 2^61 < 2^63 whatever the keys hold.  RESOLUTION: one unit is
+ *     2^e = 2^(E + 1) 2^(L - 60), so a contribution is off by at most 2^(e - 1) <= amax 2^(L - 60): 26 bits below amax at
+ *     the largest N = 2^34, 40 and more at the sizes tests run at.
+ *   - amax == 0 (dimage is all zeros): launch 2 leaves at once by a device-side test and every element is +0.
+ *   - amax NOT FINITE (an infinity or a NaN anywhere in dimage): launch 2 leaves at once and EVERY element is a quiet
+ *     NaN (bits 0x7FC00000).  A stated rule: a poisoned upstream gradient poisons the whole result.
+ *   - An element no pixel contributes to is exactly +0.
+ *
+ *   mi3d_mesh_shade_backward_workspace  host only: bytes of device scratch for a gradient of `elements` floats (3 nv or
+ *                          3 T^2): 8 (elements + 1) - the int64 sums and the amax word; 0 above 3 (2^31 - 1).
+ * ERROR AGAINST EXACT ARITHMETIC (what tests/test_mesh_shade_grad_cpu.py counts; u = 2^-24), given the binary32 weights'
+ * own error E(w) (Part 17's E(lambda); for a tap weight 2 u on top of the fractions'): a sum of n contributions is off by
+ * at most sum (|g| E(w) + u |w g|) + n 2^(e - 1), and the result adds u |grad| (2^-53 for the binary64 step is below it).
+ *
+ * No entry point allocates or synchronises.  Refused (hipErrorInvalidValue), launching nothing: everything Part 17
+ * refuses of the arguments the two share; a NULL dimage; both gradients or neither; vt without T or T without vt; vt
+ * with grad_colors; grad_texture with a T outside Part 9's range; a workspace that is NULL, too small or not 8-byte
+ * aligned.  nt = 0 is accepted (every element +0) and so is nv = 0 with grad_colors (nothing to write). */
+int mi3d_mesh_shade_f32(const float *vertices, unsigned long long nv, const int32_t *triangles, unsigned long long nt,
+                        const float *views, uint32_t V, uint32_t H, uint32_t W, const unsigned long long *vis,
+                        const float *colors, const float *vt, const float *texture, uint32_t T, const float *vn,
+                        const float *background, float *image, float *normal, float *depth, int32_t *tri, float *bary,
+                        uint8_t *alpha, void *stream);
+size_t mi3d_mesh_shade_backward_workspace(unsigned long long elements);
+int mi3d_mesh_shade_backward(const float *vertices, unsigned long long nv, const int32_t *triangles, unsigned long long nt,
+                             const float *views, uint32_t V, uint32_t H, uint32_t W, const unsigned long long *vis,
+                             const float *dimage, const float *vt, uint32_t T, float *grad_colors, float *grad_texture,
+                             void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------ Part 11: the refine stage's point cloud */
 

@@ -35,4 +35,6 @@ enum : int {
     MI3D_T_ENCODE_LDS_LEVELS = 16, // gather: levels served from LDS (default: as many as fit)
     MI3D_T_ENCODE_STATIC_TILES = 17,  // gather: 1 = tiles dealt statically (round 2's order) instead of claimed
     // 18: retired (gather: the x-group evaluation of the fine hashed levels)
+    MI3D_T_SHADE_BACKWARD_LAUNCHES = 19,  // mesh shade backward: bit 0 = the fill and k_grad_amax, bit 1 = k_shade_backward,
+                                          //          bit 2 = k_grad_finish (per-launch timing; product: 7, all of them)
 };

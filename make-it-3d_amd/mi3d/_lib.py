@@ -128,6 +128,11 @@ _SIGNATURES = {
     "mi3d_mesh_visibility": [vp, C.c_uint64, vp, C.c_uint64, vp, u32, u32, u32, vp, vp, vp],
     "mi3d_mesh_shade": [vp, C.c_uint64, vp, C.c_uint64, vp, u32, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp,
                         vp, vp],
+    # Part 18 -----------------------------------------------------------------------------------------
+    "mi3d_mesh_shade_f32": [vp, C.c_uint64, vp, C.c_uint64, vp, u32, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp,
+                            vp, vp, vp],
+    "mi3d_mesh_shade_backward": [vp, C.c_uint64, vp, C.c_uint64, vp, u32, u32, u32, vp, vp, vp, u32, vp, vp, vp, C.c_size_t,
+                                 vp],
 }
 
 # host-only queries whose return value is not a hipError_t: (argtypes, restype), bound in lib() like the block below
@@ -142,6 +147,7 @@ _LATE_SIGNATURES = {
     "mi3d_mesh_components_workspace": ([C.c_uint64, C.c_uint64], C.c_size_t),
     "mi3d_mesh_simplify_workspace": ([C.c_uint64, C.c_uint64, C.c_int], C.c_size_t),
     "mi3d_mesh_smooth_workspace": ([C.c_uint64, C.c_uint64], C.c_size_t),
+    "mi3d_mesh_shade_backward_workspace": ([C.c_uint64], C.c_size_t),
 }
 
 

@@ -23,6 +23,8 @@
   render           images of a mesh from V pinhole cameras (csrc/meshrender.hip, include/mi3d.h Part 17): a visibility buffer
                    per view, then per pixel the perspective-correct vertex colour or atlas texture, normals, depth,
                    triangle index and barycentrics; the field's shadings composed in torch
+  fit_texture      a float texture or vertex colours fitted to views through render (include/mi3d.h Part 18): the adjoint of
+  fit_colors       the shading pass in its colour source - exact 64-bit fixed-point sums - under torch's Adam
   fidelity         PSNR over the union and the intersection of two renders' masks and the masks' IoU, per view and overall
   export           volume -> surface -> per-vertex albedo (-> texture) -> files; what `NeRFRenderer.export_mesh` calls
   write_obj        vertex-coloured OBJ (`v x y z r g b`) + the reference's `mat0` material; with UVs `v` / `vt` /
@@ -644,12 +646,18 @@ def _check_views_dict(views):
     if not isinstance(views, dict):
         raise Mi3dError(f"views must be a dict with the keys {VIEW_KEYS[:3]} and optionally {VIEW_KEYS[3:]} (got "
                         f"{type(views).__name__})")
-    unknown = sorted(set(views) - set(VIEW_KEYS))
+    unknown = sorted(set(views) - set(VIEW_KEYS) - {"fit"})
     missing = [k for k in VIEW_KEYS[:3] if k not in views]
     if unknown or missing:
-        raise Mi3dError(f"views: unknown keys {unknown}, missing keys {missing}; it takes {VIEW_KEYS}")
+        raise Mi3dError(f"views: unknown keys {unknown}, missing keys {missing}; it takes {VIEW_KEYS + ('fit',)}")
+    views = dict(views)
+    fit = views.pop("fit", None)
     check_views(**views)
-    return dict(views)
+    if fit is not None:
+        if not isinstance(fit, dict) or set(fit) - set(FIT_KEYS):
+            raise Mi3dError(f"views: fit must be a dict with keys among {FIT_KEYS} (got {fit!r})")
+        fit = dict(zip(FIT_KEYS, _check_fit(fit.get("iterations", 200), fit.get("lr", 0.01))))
+    return views, fit
 
 
 def _to_dev(a, dtype, dev):
@@ -779,26 +787,82 @@ def _render_buffers(vertices, triangles, records, H, W, colors=None, uvs=None, t
     (the uint64 keys), counts int64 [2], image float32 [V, H, W, 3], alpha uint8 [V, H, W], depth, tri int32, bary and
     normal (None without `normals`).  `records` float32 [V, 24] on the mesh's device; the arguments are checked by the
     callers."""
+    vis, counts = _visibility(vertices, triangles, records, H, W)
+    out = _shade(vertices, triangles, records, H, W, vis, colors, uvs, texture, normals, bg)
+    out.update(vis=vis, counts=counts)
+    return out
+
+
+def _visibility(vertices, triangles, records, H, W):
+    """mi3d_mesh_visibility on the current stream: (vis int64 [V, H, W], counts int64 [2]), nothing read back."""
     dev, V = vertices.device, int(records.shape[0])
-    nv, nt = int(vertices.shape[0]), int(triangles.shape[0])
     vis = torch.empty(V, H, W, dtype=torch.int64, device=dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
-    _lib.launch("mi3d_mesh_visibility", vertices, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, _lib.ptr(records), V, H,
-                W, _lib.ptr(vis), _lib.ptr(counts))
-    out = dict(vis=vis, counts=counts,
-               image=torch.empty(V, H, W, 3, dtype=torch.float32, device=dev),
-               alpha=torch.empty(V, H, W, dtype=torch.uint8, device=dev),
-               depth=torch.empty(V, H, W, dtype=torch.float32, device=dev),
-               tri=torch.empty(V, H, W, dtype=torch.int32, device=dev),
-               bary=torch.empty(V, H, W, 3, dtype=torch.float32, device=dev),
-               normal=None if normals is None else torch.empty(V, H, W, 3, dtype=torch.float32, device=dev))
+    _lib.launch("mi3d_mesh_visibility", vertices, _lib.ptr(vertices), int(vertices.shape[0]), _lib.ptr(triangles),
+                int(triangles.shape[0]), _lib.ptr(records), V, H, W, _lib.ptr(vis), _lib.ptr(counts))
+    return vis, counts
+
+
+def _shade(vertices, triangles, records, H, W, vis, colors=None, uvs=None, texture=None, normals=None, bg=(1.0, 1.0, 1.0),
+           image_only=False):
+    """mi3d_mesh_shade - mi3d_mesh_shade_f32 for a float32 texture - from the keys `vis`: _render_buffers' dict without
+    vis and counts; with `image_only` the image alone is written and the other entries are None."""
+    dev, V = vertices.device, int(records.shape[0])
+    nv, nt = int(vertices.shape[0]), int(triangles.shape[0])
+
+    def buffer(*shape, dtype=torch.float32, wanted=True):
+        return torch.empty(V, H, W, *shape, dtype=dtype, device=dev) if wanted else None
+
+    out = dict(image=buffer(3), alpha=buffer(dtype=torch.uint8, wanted=not image_only), depth=buffer(wanted=not image_only),
+               tri=buffer(dtype=torch.int32, wanted=not image_only), bary=buffer(3, wanted=not image_only),
+               normal=buffer(3, wanted=normals is not None and not image_only))
     T = 0 if texture is None else int(texture.shape[0])
     background = (C.c_float * 3)(*[float(b) for b in bg])
-    _lib.launch("mi3d_mesh_shade", vertices, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, _lib.ptr(records), V, H, W,
-                _lib.ptr(vis), _lib.ptr(colors), _lib.ptr(uvs), _lib.ptr(texture), T, _lib.ptr(normals), background,
-                _lib.ptr(out["image"]), _lib.ptr(out["normal"]), _lib.ptr(out["depth"]), _lib.ptr(out["tri"]),
-                _lib.ptr(out["bary"]), _lib.ptr(out["alpha"]))
+    entry = "mi3d_mesh_shade_f32" if texture is not None and texture.dtype == torch.float32 else "mi3d_mesh_shade"
+    _lib.launch(entry, vertices, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, _lib.ptr(records), V, H, W,
+                _lib.ptr(vis), _lib.ptr(colors), _lib.ptr(uvs), _lib.ptr(texture), T,
+                _lib.ptr(normals if out["normal"] is not None else None), background, _lib.ptr(out["image"]),
+                _lib.ptr(out["normal"]), _lib.ptr(out["depth"]), _lib.ptr(out["tri"]), _lib.ptr(out["bary"]),
+                _lib.ptr(out["alpha"]))
     return out
+
+
+def _shade_backward(vertices, triangles, records, H, W, vis, dimage, uvs, shape):
+    """mi3d_mesh_shade_backward on the current stream: the gradient float32 of `shape` - [nv, 3] without `uvs`, [T, T, 3]
+    with them - from dimage float32 [V, H, W, 3].  The workspace comes from torch's allocator; nothing is read back."""
+    dev, V = vertices.device, int(records.shape[0])
+    grad = torch.empty(shape, dtype=torch.float32, device=dev)
+    ws_bytes = int(_lib.lib().mi3d_mesh_shade_backward_workspace(grad.numel()))
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    textured = uvs is not None
+    _lib.launch("mi3d_mesh_shade_backward", vertices, _lib.ptr(vertices), int(vertices.shape[0]), _lib.ptr(triangles),
+                int(triangles.shape[0]), _lib.ptr(records), V, H, W, _lib.ptr(vis), _lib.ptr(dimage), _lib.ptr(uvs),
+                int(shape[0]) if textured else 0, _lib.ptr(None if textured else grad), _lib.ptr(grad if textured else None),
+                _lib.ptr(ws), ws_bytes)
+    return grad
+
+
+class _ShadeColour(torch.autograd.Function):
+    """The shading pass as a differentiable function of its colour source (include/mi3d.h Part 18): `source` is colors
+    [nv, 3] without `uvs` and a float32 texture [T, T, 3] with them.  Visibility and geometry are constants: the keys
+    `vis` are saved for backward, and only `source` receives a gradient.  `out` (a dict) takes the buffers."""
+
+    @staticmethod
+    def forward(ctx, source, vertices, triangles, records, H, W, vis, uvs, normals, bg, image_only, out):
+        src = dict(colors=source) if uvs is None else dict(uvs=uvs, texture=source)
+        out.update(_shade(vertices, triangles, records, H, W, vis, normals=normals, bg=bg, image_only=image_only, **src))
+        ctx.save_for_backward(vertices, triangles, records, vis, *(() if uvs is None else (uvs,)))
+        ctx.size = (H, W, tuple(source.shape))
+        return out["image"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dimage):
+        vertices, triangles, records, vis, *uvs = ctx.saved_tensors
+        H, W, shape = ctx.size
+        grad = _shade_backward(vertices, triangles, records, H, W, vis, dimage.contiguous().float(),
+                               uvs[0] if uvs else None, shape)
+        return (grad,) + (None,) * 11
 
 
 def box_average(x, ssaa):
@@ -819,8 +883,11 @@ def render(vertices, triangles, c2w, K, H, W, colors=None, uvs=None, texture=Non
     """Images of an indexed mesh from V pinhole cameras (include/mi3d.h Part 17): vertices float32 [nv, 3], triangles
     int32 [nt, 3] on the GPU; c2w [V, 4, 4], K [3, 3], H, W as render_depth takes them.  The colour comes from exactly one
     of `colors` float32 [nv, 3] (per vertex, interpolated perspective-correctly) and `uvs` float32 [3 nt, 2] with
-    `texture` uint8 [T, T, 3] (what bake_texture and bake_views return: bilinear taps, row 0 the top row); all on the
-    mesh's device.  `normals` float32 [nv, 3] are interpolated too and needed by every shading but "albedo".
+    `texture` uint8 [T, T, 3] (what bake_texture and bake_views return: bilinear taps, row 0 the top row) or float32
+    [T, T, 3] (the blend of the taps as it is, no / 255); all on the mesh's device.  When `colors` or a float32 `texture`
+    requires grad, the image is differentiable in it (include/mi3d.h Part 18: visibility and geometry are constants;
+    `vertices`, `uvs` or `normals` that require grad raise Mi3dError); otherwise the launches and the bits are the same
+    with or without autograd.  `normals` float32 [nv, 3] are interpolated too and needed by every shading but "albedo".
 
     `shading` as the field's (the reference's nerf/network_tcnn.py:159-168), composed in torch from the kernel's albedo
     and normal buffers, n the normalised interpolated normal and l `light_d` (3 numbers or [V, 3], normalised here;
@@ -846,6 +913,10 @@ def render(vertices, triangles, c2w, K, H, W, colors=None, uvs=None, texture=Non
     _check_view_size(V, ssaa * H, ssaa * W)
     vertices, triangles = _check_mesh(vertices, triangles)
     nv, nt, dev = int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
+    for name, x in (("vertices", vertices), ("uvs", uvs), ("normals", normals)):
+        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+            raise Mi3dError(f"render: {name} requires grad, but visibility and geometry are constants here: only colors "
+                            f"and a float32 texture are differentiable (detach {name})")
     if (colors is None) == (uvs is None and texture is None):
         raise Mi3dError("render takes exactly one colour source: colors, or uvs with texture")
     if colors is not None:
@@ -858,7 +929,7 @@ def render(vertices, triangles, c2w, K, H, W, colors=None, uvs=None, texture=Non
         uvs = _lib.dev_f32(uvs, "uvs", 2)
         if not isinstance(texture, torch.Tensor):
             raise TypeError("texture must be a torch.Tensor")
-        texture = _lib.dev_typed(texture, "texture", torch.uint8)
+        texture = _lib.dev_typed(texture, "texture", torch.float32 if texture.dtype == torch.float32 else torch.uint8)
         if tuple(uvs.shape) != (3 * nt, 2) or uvs.device != dev:
             raise Mi3dError(f"uvs must be [{3 * nt}, 2] on the mesh's device (got {tuple(uvs.shape)} on {uvs.device})")
         if texture.dim() != 3 or texture.shape[0] != texture.shape[1] or texture.shape[2] != 3 or texture.device != dev or \
@@ -871,8 +942,16 @@ def render(vertices, triangles, c2w, K, H, W, colors=None, uvs=None, texture=Non
             raise Mi3dError(f"normals must be [{nv}, 3] on the mesh's device (got {tuple(normals.shape)} on {normals.device})")
     elif shading != "albedo":
         raise Mi3dError(f"shading={shading!r} needs normals")
-    buf = _render_buffers(vertices, triangles, torch.from_numpy(records).to(dev), ssaa * H, ssaa * W, colors, uvs, texture,
-                          normals, bg)
+    source = colors if colors is not None else texture
+    if torch.is_grad_enabled() and source.requires_grad:       # Part 18: the image as a function of its colour source
+        rec = torch.from_numpy(records).to(dev)
+        vis, counts = _visibility(vertices, triangles, rec, ssaa * H, ssaa * W)
+        buf = dict(vis=vis, counts=counts)
+        image = _ShadeColour.apply(source, vertices, triangles, rec, ssaa * H, ssaa * W, vis, uvs, normals, bg, False, buf)
+        buf["image"] = image
+    else:
+        buf = _render_buffers(vertices, triangles, torch.from_numpy(records).to(dev), ssaa * H, ssaa * W, colors, uvs,
+                              texture, normals, bg)
     bad = int(buf["counts"][0])                                 # the one host read
     if bad != 0:
         raise Mi3dError(f"{bad} of the {nt} triangles hold a vertex index outside [0, {nv})")
@@ -934,6 +1013,105 @@ def quantise(image):
     value or a NaN - what write_png is given for the previews."""
     a = torch.nan_to_num(image.float() * 255.0, nan=0.0, posinf=255.0, neginf=0.0)
     return a.floor().clamp(0.0, 255.0).to(torch.uint8)
+
+
+FIT_KEYS = ("iterations", "lr")
+MAX_FIT_ITERATIONS = 100000
+
+
+def _check_fit(iterations, lr):
+    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or \
+            not 1 <= iterations <= MAX_FIT_ITERATIONS:
+        raise Mi3dError(f"iterations must be an integer in [1, {MAX_FIT_ITERATIONS}] (got {iterations!r})")
+    if isinstance(lr, (bool, np.bool_)) or not isinstance(lr, (int, float, np.integer, np.floating)) or not 0 < lr <= 1:
+        raise Mi3dError(f"lr must be a number in (0, 1] (got {lr!r})")
+    return int(iterations), float(lr)
+
+
+def _fit(vertices, triangles, uvs, start, images, c2w, K, masks, weights, iterations, lr, ssaa, bg_color, return_history):
+    """fit_texture (with uvs) and fit_colors (without): see there."""
+    iterations, lr = _check_fit(iterations, lr)
+    _, ssaa = _check_shading("albedo", ssaa)
+    _, weights, _, _, (V, H, W) = check_views(images, c2w, K, masks, weights)
+    if not weights.sum() > 0:
+        raise Mi3dError("weights must not all be zero")
+    Ks = _host64(K) * np.array([[ssaa], [ssaa], [1.0]])
+    records = view_records(c2w, Ks)
+    _, bg, _ = _check_render_options(0.0, bg_color, None, V)
+    _check_view_size(V, ssaa * H, ssaa * W)
+    vertices, triangles = _check_mesh(vertices, triangles)
+    nv, nt, dev = int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
+    if not isinstance(start, torch.Tensor):
+        raise TypeError("the start must be a torch.Tensor")
+    if uvs is None:
+        start = _lib.dev_f32(start, "colors", 3)
+        if tuple(start.shape) != (nv, 3) or start.device != dev:
+            raise Mi3dError(f"colors must be [{nv}, 3] on the mesh's device (got {tuple(start.shape)} on {start.device})")
+    else:
+        uvs = _lib.dev_f32(uvs, "uvs", 2)
+        if tuple(uvs.shape) != (3 * nt, 2) or uvs.device != dev:
+            raise Mi3dError(f"uvs must be [{3 * nt}, 2] on the mesh's device (got {tuple(uvs.shape)} on {uvs.device})")
+        start = _lib.dev_typed(start, "texture", torch.float32 if start.dtype == torch.float32 else torch.uint8)
+        if start.dim() != 3 or start.shape[0] != start.shape[1] or start.shape[2] != 3 or start.device != dev or \
+                not MIN_TEXTURE <= start.shape[0] <= MAX_TEXTURE:
+            raise Mi3dError(f"texture must be [T, T, 3] with T in [{MIN_TEXTURE}, {MAX_TEXTURE}] on the mesh's device (got "
+                            f"{tuple(start.shape)} on {start.device})")
+        if start.dtype == torch.uint8:
+            start = start.float() / 255.0                       # what mi3d_mesh_shade makes of a byte
+    rec = torch.from_numpy(records).to(dev)
+    target = _to_dev(images, torch.float32, dev)
+    pixel = torch.from_numpy(weights).to(dev)[:, None, None].expand(V, H, W)
+    if masks is not None:
+        pixel = pixel * (_to_dev(masks, torch.float32, dev) != 0)
+    pixel = (pixel / (3.0 * pixel.sum().clamp(min=1e-30)))[..., None]     # the weighted mean over pixels and channels
+    vis, counts = _visibility(vertices, triangles, rec, ssaa * H, ssaa * W)     # once: the geometry does not move
+    with torch.enable_grad():
+        value = start.detach().clone().requires_grad_(True)
+        optimiser = torch.optim.Adam([value], lr=lr)
+        history = []
+        for _ in range(iterations):
+            optimiser.zero_grad(set_to_none=True)
+            image = _ShadeColour.apply(value, vertices, triangles, rec, ssaa * H, ssaa * W, vis, uvs, None, bg, True, {})
+            loss = (pixel * (box_average(image, ssaa) - target) ** 2).sum()
+            loss.backward()
+            optimiser.step()
+            with torch.no_grad():
+                value.clamp_(0.0, 1.0)
+            history.append(loss.detach())
+    bad, losses = int(counts[0]), torch.stack(history).cpu().tolist()    # the host reads: after the last launch
+    if bad != 0:
+        raise Mi3dError(f"{bad} of the {nt} triangles hold a vertex index outside [0, {nv})")
+    value = value.detach()
+    return (value, losses) if return_history else value
+
+
+def fit_texture(vertices, triangles, uvs, texture, images, c2w, K, masks=None, weights=None, iterations=200, lr=0.01,
+                ssaa=1, bg_color=1.0, return_history=False):
+    """A texture fitted to VIEWS through the renderer that will show it (include/mi3d.h Part 18): Adam (torch's, its
+    default betas and eps) on the weighted mean squared error between render(..., uvs=uvs, texture=value, ssaa=ssaa,
+    bg_color=bg_color) and `images` - the mean over the three channels of the pixels whose mask is non-zero, view v's
+    pixels weighted by weights[v] - starting from `texture` (float32 [T, T, 3], or uint8, read as byte / 255), the values
+    clamped to [0, 1] after every step.  The gradient reaches the four bilinear taps of every drawn pixel, gutter texels
+    included; a texel no pixel touches receives an exact zero gradient and keeps its value bit for bit.
+
+    vertices, triangles, uvs as render takes them; images float [V, H, W, 3], c2w, K, masks and weights as bake_views
+    takes them, checked by its rules before anything is launched.  Visibility is computed once.  Returns the fitted
+    float32 [T, T, 3] on the mesh's device; with `return_history=True` also the list of the loss before each step, which
+    stays on the device until the loop is over and is read once.  Pass the result through quantise() for a PNG.
+
+    iterations=200 and lr=0.01 are choices nobody has measured on a trained object."""
+    if uvs is None:
+        raise Mi3dError("fit_texture needs uvs")
+    return _fit(vertices, triangles, uvs, texture, images, c2w, K, masks, weights, iterations, lr, ssaa, bg_color,
+                return_history)
+
+
+def fit_colors(vertices, triangles, colors, images, c2w, K, masks=None, weights=None, iterations=200, lr=0.01, ssaa=1,
+               bg_color=1.0, return_history=False):
+    """fit_texture for vertex colours: `colors` float32 [nv, 3] is the start, render(..., colors=value) the model; a
+    vertex no drawn pixel's triangle names keeps its value bit for bit.  Returns the fitted float32 [nv, 3]."""
+    return _fit(vertices, triangles, None, colors, images, c2w, K, masks, weights, iterations, lr, ssaa, bg_color,
+                return_history)
 
 
 def camera_rays(c2w, K, H, W, device):
@@ -1136,7 +1314,7 @@ def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, norma
     if views is not None:                                       # before any work
         if texture_size is None:
             raise Mi3dError("export_mesh: views colour the texture: give texture_size too")
-        views = _check_views_dict(views)
+        views, fit = _check_views_dict(views)
     decimate, target_faces = _check_decimate(decimate, target_faces)
     cleaning = min_faces is not None or min_diagonal is not None or largest is not False
     if cleaning:
@@ -1174,6 +1352,11 @@ def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, norma
         albedo = vertex_albedo(model, vertices)
         if views is not None:                                   # after the floater filter and the decimation
             image, vt = bake_views(model, vertices, triangles, texture_size, ssaa=ssaa, **views)[:2]
+            if fit is not None:                                 # the bake corrected by what the renderer reads from it
+                start = image.float() / 255.0
+                fitted = fit_texture(vertices, triangles, vt, start, views["images"], views["c2w"], views["K"],
+                                     views.get("masks"), views.get("weights"), **fit)
+                image = torch.where(fitted == start, image, quantise(fitted))     # an untouched texel keeps its byte
         elif texture_size is not None:
             image, vt, _ = bake_texture(model, vertices, triangles, texture_size, ssaa)
         vn = vertex_normals(model, vertices).cpu().numpy() if normals else None

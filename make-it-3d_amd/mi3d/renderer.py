@@ -152,7 +152,12 @@ class NeRFRenderer(nn.Module):
         colour, every other keeps the field's albedo; what refine.render_views returns plugs in.  It needs
         `texture_size` (without it: Mi3dError before any work), runs after the floater filter and the decimation and
         writes the same three files.  With `views=None` nothing of this runs and the files are byte for byte what they
-        were without the argument.  `smooth=n` (an integer in [1, 1000]) or `smooth=dict(iterations=, lam=, mu=,
+        were without the argument.  `views` may also hold `fit=dict(iterations=200, lr=0.01)`: the baked image is then the
+        start of mesh.fit_texture against the same views, masks and weights (include/mi3d.h Part 18) - Adam
+        on the error of the mesh's own renders, so that the texture is corrected by what the renderer reads from it -
+        and the result is written through mesh.quantise; a texel no pixel of any view touches keeps its byte.  Both
+        defaults are choices nobody has measured on a trained object.  Without `fit` the files are byte for byte what
+        they were.  `smooth=n` (an integer in [1, 1000]) or `smooth=dict(iterations=, lam=, mu=,
         pin_border=, max_move=)` runs n iterations of Taubin's lambda | mu smoothing over the vertices (mesh.smooth,
         include/mi3d.h Part 16) after the floater filter and the decimation and before the atlas check, the
         colours, the texture bake (field or views) and the normals, which therefore all see the smoothed vertices; the
