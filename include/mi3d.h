@@ -1141,6 +1141,98 @@ int mi3d_mesh_shade_backward(const float *vertices, unsigned long long nv, const
                              const float *dimage, const float *vt, uint32_t T, float *grad_colors, float *grad_texture,
                              void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------ Part 19: edge-collapse decimation (mesh export) */
+
+/* Decimation of an indexed triangle mesh to a face count by quadric edge collapse (Garland and Heckbert, "Surface
+ * simplification using quadric error metrics", SIGGRAPH 1997), in rounds of INDEPENDENT collapses.  Where Part 14
+ * rounds every corner to a cluster mean, joins sheets closer than a cell and leaves a non-manifold mesh, a collapse
+ * keeps a closed manifold closed and manifold, places the new vertex where the planes around it meet, and stops on the
+ * face count asked for.  Integer atomics only; every binary64 operation is rounded separately (no fused multiply-add),
+ * no sqrt: two runs give byte-identical buffers, and a restatement in Python floats (tests/mesh_collapse_model.py)
+ * gives the same bytes.  Projects of this family decimate through pymeshlab, which is on no machine this project builds
+ * on: the semantics below are this project's own contract - PARITY UNPINNED, the standing of Parts 13 to 16.  Added
+ * under ABI version 5: new symbols only.  (Declared ahead of the point-cloud part, like Parts 12 to 18.)
+ *
+ * vertices float[nv][3], triangles int32[nt][3]; nv <= 2^31 - 1, nt <= 2^30 (a row slot and an edge id are uint32 below
+ * 3 nt).  target_faces >= 0 (uint64); max_error binary32, >= 0, +infinity for none.
+ *   - USABLE TRIANGLES: Part 16's rule (indices in [0, nv), pairwise distinct, three vertices finite in the input).
+ *     The others are never dereferenced past the index check, are counted, and take no part.  The usable triangles are
+ *     LIVE at the start.  A triangle keeps its input index t0 and its three corner slots for the whole run; a corner
+ *     changes only by being renamed to the vertex its vertex was collapsed into.
+ *   - QUADRICS, once: for a usable triangle with corners widened to binary64, n = (p1 - p0) x (p2 - p0) (u = p1 - p0,
+ *     v = p2 - p0, n = (uy vz - uz vy, uz vx - ux vz, ux vy - uy vx)), s = n.n, d = -(n.p0), every dot product
+ *     (x x' + y y') + z z'.  K = the ten products e_i e_j (i <= j) of e = (nx, ny, nz, d), each divided by s, in the
+ *     order q = (A00, A01, A02, b0, A11, A12, b1, A22, b2, c).  s == 0 or a non-finite s: K contributes nothing, counted.
+ *     Q_v = the sum of K_t over the usable triangles that cite v in ASCENDING triangle index, from +0.  A vertex cited
+ *     by more than MI3D_COLLAPSE_MAX_ROW = 1024 usable triangles gets a quadric of NaNs instead (its row is not sorted;
+ *     Part 16's reason): no edge at it ever has a cost.  A collapse sets Q_a <- Q_a + Q_b, entry by entry.
+ *   - E(x) = x^T A x + 2 b^T x + c, evaluated as: t0 = (A00 x + A01 y) + A02 z, t1 = (A01 x + A11 y) + A12 z,
+ *     t2 = (A02 x + A12 y) + A22 z, quad = (x t0 + y t1) + z t2, lin = (b0 x + b1 y) + b2 z, E = (quad + 2 lin) + c.
+ *   - ROUNDS.  Everything below is recomputed every round from the live triangles.  deg v = the live triangles that
+ *     cite v; N(v) = the other corners of those triangles.
+ *   - LOCKS: a vertex is locked iff it lies on an edge that exactly ONE live triangle holds, or deg v >
+ *     MI3D_COLLAPSE_MAX_DEGREE = 64.  A locked vertex neither moves nor disappears.
+ *   - CANDIDATES: the directed edge a -> b with a < b, in live triangle t0 from corner slot i to slot (i + 1) mod 3, with
+ *     c at the third slot, is a candidate iff all of: both ends are unlocked; exactly two live triangles hold the edge
+ *     and the other one runs b -> a (d = its third corner); c != d and N(a) and N(b) share no vertex but c and d (the
+ *     link condition); 3 <= deg a + deg b - 4 <= 64; deg c >= 4 and deg d >= 4; the placement below yields an x*; for
+ *     every other live triangle at a or b, with that corner at x*, n_old . n_new > 0 and n_new . n_new > 0 (normals as
+ *     above, in the triangle's own corner order, the other corners where they are); c32 = (float)max(E(x*), 0) <=
+ *     max_error.
+ *   - PLACEMENT with Q = Q_a + Q_b: the points p_a, p_b, m = (p_a + p_b) * 0.5 and - iff |det A| > 1e-3 ((tr tr) tr),
+ *     tr = ((A00 + A11) + A22) / 3, det A != 0 and |o - m|^2 <= |p_b - p_a|^2 - the optimum o = -A^-1 b by the adjugate:
+ *     c00 = A11 A22 - A12 A12, c01 = A02 A12 - A01 A22, c02 = A01 A12 - A02 A11, c11 = A00 A22 - A02 A02,
+ *     c12 = A01 A02 - A00 A12, c22 = A00 A11 - A01 A01, det = (A00 c00 + A01 c01) + A02 c02,
+ *     o = (-((c00 b0 + c01 b1) + c02 b2) / det, -((c01 b0 + c11 b1) + c12 b2) / det, -((c02 b0 + c12 b1) + c22 b2) / det).
+ *     Each point is rounded ONCE to binary32 (m and o; the distance test uses them unrounded) and E is evaluated at the
+ *     rounded point, so the cost is that of the vertex as stored.  The smallest E that is not NaN wins, ties to the
+ *     earlier point in this order; no such E: no candidate.
+ *   - KEY of a candidate in round r (r = the rounds that had a winner so far): upper word (bits(c32) & 0xFFF00000) | h,
+ *     h = ((a 2654435761 ^ b 2246822519 ^ r 3266489917) >> 7) & 0xFFFFF in uint32 arithmetic; lower word the edge id
+ *     3 t0 + i.  A cost bucket, a per-round hash, a unique id.
+ *   - INDEPENDENCE: every candidate does a 64-bit atomicMin of its key on claim[a] and claim[b].  It WINS iff
+ *     claim[a] == claim[b] == key and claim[v] >= key for every v in N(a) and N(b).  No end of one winner lies in the
+ *     closed neighbourhood of another's ends: their triangles are disjoint, and nothing one's tests read is changed by
+ *     the other.
+ *   - QUOTA: with L live triangles at the start of the round, quota = ceil((L - target_faces) / 2); the winners are
+ *     ranked by ascending edge id and the ranks below the quota are APPLIED: rep[b] = a, P[a] = x*, Q_a += Q_b; then
+ *     every live triangle renames its corners through rep and dies if two coincide, and rep[v] <- rep[rep[v]].
+ *   - A round is a NO-OP once L <= target_faces or once the round before it had no winner; both are read on the device.
+ *   - OUTPUT: the live triangles by ascending t0 in their own corner order; the vertices they cite by ascending index,
+ *     at their current positions; vertex_map int32[nv] = the output index of rep[v], -1 if it is not emitted.
+ *   - counts (device uint64[8], 8-byte aligned, zeroed by begin): [0] output vertices and [1] output triangles ([1] is
+ *     the live count after begin and after every round, [0] is filled by count), [2] unusable triangles in the low
+ *     word, usable triangles without a plane (s == 0) << 32, [3] rounds that had a winner, [4] non-finite vertices,
+ *     [5] collapses applied, [6] vertices locked in the last round that ran, [7] row slots or output rows that could
+ *     not be placed - non-zero means the result is invalid.
+ *
+ *   mi3d_mesh_collapse_workspace  host only: bytes of device scratch for a mesh of this size (0 for nv = nt = 0 and for
+ *                          sizes out of range).  ALL state of a run lives there.
+ *   mi3d_mesh_collapse_begin    usable flags, quadrics, state; counts zeroed and [1], [2], [4] filled.
+ *   mi3d_mesh_collapse_rounds   n_rounds <= 4096 rounds.  After k rounds in all, counts[3] < k tells that the run is
+ *                          over: counts[1] <= target_faces, or stalled above it.
+ *   mi3d_mesh_collapse_count    counts[0], counts[1] and the output numbering; the caller reads counts here to size
+ *   mi3d_mesh_collapse_emit     out_vertices float[nv_cap][3], out_triangles int32[nt_cap][3], vertex_map int32[nv];
+ *                          nothing is written past the caps, what could not be placed is counted in counts[7].
+ * All calls of one run go to the same stream with the same nv, nt, ws, ws_bytes and counts; count directly before
+ * emit.  No entry point allocates or synchronises.  nv = nt = 0 launches nothing and succeeds; nv = 0 or nt = 0 alone
+ * is served.  Sizes out of range, a max_error that is negative or NaN, n_rounds > 4096, a workspace that is NULL, too
+ * small or not 8-byte aligned, a counts that is NULL or not 8-byte aligned and every other NULL pointer that would be
+ * dereferenced are refused (hipErrorInvalidValue) and launch nothing. */
+#define MI3D_COLLAPSE_MAX_DEGREE 64
+#define MI3D_COLLAPSE_MAX_ROW 1024
+size_t mi3d_mesh_collapse_workspace(unsigned long long nv, unsigned long long nt);
+int mi3d_mesh_collapse_begin(const float *vertices, unsigned long long nv, const int32_t *triangles, unsigned long long nt,
+                             void *ws, size_t ws_bytes, unsigned long long *counts, void *stream);
+int mi3d_mesh_collapse_rounds(unsigned long long nv, unsigned long long nt, unsigned long long target_faces,
+                              float max_error, uint32_t n_rounds, void *ws, size_t ws_bytes, unsigned long long *counts,
+                              void *stream);
+int mi3d_mesh_collapse_count(unsigned long long nv, unsigned long long nt, void *ws, size_t ws_bytes,
+                             unsigned long long *counts, void *stream);
+int mi3d_mesh_collapse_emit(unsigned long long nv, unsigned long long nt, void *ws, size_t ws_bytes, float *out_vertices,
+                            unsigned long long nv_cap, int32_t *out_triangles, unsigned long long nt_cap,
+                            int32_t *vertex_map, unsigned long long *counts, void *stream);
+
 /* ------------------------------------------------------------------ Part 11: the refine stage's point cloud */
 
 /* Depth / mask / rgb views -> the coloured point cloud the refine stage starts from: what `depth2point`,

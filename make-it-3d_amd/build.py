@@ -25,6 +25,7 @@ UNITS = [
     ("meshclean.hip", ["-ffp-contract=off"]),
     ("meshsimplify.hip", ["-ffp-contract=off"]),
     ("meshsmooth.hip", ["-ffp-contract=off"]),
+    ("meshcollapse.hip", ["-ffp-contract=off"]),
     ("texture.hip", ["-ffp-contract=off"]),
     ("textureviews.hip", ["-ffp-contract=off"]),
     ("meshrender.hip", ["-ffp-contract=off"]),
@@ -32,7 +33,7 @@ UNITS = [
     ("pointcloud.hip", ["-ffp-contract=off"]),
     ("canny.hip", []),
 ]
-HEADERS = ["mi3d_common.h", "mi3d_grid.h", "mi3d_grid_plan.h", "mi3d_dev.h", "lds_transpose.h", "mi3d_mc_tables.h", "mi3d_meshraster.h", "mi3d_scan.h", os.path.join("..", "..", "include", "mi3d.h")]
+HEADERS = ["mi3d_common.h", "mi3d_grid.h", "mi3d_grid_plan.h", "mi3d_dev.h", "lds_transpose.h", "mi3d_mc_tables.h", "mi3d_meshraster.h", "mi3d_scan.h", "mi3d_incidence.h", os.path.join("..", "..", "include", "mi3d.h")]
 
 
 def _newer(src, dst):

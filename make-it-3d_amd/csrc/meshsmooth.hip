@@ -29,7 +29,7 @@
 #include <cmath>
 
 #include "../../include/mi3d.h"
-#include "mi3d_scan.h"
+#include "mi3d_incidence.h"
 
 namespace {
 
@@ -113,30 +113,21 @@ __global__ __launch_bounds__(kBlock) void k_sm_degree(const float *__restrict__ 
     wave_count(live && !ok, &counts[kUnusable]);
 }
 
+// the three scan steps of mi3d_incidence.h, which meshcollapse.hip shares
 __global__ __launch_bounds__(kBlock) void k_sm_block_sums(uint32_t nv, SmoothWorkspace w) {
     __shared__ uint32_t wave_sum[kWaves];
-    const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
-    uint32_t total;
-    block_scan<kWaves>(v < nv ? (uint32_t)w.cur[v] : 0u, wave_sum, total);
-    if (threadIdx.x == 0) w.block[blockIdx.x] = total;
+    mi3d_incidence::block_sums(w.cur, nv, w.block, wave_sum);
 }
 
-// exclusive scan of the row of block sums in place; the total -> offs[nv]
 __global__ __launch_bounds__(kRowThreads) void k_sm_scan(SmoothWorkspace w, uint32_t nv, uint32_t nb) {
     __shared__ uint32_t wave_sum[kRowWaves];
     __shared__ uint32_t base;
-    const uint32_t total = scan_row(w.block, nb, wave_sum, &base);
-    if (threadIdx.x == 0) w.offs[nv] = total;
+    mi3d_incidence::scan_blocks(w.block, nb, w.offs, nv, wave_sum, &base);
 }
 
 __global__ __launch_bounds__(kBlock) void k_sm_offsets(uint32_t nv, SmoothWorkspace w) {
     __shared__ uint32_t wave_sum[kWaves];
-    const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
-    uint32_t total;
-    const uint32_t rank = block_scan<kWaves>(v < nv ? (uint32_t)w.cur[v] : 0u, wave_sum, total);
-    if (v >= nv) return;
-    w.offs[v] = w.block[blockIdx.x] + rank;
-    w.cur[v] = 0;  // from here on the cursor of the row
+    mi3d_incidence::offsets(w.cur, nv, w.block, w.offs, wave_sum);
 }
 
 __global__ __launch_bounds__(kBlock) void k_sm_fill(const float *__restrict__ vertices, uint32_t nv,

@@ -1,8 +1,9 @@
 // The compaction scaffolding of the mesh, point-cloud and raster units (wave64): the exclusive scan over a workgroup,
 // the looped scan of a row of block sums by one workgroup of 1024, and the small predicates and host helpers those
 // units share.  Every "count per workgroup / scan the block sums / emit at block base + rank" pipeline in mesh.hip,
-// meshclean.hip, meshsimplify.hip, meshsmooth.hip, pointcloud.hip and raster.hip goes through the two scans here; the
-// scans of raymarching.hip and hashgrid.hip have other shapes and stay where they are.
+// meshclean.hip, meshsimplify.hip, meshsmooth.hip, meshcollapse.hip, pointcloud.hip and raster.hip goes through the two
+// scans here (the vertex -> row steps meshsmooth.hip and meshcollapse.hip share are mi3d_incidence.h); the scans of
+// raymarching.hip and hashgrid.hip have other shapes and stay where they are.
 #pragma once
 #include <hip/hip_runtime.h>
 

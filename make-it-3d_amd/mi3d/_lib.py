@@ -133,6 +133,11 @@ _SIGNATURES = {
                             vp, vp, vp],
     "mi3d_mesh_shade_backward": [vp, C.c_uint64, vp, C.c_uint64, vp, u32, u32, u32, vp, vp, vp, u32, vp, vp, vp, C.c_size_t,
                                  vp],
+    # Part 19 -----------------------------------------------------------------------------------------
+    "mi3d_mesh_collapse_begin": [vp, C.c_uint64, vp, C.c_uint64, vp, C.c_size_t, vp, vp],
+    "mi3d_mesh_collapse_rounds": [C.c_uint64, C.c_uint64, C.c_uint64, f32, u32, vp, C.c_size_t, vp, vp],
+    "mi3d_mesh_collapse_count": [C.c_uint64, C.c_uint64, vp, C.c_size_t, vp, vp],
+    "mi3d_mesh_collapse_emit": [C.c_uint64, C.c_uint64, vp, C.c_size_t, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp],
 }
 
 # host-only queries whose return value is not a hipError_t: (argtypes, restype), bound in lib() like the block below
@@ -148,6 +153,7 @@ _LATE_SIGNATURES = {
     "mi3d_mesh_simplify_workspace": ([C.c_uint64, C.c_uint64, C.c_int], C.c_size_t),
     "mi3d_mesh_smooth_workspace": ([C.c_uint64, C.c_uint64], C.c_size_t),
     "mi3d_mesh_shade_backward_workspace": ([C.c_uint64], C.c_size_t),
+    "mi3d_mesh_collapse_workspace": ([C.c_uint64, C.c_uint64], C.c_size_t),
 }
 
 

@@ -436,6 +436,117 @@ def _smooth_export(vertices, triangles, smoothing, h):
                   return_stats=True)[0]
 
 
+COLLAPSE_COUNTS = ("vertices", "triangles", "unusable_triangles", "rounds", "non_finite_vertices", "collapses",
+                   "locked_vertices", "errors")             # counts[0 .. 7] of include/mi3d.h Part 19
+COLLAPSE_KEYS = ("target_faces", "max_error", "max_rounds")
+COLLAPSE_MAX_ROUNDS, COLLAPSE_ROUNDS_PER_CALL = 1 << 20, 4096
+
+
+def _check_collapse(target_faces, max_error=None, max_rounds=256, rounds_per_read=8):
+    """The arguments of collapse() that need no tensor: (target_faces, max_error as a float or None, max_rounds,
+    rounds_per_read)."""
+    for name, x, lo, hi in (("target_faces", target_faces, 0, 2 ** 63 - 1), ("max_rounds", max_rounds, 0, COLLAPSE_MAX_ROUNDS),
+                            ("rounds_per_read", rounds_per_read, 1, COLLAPSE_ROUNDS_PER_CALL)):
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+            raise Mi3dError(f"{name} must be an integer (got {x!r})")
+        if not lo <= int(x) <= hi:
+            raise Mi3dError(f"{name} must lie in [{lo}, {hi}] (got {x})")
+    if max_error is not None:
+        if isinstance(max_error, (bool, np.bool_)) or not isinstance(max_error, (int, float, np.integer, np.floating)):
+            raise Mi3dError(f"max_error must be a number or None (got {max_error!r})")
+        if not float(max_error) >= 0.0:                         # false for NaN
+            raise Mi3dError(f"max_error must be >= 0 and not NaN (got {max_error!r})")
+        with np.errstate(over="ignore"):
+            max_error = float(np.float32(max_error))            # binary32, as the kernels take it
+    return int(target_faces), max_error, int(max_rounds), int(rounds_per_read)
+
+
+def collapse(vertices, triangles, target_faces, max_error=None, max_rounds=256, rounds_per_read=8, return_stats=False):
+    """Decimation to `target_faces` faces by quadric edge collapse, the contract of include/mi3d.h Part 19: rounds of
+    independent collapses, each of an interior edge whose removal keeps the surface manifold and flips no triangle, the
+    new vertex at the point of least quadric error among the two ends, the midpoint and (where the quadric is well
+    conditioned) its optimum.  vertices float32 [nv, 3], triangles int32 [nt, 3] on the GPU.  `max_error` (a number
+    >= 0, None: no limit) bounds the quadric error of a collapse; at most `max_rounds` rounds run, `rounds_per_read` of
+    them between two host reads of the counts.  Vertices on an open edge and vertices of more than 64 triangles stay
+    where they are.  Returns (vertices [kv, 3], triangles [kt, 3], vertex_map int32 [nv]) on the same device - the
+    surviving triangles in their original order and corner order, renumbered; the vertices they cite in ascending
+    original index; vertex_map the new index of the vertex every old vertex was collapsed into, -1 where that is not
+    emitted - and, with `return_stats=True`, a dict of the counts named in COLLAPSE_COUNTS (`unusable_triangles` without
+    the planeless ones, which stand in `planeless_triangles`) plus `rounds_launched`, `done` (the face count is at or
+    below the target) and `stalled` (a round found no collapse above the target: not an error).  A closed mesh that does
+    not stall ends on `target_faces` or one face less.  Triangles with an index outside [0, nv), a repeated index or a
+    non-finite vertex are counted and dropped.  The arguments are checked first, on any device."""
+    target, max_error, max_rounds, per_read = _check_collapse(target_faces, max_error, max_rounds, rounds_per_read)
+    vertices, triangles = _check_mesh(vertices, triangles)
+    nv, nt, dev = int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
+    if nv == 0 and nt == 0:
+        out = (vertices.new_empty(0, 3), triangles.new_empty(0, 3), torch.empty(0, dtype=torch.int32, device=dev))
+        stats = dict(zip(COLLAPSE_COUNTS, [0] * 8), planeless_triangles=0, rounds_launched=0, done=True, stalled=False)
+        return out + (stats,) if return_stats else out
+    ws_bytes = int(_lib.lib().mi3d_mesh_collapse_workspace(nv, nt))
+    if ws_bytes == 0:
+        raise Mi3dError(f"{nt} triangles are more than a collapse takes (2^30)")
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    limit = float("inf") if max_error is None else max_error
+    _lib.launch("mi3d_mesh_collapse_begin", vertices, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, _lib.ptr(ws),
+                ws_bytes, _lib.ptr(counts))
+    launched, over = 0, False
+    while launched < max_rounds and not over:
+        n = min(per_read, max_rounds - launched)
+        _lib.launch("mi3d_mesh_collapse_rounds", vertices, nv, nt, target, limit, n, _lib.ptr(ws), ws_bytes,
+                    _lib.ptr(counts))
+        launched += n
+        host = counts.tolist()                                  # one host read per batch of rounds
+        over = host[3] < launched                               # a round was a no-op or found no winner: so is every later one
+    _lib.launch("mi3d_mesh_collapse_count", vertices, nv, nt, _lib.ptr(ws), ws_bytes, _lib.ptr(counts))
+    host = counts.tolist()                                      # the read that sizes the output
+    kv, kt = host[:2]
+    out_v = torch.empty(kv, 3, dtype=torch.float32, device=dev)
+    out_t = torch.empty(kt, 3, dtype=torch.int32, device=dev)
+    vertex_map = torch.empty(nv, dtype=torch.int32, device=dev)
+    _lib.launch("mi3d_mesh_collapse_emit", vertices, nv, nt, _lib.ptr(ws), ws_bytes, _lib.ptr(out_v), kv, _lib.ptr(out_t),
+                kt, _lib.ptr(vertex_map), _lib.ptr(counts))
+    if not return_stats:
+        return out_v, out_t, vertex_map
+    host = counts.tolist()
+    if host[7] != 0:
+        raise Mi3dError(f"mesh collapse: {host[7]} slots could not be placed (the result is invalid: a bug, or the "
+                        f"buffers changed during the call)")
+    stats = dict(zip(COLLAPSE_COUNTS, host))
+    stats["planeless_triangles"], stats["unusable_triangles"] = host[2] >> 32, host[2] & 0xFFFFFFFF
+    stats["rounds_launched"], stats["done"] = launched, kt <= target
+    stats["stalled"] = kt > target and host[3] < launched
+    return out_v, out_t, vertex_map, stats
+
+
+def _check_collapse_option(collapse):
+    """export's `collapse`: None, a face count >= 1, or a dict of COLLAPSE_KEYS -> (target_faces, max_error, max_rounds)."""
+    if collapse is None:
+        return None
+    if isinstance(collapse, dict):
+        unknown = sorted(set(collapse) - set(COLLAPSE_KEYS))
+        if unknown or "target_faces" not in collapse:
+            raise Mi3dError(f"collapse: unknown keys {unknown}; it takes {COLLAPSE_KEYS}, and target_faces is required")
+        checked = _check_collapse(**collapse)[:3]
+    else:
+        checked = _check_collapse(collapse)[:3]
+    if checked[0] < 1:
+        raise Mi3dError(f"collapse: target_faces must be >= 1 (got {checked[0]})")
+    return checked
+
+
+def _collapse_export(vertices, triangles, collapsing):
+    """export's collapse step; the counts are read, so that an inconsistency raises."""
+    target, max_error, max_rounds = collapsing
+    out_v, out_t, _, stats = collapse(vertices, triangles, target, max_error=max_error, max_rounds=max_rounds,
+                                      return_stats=True)
+    if out_v.shape[0] == 0 or out_t.shape[0] == 0:
+        raise Mi3dError(f"export_mesh: nothing survives collapse: {stats['unusable_triangles']} of the "
+                        f"{triangles.shape[0]} triangles are unusable")
+    return out_v, out_t
+
+
 def _chunks(n):
     return ((s, min(s + CHUNK, n)) for s in range(0, n, CHUNK))
 
@@ -1305,9 +1416,11 @@ def vertex_normals(model, vertices):
 
 
 def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False, min_faces=None,
-           min_diagonal=None, largest=False, decimate=None, target_faces=None, views=None, smooth=None, preview=None):
+           min_diagonal=None, largest=False, decimate=None, target_faces=None, views=None, smooth=None, preview=None,
+           collapse=None):
     """What NeRFRenderer.export_mesh does (see there).  `S` only sizes the reference's chunks and is ignored."""
     del S
+    collapsing = _check_collapse_option(collapse)              # before any work
     smoothing = _check_smooth_option(smooth)                    # before any work
     if preview is not None:                                     # before any work
         preview = _check_preview(preview)
@@ -1345,6 +1458,8 @@ def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, norma
                                 f"{counts[4] >> 32} triangles ({nv0} vertices, {nt0} triangles in all)")
         if decimate is not None or target_faces is not None:    # after the floater filter, which sees the original mesh
             vertices, triangles = _decimate(vertices, triangles, R, decimate, target_faces)
+        if collapsing is not None:                              # after the clustering: cluster coarsely, then collapse
+            vertices, triangles = _collapse_export(vertices, triangles, collapsing)
         if smoothing is not None:                               # before the atlas check, the colours, the bakes, the normals
             vertices = _smooth_export(vertices, triangles, smoothing, h)
         if texture_size is not None:

@@ -119,7 +119,7 @@ class NeRFRenderer(nn.Module):
     @torch.no_grad()
     def export_mesh(self, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False, min_faces=None,
                     min_diagonal=None, largest=False, decimate=None, target_faces=None, views=None, smooth=None,
-                    preview=None):
+                    preview=None, collapse=None):
         """renderer.py:157-191 + the file writing of :300-328, reached through main.py's `--save_mesh`: sigma on the
         `resolution`^3 lattice of [-1, 1]^3 (default grid_size), marching cubes at min(mean_density, density_thresh)
         (density_thresh without cuda_ray) on the GPU (mi3d.mesh), `<path>/mesh.obj` + `mesh.mtl`.  By default
@@ -175,11 +175,19 @@ class NeRFRenderer(nn.Module):
         mesh.fidelity's figures for the pair: PSNR over the union and over the intersection of the two masks and the
         masks' IoU, per view and overall (a figure that is not finite is written as null).  The option is checked before
         any work; the return value does not change.  With `preview=None` nothing of this runs and the files are byte
-        for byte what they were without the argument."""
+        for byte what they were without the argument.  `collapse=N` (an integer >= 1) or `collapse=dict(target_faces=,
+        max_error=, max_rounds=)` decimates the mesh to N faces by quadric edge collapse (mesh.collapse, include/mi3d.h
+        Part 19): a closed manifold stays closed and manifold, new vertices go where the planes around them
+        meet, and a closed mesh ends on N or N - 1 faces unless the run stalls above (not an error).  It runs after the
+        floater filter and after `decimate=` / `target_faces=` - both may be given: cluster coarsely, then collapse - and
+        before `smooth=`, the atlas check, the colours, the bakes and the normals, which are all re-evaluated from the
+        field at the new vertices.  `max_error` (None: no limit) bounds the quadric error of a collapse, `max_rounds`
+        (default 256) the rounds.  The option is checked before any work.  With `collapse=None` nothing of this runs and
+        the files are byte for byte what they were without the argument."""
         from . import mesh
         return mesh.export(self, path, resolution, S, texture_size=texture_size, ssaa=ssaa, normals=normals,
                            min_faces=min_faces, min_diagonal=min_diagonal, largest=largest, decimate=decimate,
-                           target_faces=target_faces, views=views, smooth=smooth, preview=preview)
+                           target_faces=target_faces, views=views, smooth=smooth, preview=preview, collapse=collapse)
 
     @torch.no_grad()
     def export_point_cloud(self, outputdir, poses, ref_rgb, fov, H, W, **kwargs):
