@@ -3,8 +3,10 @@
     python make-it-3d_amd/build.py [--force]
 
 No torch, no pybind: the library exposes only the C ABI of include/mi3d.h.
-raymarching.hip is compiled with -ffp-contract=off (its fused multiply-adds are explicit, see
-csrc/mi3d_common.h); the other translation units use the default contraction.
+The units marked in UNITS are compiled with -ffp-contract=off: their fused multiply-adds are explicit (raymarching.hip,
+see csrc/mi3d_common.h) or their results are pinned bit for bit by NumPy restatements that round every operation on its
+own (optim, raster, pointcloud, the mesh and texture units).  hashgrid.hip, field.hip, groupnorm.hip and canny.hip use the
+default contraction.
 """
 import os
 import subprocess
@@ -33,7 +35,7 @@ UNITS = [
     ("pointcloud.hip", ["-ffp-contract=off"]),
     ("canny.hip", []),
 ]
-HEADERS = ["mi3d_common.h", "mi3d_grid.h", "mi3d_grid_plan.h", "mi3d_dev.h", "lds_transpose.h", "mi3d_mc_tables.h", "mi3d_meshraster.h", "mi3d_scan.h", "mi3d_incidence.h", os.path.join("..", "..", "include", "mi3d.h")]
+HEADERS = ["mi3d_common.h", "mi3d_grid.h", "mi3d_grid_plan.h", "mi3d_dev.h", "lds_transpose.h", "mi3d_mc_tables.h", "mi3d_meshraster.h", "mi3d_scan.h", "mi3d_incidence.h", "mi3d_workspace.h", os.path.join("..", "..", "include", "mi3d.h")]
 
 
 def _newer(src, dst):

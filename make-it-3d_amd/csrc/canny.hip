@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mi3d.h"
+#include "mi3d_scan.h"
 
 namespace {
 
@@ -27,7 +28,7 @@ constexpr int kTile = 32, kPerThread = kTile * kTile / kBlock;
 constexpr int kImg = kTile + 4, kMag = kTile + 2;      // tile sides with the 2- and the 1-pixel halo
 constexpr unsigned long long kMaxPixels = 0x7FFFFFFFull;
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+using mi3d_scan::as_stream;
 
 __host__ __device__ inline uint32_t tiles_of(uint32_t n) { return (n + kTile - 1) / kTile; }
 

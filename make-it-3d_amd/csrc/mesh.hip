@@ -41,28 +41,11 @@ struct McDims {
     uint32_t Rx, Ry, Rz, n;  // n = Rx Ry Rz <= 2^30
 };
 
-// workspace: [block triangle sums / offsets: u64 x nb][block vertex sums / offsets: u32 x nb (padded to 8 bytes)]
-//            [first vertex id per grid point: u32 x n]
-struct McWorkspace {
-    unsigned long long *block_t;
-    uint32_t *block_v, *first_id;
-};
+// workspace: mc_layout of mi3d_workspace.h, the one statement of its arrays and its size
+using namespace mi3d_workspace;
+static_assert(kBlock == kLayoutBlock, "mc_layout sizes its rows of block sums by this workgroup");
 
 __host__ __device__ inline uint32_t mc_blocks(uint32_t n) { return (n + kBlock - 1) / kBlock; }
-
-inline size_t mc_workspace_bytes(uint32_t n) {
-    const size_t nb = mc_blocks(n);
-    return nb * 8 + ((nb + 1) / 2) * 8 + (size_t)n * 4;
-}
-
-inline McWorkspace mc_carve(void *ws, uint32_t n) {
-    const size_t nb = mc_blocks(n);
-    McWorkspace w;
-    w.block_t = reinterpret_cast<unsigned long long *>(ws);
-    w.block_v = reinterpret_cast<uint32_t *>(w.block_t + nb);
-    w.first_id = w.block_v + ((nb + 1) / 2) * 2;
-    return w;
-}
 
 __device__ __forceinline__ bool inside(float v, float iso) { return v >= iso; }  // NaN: outside
 
@@ -214,9 +197,7 @@ bool mc_dims(uint32_t Rx, uint32_t Ry, uint32_t Rz, McDims &d) {
 
 bool mc_args(const void *vol, uint32_t Rx, uint32_t Ry, uint32_t Rz, const void *ws, size_t ws_bytes, const void *counts,
              McDims &d) {
-    if (!mc_dims(Rx, Ry, Rz, d) || vol == nullptr || ws == nullptr || counts == nullptr) return false;
-    if (!aligned8(ws) || !aligned8(counts)) return false;
-    return ws_bytes >= mc_workspace_bytes(d.n);
+    return mc_dims(Rx, Ry, Rz, d) && vol != nullptr && state_ok(ws, ws_bytes, bytes_of(mc_layout, d.n), counts);
 }
 
 }  // namespace
@@ -225,7 +206,7 @@ extern "C" {
 
 size_t mi3d_mc_workspace(uint32_t Rx, uint32_t Ry, uint32_t Rz) {
     McDims d;
-    return mc_dims(Rx, Ry, Rz, d) ? mc_workspace_bytes(d.n) : 0;
+    return mc_dims(Rx, Ry, Rz, d) ? bytes_of(mc_layout, d.n) : 0;
 }
 
 int mi3d_mc_case(uint32_t case_index, int8_t *edges_host) {
@@ -238,7 +219,7 @@ int mi3d_mc_count(const float *vol, uint32_t Rx, uint32_t Ry, uint32_t Rz, float
                   unsigned long long *counts, void *stream) {
     McDims d;
     if (!mc_args(vol, Rx, Ry, Rz, ws, ws_bytes, counts, d) || iso != iso) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_mc_count, dim3(mc_blocks(d.n)), dim3(kBlock), 0, as_stream(stream), vol, d, iso, mc_carve(ws, d.n));
+    hipLaunchKernelGGL(k_mc_count, dim3(mc_blocks(d.n)), dim3(kBlock), 0, as_stream(stream), vol, d, iso, at(ws, mc_layout, d.n));
     return (int)hipGetLastError();
 }
 
@@ -246,7 +227,7 @@ int mi3d_mc_scan(uint32_t Rx, uint32_t Ry, uint32_t Rz, void *ws, size_t ws_byte
                  void *stream) {
     McDims d;
     if (!mc_args(ws /* no volume here */, Rx, Ry, Rz, ws, ws_bytes, counts, d)) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(kRowThreads), 0, as_stream(stream), mc_carve(ws, d.n), mc_blocks(d.n),
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(kRowThreads), 0, as_stream(stream), at(ws, mc_layout, d.n), mc_blocks(d.n),
                        counts);
     return (int)hipGetLastError();
 }
@@ -260,7 +241,7 @@ int mi3d_mc_emit(const float *vol, uint32_t Rx, uint32_t Ry, uint32_t Rz, float 
         return (int)hipErrorInvalidValue;
     const McFrame f = {origin_host[0], origin_host[1], origin_host[2], spacing_host[0], spacing_host[1], spacing_host[2]};
     const uint32_t vcap = nv_cap > 0x7FFFFFFFull ? 0x7FFFFFFFu : (uint32_t)nv_cap;  // ids are int32 in `triangles`
-    const McWorkspace w = mc_carve(ws, d.n);
+    const McWorkspace w = at(ws, mc_layout, d.n);
     const hipStream_t st = as_stream(stream);
     hipLaunchKernelGGL(k_mc_vertices, dim3(mc_blocks(d.n)), dim3(kBlock), 0, st, vol, d, iso, f, w, vertices, vcap, counts);
     hipLaunchKernelGGL(k_mc_triangles, dim3(mc_blocks(d.n)), dim3(kBlock), 0, st, vol, d, iso, w, triangles, nt_cap,

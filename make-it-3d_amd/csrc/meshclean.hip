@@ -57,27 +57,9 @@ constexpr unsigned long long kMaxCount = 0x7FFFFFFFull;  // nv, nt <= 2^31 - 1: 
 // place, 7 unused (0)
 enum { kKeptV = 0, kKeptT = 1, kBad = 2, kGaveUp = 3, kLargest = 4, kComponents = 5, kLost = 6 };
 
-// workspace: [kept vertices per workgroup / offsets: u32 x nbv (padded to 8 bytes)][the same for triangles: u32 x nbt]
-//            [keep flag per vertex, meaningful at label rows: u8 x nv]
-struct CleanWorkspace {
-    uint32_t *block_v, *block_t;
-    uint8_t *flag;
-};
-
-inline size_t clean_workspace_bytes(uint32_t nv, uint32_t nt) {
-    return pad8((size_t)blocks_of(nv, kBlock) * 4) + pad8((size_t)blocks_of(nt, kBlock) * 4) + pad8(nv);
-}
-
-inline CleanWorkspace clean_carve(void *ws, uint32_t nv, uint32_t nt) {
-    char *p = reinterpret_cast<char *>(ws);
-    CleanWorkspace w;
-    w.block_v = reinterpret_cast<uint32_t *>(p);
-    p += pad8((size_t)blocks_of(nv, kBlock) * 4);
-    w.block_t = reinterpret_cast<uint32_t *>(p);
-    p += pad8((size_t)blocks_of(nt, kBlock) * 4);
-    w.flag = reinterpret_cast<uint8_t *>(p);
-    return w;
-}
+// workspace: clean_layout of mi3d_workspace.h, the one statement of its arrays and its size
+using namespace mi3d_workspace;
+static_assert(kBlock == kLayoutBlock, "clean_layout sizes its rows of block sums by this workgroup");
 
 // the order-preserving integer image of a binary32: a < b as floats <=> key(a) < key(b) as unsigned (-0 below +0).
 // NaNs are never inserted, so 0xFFFFFFFF / 0 are free to mean "no minimum / no maximum yet".
@@ -458,20 +440,18 @@ __global__ __launch_bounds__(kBlock) void k_cl_emit_t(const int32_t *__restrict_
     o[2] = vertex_map[c];
 }
 
-bool sizes_ok(unsigned long long nv, unsigned long long nt) { return nv <= kMaxCount && nt <= kMaxCount; }
-
 }  // namespace
 
 extern "C" {
 
 size_t mi3d_mesh_components_workspace(unsigned long long nv, unsigned long long nt) {
-    return sizes_ok(nv, nt) ? clean_workspace_bytes((uint32_t)nv, (uint32_t)nt) : 0;
+    return sizes_ok(nv, nt, kMaxCount, kMaxCount) ? bytes_of(clean_layout, (uint32_t)nv, (uint32_t)nt) : 0;
 }
 
 int mi3d_mesh_components(const float *vertices, unsigned long long nv, const int32_t *triangles, unsigned long long nt,
                          int32_t *label, uint32_t *faces, float *box_min, float *box_max, unsigned long long *counts,
                          void *stream) {
-    if (!sizes_ok(nv, nt)) return (int)hipErrorInvalidValue;
+    if (!sizes_ok(nv, nt, kMaxCount, kMaxCount)) return (int)hipErrorInvalidValue;
     if (nv == 0 && nt == 0) return (int)hipSuccess;
     if (counts == nullptr || !aligned8(counts) || (nt > 0 && triangles == nullptr) ||
         (nv > 0 && (vertices == nullptr || label == nullptr || faces == nullptr || box_min == nullptr || box_max == nullptr)))
@@ -500,16 +480,16 @@ int mi3d_mesh_clean_count(const int32_t *triangles, unsigned long long nv, unsig
                           const uint32_t *faces, const float *box_min, const float *box_max, uint32_t min_faces,
                           float min_diagonal, int largest, void *ws, size_t ws_bytes, unsigned long long *counts,
                           void *stream) {
-    if (!sizes_ok(nv, nt) || !(min_diagonal >= 0.f)) return (int)hipErrorInvalidValue;
+    if (!sizes_ok(nv, nt, kMaxCount, kMaxCount) || !(min_diagonal >= 0.f)) return (int)hipErrorInvalidValue;
     if (nv == 0 && nt == 0) return (int)hipSuccess;
-    if (counts == nullptr || !aligned8(counts) || ws == nullptr || !aligned8(ws) ||
-        ws_bytes < clean_workspace_bytes((uint32_t)nv, (uint32_t)nt) || (nt > 0 && triangles == nullptr) ||
+    if (!state_ok(ws, ws_bytes, bytes_of(clean_layout, (uint32_t)nv, (uint32_t)nt), counts) ||
+        (nt > 0 && triangles == nullptr) ||
         (nv > 0 && (label == nullptr || faces == nullptr || box_min == nullptr || box_max == nullptr)))
         return (int)hipErrorInvalidValue;
     const uint32_t n = (uint32_t)nv, m = (uint32_t)nt;
     const uint32_t nbv = blocks_of(n, kBlock), nbt = blocks_of(m, kBlock);
     const hipStream_t st = as_stream(stream);
-    const CleanWorkspace w = clean_carve(ws, n, m);
+    const CleanWorkspace w = at(ws, clean_layout, n, m);
     const KeepRule rule = {min_faces, min_diagonal * min_diagonal, largest != 0};
     if (n) {
         hipLaunchKernelGGL(k_cl_flags, dim3(nbv), dim3(kBlock), 0, st, n, label, faces, box_min, box_max, rule,
@@ -526,19 +506,18 @@ int mi3d_mesh_clean_emit(const float *vertices, unsigned long long nv, const int
                          const int32_t *label, void *ws, size_t ws_bytes, unsigned long long *counts, float *out_vertices,
                          unsigned long long nv_cap, int32_t *out_triangles, unsigned long long nt_cap, int32_t *vertex_map,
                          void *stream) {
-    if (!sizes_ok(nv, nt)) return (int)hipErrorInvalidValue;
+    if (!sizes_ok(nv, nt, kMaxCount, kMaxCount)) return (int)hipErrorInvalidValue;
     if (nv == 0) return (int)hipSuccess;  // nothing to map, and no triangle is valid
-    if (counts == nullptr || !aligned8(counts) || ws == nullptr || !aligned8(ws) ||
-        ws_bytes < clean_workspace_bytes((uint32_t)nv, (uint32_t)nt) || vertices == nullptr || label == nullptr ||
-        vertex_map == nullptr || (nt > 0 && triangles == nullptr) || (nv_cap > 0 && out_vertices == nullptr) ||
-        (nt_cap > 0 && out_triangles == nullptr))
+    if (!state_ok(ws, ws_bytes, bytes_of(clean_layout, (uint32_t)nv, (uint32_t)nt), counts) || vertices == nullptr ||
+        label == nullptr || vertex_map == nullptr || (nt > 0 && triangles == nullptr) ||
+        (nv_cap > 0 && out_vertices == nullptr) || (nt_cap > 0 && out_triangles == nullptr))
         return (int)hipErrorInvalidValue;
     const uint32_t n = (uint32_t)nv, m = (uint32_t)nt;
     const uint32_t nbv = blocks_of(n, kBlock), nbt = blocks_of(m, kBlock);
     const uint32_t vcap = nv_cap > kMaxCount ? (uint32_t)kMaxCount : (uint32_t)nv_cap;
     const uint32_t tcap = nt_cap > kMaxCount ? (uint32_t)kMaxCount : (uint32_t)nt_cap;
     const hipStream_t st = as_stream(stream);
-    const CleanWorkspace w = clean_carve(ws, n, m);
+    const CleanWorkspace w = at(ws, clean_layout, n, m);
     hipLaunchKernelGGL(k_cl_emit_v, dim3(nbv), dim3(kBlock), 0, st, vertices, n, label, w, out_vertices, vcap,
                        vertex_map, counts);
     if (m) hipLaunchKernelGGL(k_cl_emit_t, dim3(nbt), dim3(kBlock), 0, st, triangles, m, n, label, w, vertex_map,

@@ -55,65 +55,15 @@ constexpr unsigned long long kNone = ~0ull;                 // a claim nobody ma
 // counts (device uint64[8]): see Part 19
 enum { kVertices = 0, kTriangles = 1, kUnusable = 2, kRounds = 3, kNonFinite = 4, kCollapses = 5, kLocked = 6, kErrors = 7 };
 
-// what the rounds keep between kernels, in the workspace
-struct Ctrl {
-    uint32_t live;          // live triangles at the start of the round
-    uint32_t live_next;     // summed by k_co_rename
-    uint32_t active;        // this round runs
-    uint32_t quota;         // winners applied at most
-    uint32_t round;         // r of the key's hash: the rounds run before this one
-    uint32_t winners;       // of this round
-    uint32_t last_winners;  // of the last round that ran (1 before the first)
-    uint32_t planeless;     // usable triangles with s == 0 or a non-finite s
-    uint32_t pad[8];
-};
+// workspace: collapse_layout of mi3d_workspace.h, the one statement of its arrays and its size; Ctrl, its first 64 bytes,
+// is what the rounds keep between kernels
+using Ctrl = mi3d_workspace::CollapseCtrl;
+using Ws = mi3d_workspace::CollapseWorkspace;
+using namespace mi3d_workspace;
+static_assert(kBlock == kLayoutBlock, "collapse_layout sizes its rows of block sums by this workgroup");
 
-struct Ws {
-    Ctrl *ctrl;
-    double *Q;                   // [nv][10]
-    unsigned long long *claim;   // [nv]
-    unsigned long long *keys;    // [3 nt]
-    float *P;                    // [nv][3]
-    int32_t *rep, *cur;          // [nv]
-    uint32_t *offs, *blockv;     // [nv + 1], [blocks of nv]
-    int32_t *tri;                // [nt][3]: the corners as renamed so far
-    uint32_t *rows;              // [3 nt]: 3 t + k for every live triangle t with v at corner k
-    float *xstar;                // [3 nt][3]
-    uint32_t *blockt;            // [blocks of nt]
-    uint8_t *locked, *alive, *wins;
-};
-
-inline size_t ws_bytes_of(uint32_t nv, uint32_t nt) {
-    return sizeof(Ctrl) + (size_t)nv * 80 + (size_t)nv * 8 + (size_t)nt * 24 + pad8((size_t)nv * 12) + 2 * pad8((size_t)nv * 4) +
-           pad8(((size_t)nv + 1) * 4) + pad8((size_t)blocks_of(nv, kBlock) * 4) + 2 * pad8((size_t)nt * 12) +
-           pad8((size_t)nt * 36) + pad8((size_t)blocks_of(nt, kBlock) * 4) + pad8(nv) + 2 * pad8(nt);
-}
-
-inline Ws carve(void *ws, uint32_t nv, uint32_t nt) {
-    char *p = reinterpret_cast<char *>(ws);
-    Ws w;
-    auto take = [&p](size_t bytes) {
-        char *q = p;
-        p += bytes;
-        return q;
-    };
-    w.ctrl = reinterpret_cast<Ctrl *>(take(sizeof(Ctrl)));
-    w.Q = reinterpret_cast<double *>(take((size_t)nv * 80));
-    w.claim = reinterpret_cast<unsigned long long *>(take((size_t)nv * 8));
-    w.keys = reinterpret_cast<unsigned long long *>(take((size_t)nt * 24));
-    w.P = reinterpret_cast<float *>(take(pad8((size_t)nv * 12)));
-    w.rep = reinterpret_cast<int32_t *>(take(pad8((size_t)nv * 4)));
-    w.cur = reinterpret_cast<int32_t *>(take(pad8((size_t)nv * 4)));
-    w.offs = reinterpret_cast<uint32_t *>(take(pad8(((size_t)nv + 1) * 4)));
-    w.blockv = reinterpret_cast<uint32_t *>(take(pad8((size_t)blocks_of(nv, kBlock) * 4)));
-    w.tri = reinterpret_cast<int32_t *>(take(pad8((size_t)nt * 12)));
-    w.rows = reinterpret_cast<uint32_t *>(take(pad8((size_t)nt * 12)));
-    w.xstar = reinterpret_cast<float *>(take(pad8((size_t)nt * 36)));
-    w.blockt = reinterpret_cast<uint32_t *>(take(pad8((size_t)blocks_of(nt, kBlock) * 4)));
-    w.locked = reinterpret_cast<uint8_t *>(take(pad8(nv)));
-    w.alive = reinterpret_cast<uint8_t *>(take(pad8(nt)));
-    w.wins = reinterpret_cast<uint8_t *>(take(pad8(nt)));
-    return w;
+inline size_t ws_bytes_of(unsigned long long nv, unsigned long long nt) {
+    return bytes_of(collapse_layout, (uint32_t)nv, (uint32_t)nt);
 }
 
 // ------------------------------------------------------------------------------------------------ binary64 geometry
@@ -218,8 +168,7 @@ __global__ __launch_bounds__(kBlock) void k_co_vertices(const float *__restrict_
     wave_count(in && !finite, &counts[kNonFinite]);
 }
 
-// usable as in Part 16: indices in range, pairwise distinct, three finite vertices; nothing dereferenced before the
-// index check
+// usable as in Part 16 (mi3d_incidence.h)
 __global__ __launch_bounds__(kBlock) void k_co_usable(const float *__restrict__ vertices, uint32_t nv,
                                                       const int32_t *__restrict__ tri, uint32_t nt, Ws w) {
     __shared__ uint32_t wave_sum[kWaves];
@@ -227,12 +176,7 @@ __global__ __launch_bounds__(kBlock) void k_co_usable(const float *__restrict__ 
     bool ok = false, planeless = false;
     if (t < nt) {
         int32_t c[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) c[k] = tri[(size_t)t * 3 + k];
-        ok = in_range(c[0], nv) && in_range(c[1], nv) && in_range(c[2], nv) && c[0] != c[1] && c[1] != c[2] && c[0] != c[2];
-        if (ok)
-            ok = finite3(vertices + (size_t)c[0] * 3) && finite3(vertices + (size_t)c[1] * 3) &&
-                 finite3(vertices + (size_t)c[2] * 3);
+        ok = mi3d_incidence::usable(vertices, nv, tri, t, c);
         if (ok) {
             double K[10];
             planeless = !plane_quadric(widen(vertices + (size_t)c[0] * 3), widen(vertices + (size_t)c[1] * 3),
@@ -285,13 +229,9 @@ __global__ __launch_bounds__(kBlock) void k_co_fill(uint32_t nt, Ws w, int alway
     uint32_t lost = 0;
     if (t < nt && w.alive[t]) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const uint32_t v = (uint32_t)w.tri[(size_t)t * 3 + k];
-            const uint32_t begin = w.offs[v], len = w.offs[v + 1] - begin;
-            const uint32_t slot = (uint32_t)atomicAdd(w.cur + v, 1);
-            if (slot < len) w.rows[(size_t)begin + slot] = 3u * t + (uint32_t)k;
-            else ++lost;  // the state changed since the degrees were counted: counted, nothing stored
-        }
+        for (int k = 0; k < 3; ++k)  // lost: the state changed since the degrees were counted
+            lost += mi3d_incidence::fill(w.cur, w.offs, (uint32_t)w.tri[(size_t)t * 3 + k],
+                                         [&](size_t i) { w.rows[i] = 3u * t + (uint32_t)k; });
     }
     if (lost != 0) atomicAdd(&counts[kErrors], (unsigned long long)lost);  // never
 }
@@ -651,14 +591,6 @@ __global__ __launch_bounds__(kBlock) void k_co_emit_triangles(uint32_t nt, Ws w,
     wave_count(lost, &counts[kErrors]);
 }
 
-bool sizes_ok(unsigned long long nv, unsigned long long nt) { return nv <= kMaxVertices && nt <= kMaxTriangles; }
-
-// what every entry point asks of the sizes, the workspace and counts
-bool state_ok(unsigned long long nv, unsigned long long nt, const void *ws, size_t ws_bytes, const void *counts) {
-    return sizes_ok(nv, nt) && ws != nullptr && aligned8(ws) && ws_bytes >= ws_bytes_of((uint32_t)nv, (uint32_t)nt) &&
-           counts != nullptr && aligned8(counts);
-}
-
 void launch_incidence(const Ws &w, uint32_t n, uint32_t m, int always, unsigned long long *counts, hipStream_t st) {
     const uint32_t nb = blocks_of(n, kBlock), nbt = blocks_of(m, kBlock);
     hipLaunchKernelGGL(k_co_block_sums, dim3(nb), dim3(kBlock), 0, st, n, w, always);
@@ -672,19 +604,19 @@ void launch_incidence(const Ws &w, uint32_t n, uint32_t m, int always, unsigned 
 extern "C" {
 
 size_t mi3d_mesh_collapse_workspace(unsigned long long nv, unsigned long long nt) {
-    if (!sizes_ok(nv, nt) || (nv == 0 && nt == 0)) return 0;
-    return ws_bytes_of((uint32_t)nv, (uint32_t)nt);
+    if (!sizes_ok(nv, nt, kMaxVertices, kMaxTriangles) || (nv == 0 && nt == 0)) return 0;
+    return ws_bytes_of(nv, nt);
 }
 
 int mi3d_mesh_collapse_begin(const float *vertices, unsigned long long nv, const int32_t *triangles, unsigned long long nt,
                              void *ws, size_t ws_bytes, unsigned long long *counts, void *stream) {
-    if (!sizes_ok(nv, nt)) return (int)hipErrorInvalidValue;
+    if (!sizes_ok(nv, nt, kMaxVertices, kMaxTriangles)) return (int)hipErrorInvalidValue;
     if (nv == 0 && nt == 0) return (int)hipSuccess;
-    if (!state_ok(nv, nt, ws, ws_bytes, counts) || (nv > 0 && vertices == nullptr) || (nt > 0 && triangles == nullptr))
+    if (!state_ok(ws, ws_bytes, ws_bytes_of(nv, nt), counts) || (nv > 0 && vertices == nullptr) || (nt > 0 && triangles == nullptr))
         return (int)hipErrorInvalidValue;
     const uint32_t n = (uint32_t)nv, m = (uint32_t)nt, nb = blocks_of(n, kBlock), nbt = blocks_of(m, kBlock);
     const hipStream_t st = as_stream(stream);
-    const Ws w = carve(ws, n, m);
+    const Ws w = at(ws, collapse_layout, n, m);
     hipLaunchKernelGGL(k_co_zero, dim3(1), dim3(64), 0, st, w, counts);
     if (n) hipLaunchKernelGGL(k_co_vertices, dim3(nb), dim3(kBlock), 0, st, vertices, n, w, counts);
     if (m) hipLaunchKernelGGL(k_co_usable, dim3(nbt), dim3(kBlock), 0, st, vertices, n, triangles, m, w);
@@ -699,13 +631,13 @@ int mi3d_mesh_collapse_begin(const float *vertices, unsigned long long nv, const
 int mi3d_mesh_collapse_rounds(unsigned long long nv, unsigned long long nt, unsigned long long target_faces,
                               float max_error, uint32_t n_rounds, void *ws, size_t ws_bytes, unsigned long long *counts,
                               void *stream) {
-    if (!sizes_ok(nv, nt) || !(max_error >= 0.f) || n_rounds > kMaxRounds) return (int)hipErrorInvalidValue;
+    if (!sizes_ok(nv, nt, kMaxVertices, kMaxTriangles) || !(max_error >= 0.f) || n_rounds > kMaxRounds) return (int)hipErrorInvalidValue;
     if (nv == 0 && nt == 0) return (int)hipSuccess;
-    if (!state_ok(nv, nt, ws, ws_bytes, counts)) return (int)hipErrorInvalidValue;
+    if (!state_ok(ws, ws_bytes, ws_bytes_of(nv, nt), counts)) return (int)hipErrorInvalidValue;
     if (nv == 0 || nt == 0) return (int)hipSuccess;  // no live triangle: every round is a no-op
     const uint32_t n = (uint32_t)nv, m = (uint32_t)nt, nb = blocks_of(n, kBlock), nbt = blocks_of(m, kBlock);
     const hipStream_t st = as_stream(stream);
-    const Ws w = carve(ws, n, m);
+    const Ws w = at(ws, collapse_layout, n, m);
     for (uint32_t r = 0; r < n_rounds; ++r) {
         hipLaunchKernelGGL(k_co_round_begin, dim3(1), dim3(64), 0, st, w, target_faces, counts);
         hipLaunchKernelGGL(k_co_clear, dim3(nb), dim3(kBlock), 0, st, n, w, 0);
@@ -724,13 +656,13 @@ int mi3d_mesh_collapse_rounds(unsigned long long nv, unsigned long long nt, unsi
 
 int mi3d_mesh_collapse_count(unsigned long long nv, unsigned long long nt, void *ws, size_t ws_bytes,
                              unsigned long long *counts, void *stream) {
-    if (!sizes_ok(nv, nt)) return (int)hipErrorInvalidValue;
+    if (!sizes_ok(nv, nt, kMaxVertices, kMaxTriangles)) return (int)hipErrorInvalidValue;
     if (nv == 0 && nt == 0) return (int)hipSuccess;
-    if (!state_ok(nv, nt, ws, ws_bytes, counts)) return (int)hipErrorInvalidValue;
+    if (!state_ok(ws, ws_bytes, ws_bytes_of(nv, nt), counts)) return (int)hipErrorInvalidValue;
     if (nv == 0 || nt == 0) return (int)hipSuccess;  // counts[0] and [1] are the zeros of begin
     const uint32_t n = (uint32_t)nv, m = (uint32_t)nt, nb = blocks_of(n, kBlock), nbt = blocks_of(m, kBlock);
     const hipStream_t st = as_stream(stream);
-    const Ws w = carve(ws, n, m);
+    const Ws w = at(ws, collapse_layout, n, m);
     hipLaunchKernelGGL(k_co_clear, dim3(nb), dim3(kBlock), 0, st, n, w, 1);
     hipLaunchKernelGGL(k_co_cite, dim3(nbt), dim3(kBlock), 0, st, m, w);
     hipLaunchKernelGGL(k_co_block_sums, dim3(nb), dim3(kBlock), 0, st, n, w, 1);
@@ -743,14 +675,14 @@ int mi3d_mesh_collapse_count(unsigned long long nv, unsigned long long nt, void 
 int mi3d_mesh_collapse_emit(unsigned long long nv, unsigned long long nt, void *ws, size_t ws_bytes, float *out_vertices,
                             unsigned long long nv_cap, int32_t *out_triangles, unsigned long long nt_cap,
                             int32_t *vertex_map, unsigned long long *counts, void *stream) {
-    if (!sizes_ok(nv, nt)) return (int)hipErrorInvalidValue;
+    if (!sizes_ok(nv, nt, kMaxVertices, kMaxTriangles)) return (int)hipErrorInvalidValue;
     if (nv == 0 && nt == 0) return (int)hipSuccess;
-    if (!state_ok(nv, nt, ws, ws_bytes, counts) || (nv > 0 && vertex_map == nullptr) ||
+    if (!state_ok(ws, ws_bytes, ws_bytes_of(nv, nt), counts) || (nv > 0 && vertex_map == nullptr) ||
         (nv_cap > 0 && out_vertices == nullptr) || (nt_cap > 0 && out_triangles == nullptr))
         return (int)hipErrorInvalidValue;
     const uint32_t n = (uint32_t)nv, m = (uint32_t)nt, nb = blocks_of(n, kBlock), nbt = blocks_of(m, kBlock);
     const hipStream_t st = as_stream(stream);
-    const Ws w = carve(ws, n, m);
+    const Ws w = at(ws, collapse_layout, n, m);
     if (n && m) {
         hipLaunchKernelGGL(k_co_emit_vertices, dim3(nb), dim3(kBlock), 0, st, n, w, out_vertices, nv_cap, vertex_map, counts);
         hipLaunchKernelGGL(k_co_emit_triangles, dim3(nbt), dim3(kBlock), 0, st, m, w, out_triangles, nt_cap, counts);

@@ -32,6 +32,7 @@
 #include "../../include/mi3d.h"
 #include "mi3d_dev.h"
 #include "mi3d_meshraster.h"
+#include "mi3d_scan.h"
 
 namespace {
 
@@ -41,7 +42,8 @@ constexpr unsigned long long kEmpty = ~0ull;
 
 using namespace mi3d_meshraster;
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+using mi3d_scan::as_stream;
+using mi3d_scan::aligned8;
 
 __global__ __launch_bounds__(kBlock) void k_vis_fill(unsigned long long *__restrict__ vis, size_t n,
                                                      unsigned long long *__restrict__ counts) {
@@ -283,7 +285,7 @@ int shade(const float *vertices, unsigned long long nv, const int32_t *triangles
           const Texel *texture, uint32_t T, const float *vn, const float *background, float *image, float *normal,
           float *depth, int32_t *tri, float *bary, uint8_t *alpha, void *stream) {
     const bool by_vertex = colors != nullptr, textured = vt != nullptr || texture != nullptr;
-    if (!views_ok(V, H, W) || views == nullptr || vis == nullptr || (reinterpret_cast<uintptr_t>(vis) & 7u) != 0 ||
+    if (!views_ok(V, H, W) || views == nullptr || vis == nullptr || !aligned8(vis) ||
         background == nullptr || image == nullptr || !mesh_ok(vertices, nv, triangles, nt) || by_vertex == textured ||
         (textured && (vt == nullptr || texture == nullptr || T < kMinT || T > kMaxT)) || (normal != nullptr && vn == nullptr))
         return (int)hipErrorInvalidValue;
@@ -308,9 +310,8 @@ extern "C" {
 int mi3d_mesh_visibility(const float *vertices, unsigned long long nv, const int32_t *triangles, unsigned long long nt,
                          const float *views, uint32_t V, uint32_t H, uint32_t W, unsigned long long *vis,
                          unsigned long long *counts, void *stream) {
-    if (!views_ok(V, H, W) || views == nullptr || vis == nullptr || counts == nullptr ||
-        (reinterpret_cast<uintptr_t>(counts) & 7u) != 0 || (reinterpret_cast<uintptr_t>(vis) & 7u) != 0 ||
-        !mesh_ok(vertices, nv, triangles, nt))
+    if (!views_ok(V, H, W) || views == nullptr || vis == nullptr || counts == nullptr || !aligned8(counts) ||
+        !aligned8(vis) || !mesh_ok(vertices, nv, triangles, nt))
         return (int)hipErrorInvalidValue;
     const hipStream_t st = as_stream(stream);
     const size_t n = (size_t)V * H * W;
@@ -349,10 +350,10 @@ int mi3d_mesh_shade_backward(const float *vertices, unsigned long long nv, const
                              const float *dimage, const float *vt, uint32_t T, float *grad_colors, float *grad_texture,
                              void *ws, size_t ws_bytes, void *stream) {
     const bool by_vertex = grad_colors != nullptr, textured = grad_texture != nullptr;
-    if (!views_ok(V, H, W) || views == nullptr || vis == nullptr || (reinterpret_cast<uintptr_t>(vis) & 7u) != 0 ||
+    if (!views_ok(V, H, W) || views == nullptr || vis == nullptr || !aligned8(vis) ||
         dimage == nullptr || !mesh_ok(vertices, nv, triangles, nt) || by_vertex == textured || (vt != nullptr) != (T != 0) ||
         (textured && (vt == nullptr || T < kMinT || T > kMaxT)) || (by_vertex && vt != nullptr) || ws == nullptr ||
-        (reinterpret_cast<uintptr_t>(ws) & 7u) != 0)
+        !aligned8(ws))
         return (int)hipErrorInvalidValue;
     const size_t count = textured ? (size_t)T * T * 3 : (size_t)nv * 3;
     if (ws_bytes < mi3d_mesh_shade_backward_workspace(count)) return (int)hipErrorInvalidValue;

@@ -51,7 +51,6 @@ using namespace mi3d_scan;
 
 constexpr int kBlock = 256, kWaves = kBlock / 64;
 constexpr unsigned long long kMaxCount = 0x7FFFFFFFull;  // nv, nt <= 2^31 - 1: indices are int32
-constexpr unsigned long long kMaxCapacity = 1ull << 31;  // slots are int32 too
 constexpr uint32_t kInitBlocks = 2048;
 
 // counts (device uint64[8]): 0 emitted vertices, 1 surviving triangles, 2 triangles with an index outside [0, nv) or a
@@ -64,75 +63,14 @@ struct Lattice {
     float cell;
 };
 
-// workspace: [cluster table: i32 x cap_v][duplicate table: i32 x cap_t]           <- filled with -1
-//            [S and n per vertex: i64 x 4 nv][reference mark per vertex: u8 x nv]  <- zeroed
-//            [lead: i32 x nv][tslot: i32 x nt][emitted vertices per workgroup / offsets: u32 x nbv][the same for
-//            triangles: u32 x nbt][clusters per workgroup: u32 x nbv][degenerate, duplicate triangles per workgroup:
-//            u32 x nbt each]; every array padded to 8 bytes
-struct SimplifyWorkspace {
-    int32_t *table_v, *table_t;
-    unsigned long long *acc;
-    uint8_t *ref;
-    int32_t *lead, *tslot;
-    uint32_t *block_v, *block_t;
-    uint32_t *clusters_v, *degenerate_t, *duplicate_t;
-    uint32_t cap_v, cap_t;          // powers of two, at most 2^31
-    unsigned long long fill_words;  // 8-byte words of the -1 region
-    unsigned long long zero_words;  // 8-byte words of the zeroed region behind it
-};
-
-// the smallest power of two above n, shifted by `shift`, at most 2^31
-inline unsigned long long capacity_of(unsigned long long n, int shift) {
-    unsigned long long p = 1;
-    while (p <= n) p <<= 1;
-    p <<= shift;
-    return p > kMaxCapacity ? kMaxCapacity : p;
-}
-
-inline size_t table_bytes(uint32_t nv, uint32_t nt, int shift) {
-    return pad8((size_t)capacity_of(nv, shift) * 4) + pad8((size_t)capacity_of(nt, shift) * 4);
-}
-
-inline size_t fixed_bytes(uint32_t nv, uint32_t nt) {
-    return pad8((size_t)nv * 32) + pad8(nv) + pad8((size_t)nv * 4) + pad8((size_t)nt * 4) +
-           2 * pad8((size_t)blocks_of(nv, kBlock) * 4) + 3 * pad8((size_t)blocks_of(nt, kBlock) * 4);
-}
-
-inline size_t simplify_workspace_bytes(uint32_t nv, uint32_t nt, int tight) {
-    return table_bytes(nv, nt, tight ? 0 : 1) + fixed_bytes(nv, nt);
-}
+// workspace: simplify_layout of mi3d_workspace.h, the one statement of its arrays, of the region k_sp_init fills with -1
+// and the one it zeroes behind it, and of its size for either table capacity
+using namespace mi3d_workspace;
+static_assert(kBlock == kLayoutBlock, "simplify_layout sizes its rows of block sums by this workgroup");
 
 // the capacities are the largest the caller's bytes hold: recommended (shift 1) or tight (shift 0)
 inline SimplifyWorkspace simplify_carve(void *ws, size_t ws_bytes, uint32_t nv, uint32_t nt) {
-    const int shift = ws_bytes >= simplify_workspace_bytes(nv, nt, 0 /* recommended */) ? 1 : 0;
-    char *p = reinterpret_cast<char *>(ws);
-    SimplifyWorkspace w;
-    w.cap_v = (uint32_t)capacity_of(nv, shift);
-    w.cap_t = (uint32_t)capacity_of(nt, shift);
-    w.table_v = reinterpret_cast<int32_t *>(p);
-    p += pad8((size_t)w.cap_v * 4);
-    w.table_t = reinterpret_cast<int32_t *>(p);
-    p += pad8((size_t)w.cap_t * 4);
-    w.fill_words = (unsigned long long)(p - reinterpret_cast<char *>(ws)) / 8;
-    w.acc = reinterpret_cast<unsigned long long *>(p);
-    p += pad8((size_t)nv * 32);
-    w.ref = reinterpret_cast<uint8_t *>(p);
-    p += pad8(nv);
-    w.zero_words = (unsigned long long)(p - reinterpret_cast<char *>(ws)) / 8 - w.fill_words;
-    w.lead = reinterpret_cast<int32_t *>(p);
-    p += pad8((size_t)nv * 4);
-    w.tslot = reinterpret_cast<int32_t *>(p);
-    p += pad8((size_t)nt * 4);
-    w.block_v = reinterpret_cast<uint32_t *>(p);
-    p += pad8((size_t)blocks_of(nv, kBlock) * 4);
-    w.block_t = reinterpret_cast<uint32_t *>(p);
-    p += pad8((size_t)blocks_of(nt, kBlock) * 4);
-    w.clusters_v = reinterpret_cast<uint32_t *>(p);
-    p += pad8((size_t)blocks_of(nv, kBlock) * 4);
-    w.degenerate_t = reinterpret_cast<uint32_t *>(p);
-    p += pad8((size_t)blocks_of(nt, kBlock) * 4);
-    w.duplicate_t = reinterpret_cast<uint32_t *>(p);
-    return w;
+    return at(ws, simplify_layout, nv, nt, ws_bytes >= bytes_of(simplify_layout, nv, nt, 1) ? 1 : 0);
 }
 
 // relaxed, agent scope: past the CU's L1
@@ -419,8 +357,6 @@ __global__ __launch_bounds__(kBlock) void k_sp_emit_t(const int32_t *__restrict_
     for (int k = 0; k < 3; ++k) out[(size_t)id * 3 + k] = vertex_map[tri[(size_t)t * 3 + k]];  // a survivor's indices are valid
 }
 
-bool sizes_ok(unsigned long long nv, unsigned long long nt) { return nv <= kMaxCount && nt <= kMaxCount; }
-
 bool lattice_ok(const float *origin_host, float cell) {
     if (origin_host == nullptr || !(cell > 0.f) || !std::isfinite(cell)) return false;
     return std::isfinite(origin_host[0]) && std::isfinite(origin_host[1]) && std::isfinite(origin_host[2]);
@@ -431,18 +367,17 @@ bool lattice_ok(const float *origin_host, float cell) {
 extern "C" {
 
 size_t mi3d_mesh_simplify_workspace(unsigned long long nv, unsigned long long nt, int tight) {
-    if (!sizes_ok(nv, nt) || (nv == 0 && nt == 0)) return 0;
-    return simplify_workspace_bytes((uint32_t)nv, (uint32_t)nt, tight ? 1 : 0);
+    if (!sizes_ok(nv, nt, kMaxCount, kMaxCount) || (nv == 0 && nt == 0)) return 0;
+    return bytes_of(simplify_layout, (uint32_t)nv, (uint32_t)nt, tight ? 0 : 1);
 }
 
 int mi3d_mesh_simplify_count(const float *vertices, unsigned long long nv, const int32_t *triangles, unsigned long long nt,
                              const float *origin_host, float cell, void *ws, size_t ws_bytes, unsigned long long *counts,
                              void *stream) {
-    if (!sizes_ok(nv, nt) || !lattice_ok(origin_host, cell)) return (int)hipErrorInvalidValue;
+    if (!sizes_ok(nv, nt, kMaxCount, kMaxCount) || !lattice_ok(origin_host, cell)) return (int)hipErrorInvalidValue;
     if (nv == 0 && nt == 0) return (int)hipSuccess;
-    if (counts == nullptr || !aligned8(counts) || ws == nullptr || !aligned8(ws) ||
-        ws_bytes < simplify_workspace_bytes((uint32_t)nv, (uint32_t)nt, 1) || (nt > 0 && triangles == nullptr) ||
-        (nv > 0 && vertices == nullptr))
+    if (!state_ok(ws, ws_bytes, bytes_of(simplify_layout, (uint32_t)nv, (uint32_t)nt, 0), counts) ||
+        (nt > 0 && triangles == nullptr) || (nv > 0 && vertices == nullptr))
         return (int)hipErrorInvalidValue;
     const uint32_t n = (uint32_t)nv, m = (uint32_t)nt;
     const uint32_t nbv = blocks_of(n, kBlock), nbt = blocks_of(m, kBlock);
@@ -471,10 +406,9 @@ int mi3d_mesh_simplify_emit(const float *vertices, unsigned long long nv, const 
                             const float *origin_host, float cell, void *ws, size_t ws_bytes, float *out_vertices,
                             unsigned long long nv_cap, int32_t *out_triangles, unsigned long long nt_cap,
                             int32_t *vertex_map, unsigned long long *lost, void *stream) {
-    if (!sizes_ok(nv, nt) || !lattice_ok(origin_host, cell)) return (int)hipErrorInvalidValue;
+    if (!sizes_ok(nv, nt, kMaxCount, kMaxCount) || !lattice_ok(origin_host, cell)) return (int)hipErrorInvalidValue;
     if (nv == 0) return (int)hipSuccess;  // nothing to map, and no triangle survives
-    if (lost == nullptr || !aligned8(lost) || ws == nullptr || !aligned8(ws) ||
-        ws_bytes < simplify_workspace_bytes((uint32_t)nv, (uint32_t)nt, 1) || vertices == nullptr ||
+    if (!state_ok(ws, ws_bytes, bytes_of(simplify_layout, (uint32_t)nv, (uint32_t)nt, 0), lost) || vertices == nullptr ||
         vertex_map == nullptr || (nt > 0 && triangles == nullptr) || (nv_cap > 0 && out_vertices == nullptr) ||
         (nt_cap > 0 && out_triangles == nullptr))
         return (int)hipErrorInvalidValue;

@@ -46,50 +46,10 @@ constexpr double kSaturate = 1099511627776.0;  // 2^40
 // counts (device uint64[8]): see Part 16
 enum { kUnusable = 0, kNonFinite = 1, kIsolated = 2, kBorder = 3, kOverDegree = 4, kClamped = 5, kErrors = 6 };
 
-// workspace: [cursor / degree: i32 x nv][offs: u32 x (nv + 1)][block sums / offsets: u32 x nbv][moves: u8 x nv]
-//            [second vertex buffer: f32 x 3 nv][pairs: i32 x 2 x 3 nt]; every array padded to 8 bytes
-struct SmoothWorkspace {
-    int32_t *cur;
-    uint32_t *offs, *block;
-    uint8_t *moves;
-    float *tmp;
-    int2 *pairs;
-};
-
-inline size_t smooth_workspace_bytes(uint32_t nv, uint32_t nt) {
-    return pad8((size_t)nv * 4) + pad8(((size_t)nv + 1) * 4) + pad8((size_t)blocks_of(nv, kBlock) * 4) + pad8(nv) +
-           pad8((size_t)nv * 12) + (size_t)nt * 24;
-}
-
-inline SmoothWorkspace smooth_carve(void *ws, uint32_t nv) {
-    char *p = reinterpret_cast<char *>(ws);
-    SmoothWorkspace w;
-    w.cur = reinterpret_cast<int32_t *>(p);
-    p += pad8((size_t)nv * 4);
-    w.offs = reinterpret_cast<uint32_t *>(p);
-    p += pad8(((size_t)nv + 1) * 4);
-    w.block = reinterpret_cast<uint32_t *>(p);
-    p += pad8((size_t)blocks_of(nv, kBlock) * 4);
-    w.moves = reinterpret_cast<uint8_t *>(p);
-    p += pad8(nv);
-    w.tmp = reinterpret_cast<float *>(p);
-    p += pad8((size_t)nv * 12);
-    w.pairs = reinterpret_cast<int2 *>(p);
-    return w;
-}
-
-// The corners of triangle t if it is usable (Part 16): indices in range, pairwise distinct, three finite vertices of the
-// INPUT.  Nothing is dereferenced before the index check.
-__device__ __forceinline__ bool usable(const float *__restrict__ vertices, uint32_t nv, const int32_t *__restrict__ tri,
-                                       uint32_t t, int32_t c[3]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) c[k] = tri[(size_t)t * 3 + k];
-    if (!(in_range(c[0], nv) && in_range(c[1], nv) && in_range(c[2], nv))) return false;
-    if (c[0] == c[1] || c[1] == c[2] || c[0] == c[2]) return false;
-    for (int k = 0; k < 3; ++k)
-        if (!finite3(vertices + (size_t)c[k] * 3)) return false;
-    return true;
-}
+// workspace: smooth_layout of mi3d_workspace.h, the one statement of its arrays and its size
+using mi3d_incidence::usable;
+using namespace mi3d_workspace;
+static_assert(kBlock == kLayoutBlock, "smooth_layout sizes its row of block sums by this workgroup");
 
 // ------------------------------------------------------------------------------------------------ the incidence, once
 
@@ -138,13 +98,10 @@ __global__ __launch_bounds__(kBlock) void k_sm_fill(const float *__restrict__ ve
     uint32_t lost = 0;
     if (t < nt && usable(vertices, nv, tri, t, c)) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const uint32_t v = (uint32_t)c[k];
-            const uint32_t begin = w.offs[v], len = w.offs[v + 1] - begin;
-            const uint32_t slot = (uint32_t)atomicAdd(w.cur + v, 1);
-            if (slot < len) w.pairs[(size_t)begin + slot] = make_int2(c[(k + 1) % 3], c[(k + 2) % 3]);
-            else ++lost;  // the mesh changed since k_sm_degree: counted, nothing stored
-        }
+        for (int k = 0; k < 3; ++k)  // lost: the mesh changed since k_sm_degree
+            lost += mi3d_incidence::fill(w.cur, w.offs, (uint32_t)c[k], [&](size_t i) {
+                w.pairs[i] = IndexPair{c[(k + 1) % 3], c[(k + 2) % 3]};
+            });
     }
     if (lost != 0) atomicAdd(&counts[kErrors], (unsigned long long)lost);  // never, on a mesh that stays as it is
 }
@@ -203,7 +160,7 @@ __global__ __launch_bounds__(kBlock) void k_sm_pass(const float *__restrict__ sr
             const uint32_t begin = w.offs[v], end = w.offs[v + 1];  // 0 < end - begin <= kMaxDegree
             long long S[3] = {0, 0, 0};
             for (uint32_t r = begin; r < end; ++r) {
-                const int2 pr = w.pairs[r];  // two vertices of a usable triangle: in range
+                const IndexPair pr = w.pairs[r];  // two vertices of a usable triangle: in range
                 if (!in_range(pr.x, nv) || !in_range(pr.y, nv)) continue;  // a slot k_sm_fill lost (counts[6]): no fault
 #pragma unroll
                 for (int a = 0; a < 3; ++a)
@@ -238,8 +195,6 @@ __global__ __launch_bounds__(kBlock) void k_sm_copy(const float *__restrict__ sr
     if (i < n) dst[i] = src[i];
 }
 
-bool sizes_ok(unsigned long long nv, unsigned long long nt) { return nv <= kMaxVertices && nt <= kMaxTriangles; }
-
 bool factor_ok(double k) { return std::isfinite(k) && k >= -1.0 && k <= 1.0; }
 
 }  // namespace
@@ -247,25 +202,25 @@ bool factor_ok(double k) { return std::isfinite(k) && k >= -1.0 && k <= 1.0; }
 extern "C" {
 
 size_t mi3d_mesh_smooth_workspace(unsigned long long nv, unsigned long long nt) {
-    if (!sizes_ok(nv, nt) || nv == 0) return 0;
-    return smooth_workspace_bytes((uint32_t)nv, (uint32_t)nt);
+    if (!sizes_ok(nv, nt, kMaxVertices, kMaxTriangles) || nv == 0) return 0;
+    return bytes_of(smooth_layout, (uint32_t)nv, (uint32_t)nt);
 }
 
 int mi3d_mesh_smooth(const float *vertices, unsigned long long nv, const int32_t *triangles, unsigned long long nt,
                      uint32_t iterations, double lambda, double mu, int pin_border, float max_move,
                      uint32_t fraction_bits, void *ws, size_t ws_bytes, float *out_vertices, unsigned long long *counts,
                      void *stream) {
-    if (!sizes_ok(nv, nt) || iterations < 1 || iterations > kMaxIterations || fraction_bits > kMaxFractionBits ||
+    if (!sizes_ok(nv, nt, kMaxVertices, kMaxTriangles) || iterations < 1 || iterations > kMaxIterations || fraction_bits > kMaxFractionBits ||
         !factor_ok(lambda) || !factor_ok(mu) || !(max_move >= 0.f))
         return (int)hipErrorInvalidValue;
     if (nv == 0) return (int)hipSuccess;
-    if (vertices == nullptr || out_vertices == nullptr || out_vertices == vertices || counts == nullptr ||
-        !aligned8(counts) || ws == nullptr || !aligned8(ws) ||
-        ws_bytes < smooth_workspace_bytes((uint32_t)nv, (uint32_t)nt) || (nt > 0 && triangles == nullptr))
+    if (vertices == nullptr || out_vertices == nullptr || out_vertices == vertices ||
+        !state_ok(ws, ws_bytes, bytes_of(smooth_layout, (uint32_t)nv, (uint32_t)nt), counts) ||
+        (nt > 0 && triangles == nullptr))
         return (int)hipErrorInvalidValue;
     const uint32_t n = (uint32_t)nv, m = (uint32_t)nt, nb = blocks_of(n, kBlock), nbt = blocks_of(m, kBlock);
     const hipStream_t st = as_stream(stream);
-    const SmoothWorkspace w = smooth_carve(ws, n);
+    const SmoothWorkspace w = at(ws, smooth_layout, n, m);
     hipLaunchKernelGGL(k_sm_init, dim3(nb < kInitBlocks ? nb : kInitBlocks), dim3(kBlock), 0, st, w.cur, n, counts);
     if (m) hipLaunchKernelGGL(k_sm_degree, dim3(nbt), dim3(kBlock), 0, st, vertices, n, triangles, m, w.cur, counts);
     hipLaunchKernelGGL(k_sm_block_sums, dim3(nb), dim3(kBlock), 0, st, n, w);

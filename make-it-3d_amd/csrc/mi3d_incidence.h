@@ -1,6 +1,7 @@
 // The vertex -> row scaffolding meshsmooth.hip and meshcollapse.hip share: per-vertex counts (the degrees, or a 0 / 1
 // flag) become row offsets by "sum per workgroup / one workgroup scans the sums / offsets = block base + rank".  The
 // three steps are device functions; each unit wraps them in its own kernels, which decide whether the step runs at all.
+// With them the rule that says which triangles take part (usable) and the claim of a row slot by its cursor (fill).
 #pragma once
 #include "mi3d_scan.h"
 
@@ -36,6 +37,30 @@ __device__ __forceinline__ void offsets(int32_t *__restrict__ cur, uint32_t nv, 
     if (v >= nv) return;
     offs[v] = block[blockIdx.x] + rank;
     cur[v] = 0;
+}
+
+// The corners of triangle t if it is usable (include/mi3d.h Part 16): indices in range, pairwise distinct, three finite
+// vertices.  Nothing is dereferenced before the index check.
+__device__ __forceinline__ bool usable(const float *__restrict__ vertices, uint32_t nv, const int32_t *__restrict__ tri,
+                                       uint32_t t, int32_t c[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = tri[(size_t)t * 3 + k];
+    if (!(in_range(c[0], nv) && in_range(c[1], nv) && in_range(c[2], nv))) return false;
+    if (c[0] == c[1] || c[1] == c[2] || c[0] == c[2]) return false;
+    for (int k = 0; k < 3; ++k)
+        if (!finite3(vertices + (size_t)c[k] * 3)) return false;
+    return true;
+}
+
+// One entry of v's row [offs[v], offs[v + 1]): the cursor hands out the slot, put(index) stores the payload there.
+// Returns 1, and stores nothing, for a slot beyond the row (the degrees were counted on another mesh), else 0.
+template <typename Put>
+__device__ __forceinline__ uint32_t fill(int32_t *cur, const uint32_t *offs, uint32_t v, Put put) {
+    const uint32_t begin = offs[v], len = offs[v + 1] - begin;
+    const uint32_t slot = (uint32_t)atomicAdd(cur + v, 1);
+    if (slot >= len) return 1u;
+    put((size_t)begin + slot);
+    return 0u;
 }
 
 }  // namespace mi3d_incidence

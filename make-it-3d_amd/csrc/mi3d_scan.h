@@ -10,6 +10,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "mi3d_workspace.h"
+
 namespace mi3d_scan {
 
 constexpr int kRowThreads = 1024, kRowWaves = kRowThreads / 64;  // the workgroup scan_row runs in
@@ -101,10 +103,20 @@ __device__ __forceinline__ void wave_count(bool pred, unsigned long long *counte
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
-inline uint32_t blocks_of(uint32_t n, uint32_t block) { return (n + block - 1) / block; }
-
-inline size_t pad8(size_t b) { return (b + 7) / 8 * 8; }
+using mi3d_workspace::blocks_of;
+using mi3d_workspace::bytes_of;
+using mi3d_workspace::pad8;
 
 inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
+// the sizes of a mesh within what the unit's indices hold
+inline bool sizes_ok(unsigned long long nv, unsigned long long nt, unsigned long long max_nv, unsigned long long max_nt) {
+    return nv <= max_nv && nt <= max_nt;
+}
+
+// what an entry point asks of its workspace and its counts: present, 8-byte aligned, the workspace of `need` bytes
+inline bool state_ok(const void *ws, size_t ws_bytes, size_t need, const void *counts) {
+    return counts != nullptr && aligned8(counts) && ws != nullptr && aligned8(ws) && ws_bytes >= need;
+}
 
 }  // namespace mi3d_scan

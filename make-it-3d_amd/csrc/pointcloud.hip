@@ -30,7 +30,7 @@ constexpr uint32_t kMaxSide = 16384;           // H, W: H * W <= 2^28 pixels, ev
 constexpr unsigned long long kMaxPoints = 0x7FFFFFFFull * kBlock;  // one thread per point, grid.x < 2^31
 constexpr int kTile = 32, kMaxBox = 31, kMaxTile = kTile + kMaxBox - 1;
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+using mi3d_scan::as_stream;
 
 // world -> camera rows [R | t] (3 x 4, row-major) and the intrinsics (3 x 3, row-major), by value in the kernel arguments
 struct Camera {

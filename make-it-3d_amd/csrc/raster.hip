@@ -31,7 +31,7 @@ using mi3d_scan::kRowWaves;
 
 constexpr int kTilePx = 16, kTileThreads = kTilePx * kTilePx, kMaxK = 8, kMaxC = 32;
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+using mi3d_scan::as_stream;
 
 // pytorch3d rasterization_utils.cuh PixToNonSquareNdc: centre of pixel i along an axis of S1 pixels (other axis S2)
 __host__ __device__ inline float pix_to_ndc(int i, int S1, int S2) {

@@ -16,13 +16,14 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mi3d.h"
+#include "mi3d_scan.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr uint32_t kMinT = 64, kMaxT = 16384, kMinCell = 4;
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+using mi3d_scan::as_stream;
 
 struct Atlas {
     uint32_t T, c, cols, rows, nt;  // cols x rows cells of (c + 1) x c texels; triangle i in cell i / 2 as half i & 1

@@ -17,6 +17,7 @@
 
 #include "../../include/mi3d.h"
 #include "mi3d_meshraster.h"
+#include "mi3d_scan.h"
 
 namespace {
 
@@ -26,7 +27,7 @@ constexpr uint32_t kMinT = 64, kMaxT = 16384;
 // the view record, the projection, the watertight edge function and the bounding-box walk: shared with meshrender.hip
 using namespace mi3d_meshraster;
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+using mi3d_scan::as_stream;
 
 __global__ __launch_bounds__(kBlock) void k_depth_fill(float *__restrict__ depth, size_t n,
                                                        unsigned long long *__restrict__ counts) {

@@ -49,6 +49,59 @@ CHUNK = 1 << 21      # field evaluations per launch group: the gather's planes c
 MIN_DIM, MAX_DIM = 2, 1024
 
 
+def _is_number(x, integer=False):
+    """An int or a float, NumPy's included, never a bool; with `integer` an int."""
+    kinds = (int, np.integer) if integer else (int, float, np.integer, np.floating)
+    return isinstance(x, kinds) and not isinstance(x, (bool, np.bool_))
+
+
+def _integer(x, name, lo, hi):
+    if not _is_number(x, integer=True):
+        raise Mi3dError(f"{name} must be an integer (got {x!r})")
+    if not lo <= int(x) <= hi:
+        raise Mi3dError(f"{name} must lie in [{lo}, {hi}] (got {x})")
+    return int(x)
+
+
+def _real(x, name, lo, hi, none=False):
+    """A number in [lo, hi] (never NaN) as a binary64; with `none`, None passes through."""
+    if x is None and none:
+        return None
+    if not _is_number(x):
+        raise Mi3dError(f"{name} must be a number{' or None' if none else ''} (got {x!r})")
+    if not lo <= float(x) <= hi:                                # false for NaN
+        raise Mi3dError(f"{name} must lie in [{lo:g}, {hi:g}] (got {x!r})")
+    return float(x)
+
+
+def _number(x, name, lo, hi):
+    return float(np.float32(_real(x, name, lo, hi)))           # as the kernels take it
+
+
+def _flag(x, name):
+    if not isinstance(x, (bool, np.bool_)):
+        raise Mi3dError(f"{name} must be a bool (got {x!r})")
+    return bool(x)
+
+
+_INF = float("inf")
+
+
+def _workspace(dev, query, *sizes, what=None):
+    """The workspace of a *_workspace query of the library: (int64 tensor on `dev`, its bytes).  With `what`, 0 bytes for
+    the mesh sizes (nv, nt) means more triangles than the unit takes."""
+    ws_bytes = int(getattr(_lib.lib(), query)(*sizes))
+    if ws_bytes == 0 and what is not None:
+        raise Mi3dError(f"{sizes[1]} triangles are more than {what} takes (2^30)")
+    return torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev), ws_bytes
+
+
+def _outputs(kv, kt, nv, dev):
+    """(vertices float32 [kv, 3], triangles int32 [kt, 3], vertex_map int32 [nv]) for an emit to fill."""
+    return (torch.empty(kv, 3, dtype=torch.float32, device=dev), torch.empty(kt, 3, dtype=torch.int32, device=dev),
+            torch.empty(nv, dtype=torch.int32, device=dev))
+
+
 def marching_cubes(volume, iso, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0)):
     """volume: float32 [Rx, Ry, Rz] on the GPU (x slowest).  Returns (vertices float32 [nv, 3], triangles int32 [nt, 3])
     on the same device, in the deterministic order of include/mi3d.h Part 8; an empty surface gives [0, 3] tensors."""
@@ -62,8 +115,7 @@ def marching_cubes(volume, iso, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0))
     if iso != iso:
         raise Mi3dError("iso must not be NaN")
     dev = vol.device
-    ws_bytes = int(_lib.lib().mi3d_mc_workspace(Rx, Ry, Rz))
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    ws, ws_bytes = _workspace(dev, "mi3d_mc_workspace", Rx, Ry, Rz)
     counts = torch.empty(4, dtype=torch.int64, device=dev)
     org = (C.c_float * 3)(*[float(o) for o in origin])
     spc = (C.c_float * 3)(*[float(s) for s in spacing])
@@ -101,17 +153,8 @@ def _check_mesh(vertices, triangles):
 
 
 def _check_keep_rule(min_faces, min_diagonal, largest):
-    if isinstance(min_faces, bool) or not isinstance(min_faces, (int, np.integer)):
-        raise Mi3dError(f"min_faces must be an integer (got {min_faces!r})")
-    if not 0 <= int(min_faces) < 2 ** 32:
-        raise Mi3dError(f"min_faces must lie in [0, 2^32) (got {min_faces})")
-    if isinstance(min_diagonal, bool) or not isinstance(min_diagonal, (int, float, np.integer, np.floating)):
-        raise Mi3dError(f"min_diagonal must be a number (got {min_diagonal!r})")
-    if not float(min_diagonal) >= 0.0:
-        raise Mi3dError(f"min_diagonal must be >= 0 and not NaN (got {min_diagonal})")
-    if not isinstance(largest, (bool, np.bool_)):
-        raise Mi3dError(f"largest must be a bool (got {largest!r})")
-    return int(min_faces), float(min_diagonal), bool(largest)
+    return (_integer(min_faces, "min_faces", 0, 2 ** 32 - 1), _real(min_diagonal, "min_diagonal", 0.0, _INF),
+            _flag(largest, "largest"))
 
 
 def _label_components(vertices, triangles):
@@ -152,20 +195,17 @@ def components(vertices, triangles):
 def _clean(vertices, triangles, min_faces, min_diagonal, largest):
     """clean() behind its argument checks; also returns the host copy of `counts`."""
     nv, nt, dev = int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
-    vertex_map = torch.empty(nv, dtype=torch.int32, device=dev)
     if nv == 0 and nt == 0:
-        return vertices.new_empty(0, 3), triangles.new_empty(0, 3), vertex_map, [0] * 8
+        return _outputs(0, 0, 0, dev) + ([0] * 8,)
     label, faces, box_min, box_max, counts = _label_components(vertices, triangles)
-    ws_bytes = int(_lib.lib().mi3d_mesh_components_workspace(nv, nt))
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    ws, ws_bytes = _workspace(dev, "mi3d_mesh_components_workspace", nv, nt)
     _lib.launch("mi3d_mesh_clean_count", vertices, _lib.ptr(triangles), nv, nt, _lib.ptr(label), _lib.ptr(faces),
                 _lib.ptr(box_min), _lib.ptr(box_max), min_faces, min_diagonal, int(largest), _lib.ptr(ws), ws_bytes,
                 _lib.ptr(counts))
     host = counts.tolist()                                   # the one host read a clean needs
     _check_counts(host, nv, nt)
     kv, kt = host[:2]
-    out_v = torch.empty(kv, 3, dtype=torch.float32, device=dev)
-    out_t = torch.empty(kt, 3, dtype=torch.int32, device=dev)
+    out_v, out_t, vertex_map = _outputs(kv, kt, nv, dev)
     _lib.launch("mi3d_mesh_clean_emit", vertices, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, _lib.ptr(label),
                 _lib.ptr(ws), ws_bytes, _lib.ptr(counts), _lib.ptr(out_v), kv, _lib.ptr(out_t), kt, _lib.ptr(vertex_map))
     return out_v, out_t, vertex_map, host
@@ -192,7 +232,7 @@ SIMPLIFY_COUNTS = ("vertices", "triangles", "bad_triangles", "gave_up", "non_fin
 
 def _check_positive(x, name):
     """A finite number > 0 that is still finite and > 0 as a binary32; returns it as a float."""
-    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+    if not _is_number(x):
         raise Mi3dError(f"{name} must be a number (got {x!r})")
     with np.errstate(over="ignore"):
         x32 = float(np.float32(x))
@@ -205,8 +245,7 @@ def _simplify_count(vertices, triangles, origin, cell):
     """mi3d_mesh_simplify_count on the current stream and the one host read: (state for _simplify_emit, counts as a
     list).  `origin` 3 floats, `cell` a float; both are rounded to binary32 here."""
     nv, nt, dev = int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
-    ws_bytes = int(_lib.lib().mi3d_mesh_simplify_workspace(nv, nt, 0))
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    ws, ws_bytes = _workspace(dev, "mi3d_mesh_simplify_workspace", nv, nt, 0)
     counts = torch.empty(8, dtype=torch.int64, device=dev)
     org = (C.c_float * 3)(*[float(o) for o in origin])
     cell = float(np.float32(cell))
@@ -223,9 +262,7 @@ def _simplify_emit(vertices, triangles, state, host):
     nv, nt, dev = int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
     ws, ws_bytes, org, cell = state
     kv, kt = host[:2]
-    out_v = torch.empty(kv, 3, dtype=torch.float32, device=dev)
-    out_t = torch.empty(kt, 3, dtype=torch.int32, device=dev)
-    vertex_map = torch.empty(nv, dtype=torch.int32, device=dev)
+    out_v, out_t, vertex_map = _outputs(kv, kt, nv, dev)
     lost = torch.empty(1, dtype=torch.int64, device=dev)
     _lib.launch("mi3d_mesh_simplify_emit", vertices, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, org, cell,
                 _lib.ptr(ws), ws_bytes, _lib.ptr(out_v), kv, _lib.ptr(out_t), kt, _lib.ptr(vertex_map), _lib.ptr(lost))
@@ -265,7 +302,7 @@ def simplify(vertices, triangles, cell, origin=None, return_stats=False):
         if len(origin) != 3 or not all(np.isfinite(o) for o in origin):
             raise Mi3dError(f"origin must be 3 finite numbers (got {origin!r})")
     if nv == 0 and nt == 0:
-        out = (vertices.new_empty(0, 3), triangles.new_empty(0, 3), torch.empty(0, dtype=torch.int32, device=dev))
+        out = _outputs(0, 0, 0, dev)
         return out + (dict(zip(SIMPLIFY_COUNTS, [0] * 8)),) if return_stats else out
     state, host = _simplify_count(vertices, triangles, origin, cell)
     _check_simplify_counts(host, nv, nt)
@@ -289,11 +326,7 @@ def _check_decimate(decimate, target_faces):
     if decimate is not None:
         decimate = _check_positive(decimate, "decimate")
     if target_faces is not None:
-        if isinstance(target_faces, (bool, np.bool_)) or not isinstance(target_faces, (int, np.integer)):
-            raise Mi3dError(f"target_faces must be an integer (got {target_faces!r})")
-        if int(target_faces) < 1:
-            raise Mi3dError(f"target_faces must be >= 1 (got {target_faces})")
-        target_faces = int(target_faces)
+        target_faces = _integer(target_faces, "target_faces", 1, 2 ** 63 - 1)
     return decimate, target_faces
 
 
@@ -340,35 +373,15 @@ SMOOTH_KEYS = ("iterations", "lam", "mu", "pin_border", "max_move")
 
 def _check_smooth(iterations, lam=SMOOTH_LAMBDA, mu=SMOOTH_MU, pin_border=True, max_move=None):
     """The arguments of smooth() that need no tensor: (iterations, lam, mu, pin_border, max_move as a float or None)."""
-    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)):
-        raise Mi3dError(f"iterations must be an integer (got {iterations!r})")
-    if not 1 <= int(iterations) <= SMOOTH_MAX_ITERATIONS:
-        raise Mi3dError(f"iterations must lie in [1, {SMOOTH_MAX_ITERATIONS}] (got {iterations})")
-    for name, k in (("lam", lam), ("mu", mu)):
-        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, float, np.integer, np.floating)):
-            raise Mi3dError(f"{name} must be a number (got {k!r})")
-        if not -1.0 <= float(k) <= 1.0:                         # false for NaN
-            raise Mi3dError(f"{name} must be finite and lie in [-1, 1] (got {k!r})")
-    lam, mu = float(lam), float(mu)                             # binary64, as the kernels take them
-    if not isinstance(pin_border, (bool, np.bool_)):
-        raise Mi3dError(f"pin_border must be a bool (got {pin_border!r})")
-    if max_move is not None:
-        if isinstance(max_move, (bool, np.bool_)) or not isinstance(max_move, (int, float, np.integer, np.floating)):
-            raise Mi3dError(f"max_move must be a number or None (got {max_move!r})")
-        if not float(max_move) >= 0.0:                          # false for NaN
-            raise Mi3dError(f"max_move must be >= 0 and not NaN (got {max_move!r})")
-        max_move = float(max_move)
-    return int(iterations), lam, mu, bool(pin_border), max_move
+    return (_integer(iterations, "iterations", 1, SMOOTH_MAX_ITERATIONS),
+            _real(lam, "lam", -1.0, 1.0), _real(mu, "mu", -1.0, 1.0),     # binary64, as the kernels take them
+            _flag(pin_border, "pin_border"), _real(max_move, "max_move", 0.0, _INF, none=True))
 
 
 def smooth_fraction_bits(extent):
     """The fraction bits e of include/mi3d.h Part 16 for coordinates up to `extent` in magnitude: the largest e <= 40
     with extent * 2^e <= 2^38, so that a coordinate may grow fourfold before its fixed-point image saturates."""
-    if isinstance(extent, (bool, np.bool_)) or not isinstance(extent, (int, float, np.integer, np.floating)):
-        raise Mi3dError(f"extent must be a number (got {extent!r})")
-    extent = float(extent)
-    if not (np.isfinite(extent) and extent >= 0.0):
-        raise Mi3dError(f"extent must be finite and >= 0 (got {extent!r})")
+    extent = _real(extent, "extent", 0.0, float(np.finfo(np.float64).max))      # finite
     exponent = int(np.frexp(extent)[1]) if extent > 0.0 else -SMOOTH_MAX_FRACTION_BITS   # extent <= 2^exponent
     return min(max(38 - exponent, 0), SMOOTH_MAX_FRACTION_BITS)
 
@@ -397,10 +410,7 @@ def smooth(vertices, triangles, iterations, lam=SMOOTH_LAMBDA, mu=SMOOTH_MU, pin
     if e is None:
         mag = torch.where(torch.isfinite(vertices), vertices.abs(), torch.zeros_like(vertices)).amax()
         e = smooth_fraction_bits(float(mag))                    # the one host read
-    ws_bytes = int(_lib.lib().mi3d_mesh_smooth_workspace(nv, nt))
-    if ws_bytes == 0:
-        raise Mi3dError(f"{nt} triangles are more than a smoothing takes (2^30)")
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    ws, ws_bytes = _workspace(dev, "mi3d_mesh_smooth_workspace", nv, nt, what="a smoothing")
     counts = torch.empty(8, dtype=torch.int64, device=dev)
     _lib.launch("mi3d_mesh_smooth", vertices, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, iterations, lam, mu,
                 int(pin_border), float("inf") if max_move is None else max_move, e, _lib.ptr(ws), ws_bytes, _lib.ptr(out),
@@ -445,20 +455,14 @@ COLLAPSE_MAX_ROUNDS, COLLAPSE_ROUNDS_PER_CALL = 1 << 20, 4096
 def _check_collapse(target_faces, max_error=None, max_rounds=256, rounds_per_read=8):
     """The arguments of collapse() that need no tensor: (target_faces, max_error as a float or None, max_rounds,
     rounds_per_read)."""
-    for name, x, lo, hi in (("target_faces", target_faces, 0, 2 ** 63 - 1), ("max_rounds", max_rounds, 0, COLLAPSE_MAX_ROUNDS),
-                            ("rounds_per_read", rounds_per_read, 1, COLLAPSE_ROUNDS_PER_CALL)):
-        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
-            raise Mi3dError(f"{name} must be an integer (got {x!r})")
-        if not lo <= int(x) <= hi:
-            raise Mi3dError(f"{name} must lie in [{lo}, {hi}] (got {x})")
+    target_faces = _integer(target_faces, "target_faces", 0, 2 ** 63 - 1)
+    max_rounds = _integer(max_rounds, "max_rounds", 0, COLLAPSE_MAX_ROUNDS)
+    rounds_per_read = _integer(rounds_per_read, "rounds_per_read", 1, COLLAPSE_ROUNDS_PER_CALL)
+    max_error = _real(max_error, "max_error", 0.0, _INF, none=True)
     if max_error is not None:
-        if isinstance(max_error, (bool, np.bool_)) or not isinstance(max_error, (int, float, np.integer, np.floating)):
-            raise Mi3dError(f"max_error must be a number or None (got {max_error!r})")
-        if not float(max_error) >= 0.0:                         # false for NaN
-            raise Mi3dError(f"max_error must be >= 0 and not NaN (got {max_error!r})")
         with np.errstate(over="ignore"):
             max_error = float(np.float32(max_error))            # binary32, as the kernels take it
-    return int(target_faces), max_error, int(max_rounds), int(rounds_per_read)
+    return target_faces, max_error, max_rounds, rounds_per_read
 
 
 def collapse(vertices, triangles, target_faces, max_error=None, max_rounds=256, rounds_per_read=8, return_stats=False):
@@ -480,13 +484,10 @@ def collapse(vertices, triangles, target_faces, max_error=None, max_rounds=256, 
     vertices, triangles = _check_mesh(vertices, triangles)
     nv, nt, dev = int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
     if nv == 0 and nt == 0:
-        out = (vertices.new_empty(0, 3), triangles.new_empty(0, 3), torch.empty(0, dtype=torch.int32, device=dev))
+        out = _outputs(0, 0, 0, dev)
         stats = dict(zip(COLLAPSE_COUNTS, [0] * 8), planeless_triangles=0, rounds_launched=0, done=True, stalled=False)
         return out + (stats,) if return_stats else out
-    ws_bytes = int(_lib.lib().mi3d_mesh_collapse_workspace(nv, nt))
-    if ws_bytes == 0:
-        raise Mi3dError(f"{nt} triangles are more than a collapse takes (2^30)")
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    ws, ws_bytes = _workspace(dev, "mi3d_mesh_collapse_workspace", nv, nt, what="a collapse")
     counts = torch.empty(8, dtype=torch.int64, device=dev)
     limit = float("inf") if max_error is None else max_error
     _lib.launch("mi3d_mesh_collapse_begin", vertices, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, _lib.ptr(ws),
@@ -502,9 +503,7 @@ def collapse(vertices, triangles, target_faces, max_error=None, max_rounds=256, 
     _lib.launch("mi3d_mesh_collapse_count", vertices, nv, nt, _lib.ptr(ws), ws_bytes, _lib.ptr(counts))
     host = counts.tolist()                                      # the read that sizes the output
     kv, kt = host[:2]
-    out_v = torch.empty(kv, 3, dtype=torch.float32, device=dev)
-    out_t = torch.empty(kt, 3, dtype=torch.int32, device=dev)
-    vertex_map = torch.empty(nv, dtype=torch.int32, device=dev)
+    out_v, out_t, vertex_map = _outputs(kv, kt, nv, dev)
     _lib.launch("mi3d_mesh_collapse_emit", vertices, nv, nt, _lib.ptr(ws), ws_bytes, _lib.ptr(out_v), kv, _lib.ptr(out_t),
                 kt, _lib.ptr(vertex_map), _lib.ptr(counts))
     if not return_stats:
@@ -713,14 +712,6 @@ def _check_view_size(V, H, W):
         raise Mi3dError(f"H and W must lie in [{MIN_VIEW_SIDE}, {MAX_VIEW_SIDE}] (got {H} x {W})")
 
 
-def _number(x, name, lo, hi):
-    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
-        raise Mi3dError(f"{name} must be a number (got {x!r})")
-    if not lo <= float(x) <= hi:                                # false for NaN
-        raise Mi3dError(f"{name} must lie in [{lo:g}, {hi:g}] (got {x!r})")
-    return float(np.float32(x))
-
-
 def check_views(images, c2w, K, masks=None, weights=None, power=4, min_cos=0.2, depth_tol=0.02):
     """Every view argument of bake_views, on the host, before anything is uploaded or launched.  Returns (records float32
     [V, 24], weights float32 [V], min_cos^2 as the binary32 product, depth_tol as a binary32, (V, H, W))."""
@@ -872,7 +863,7 @@ PREVIEW_KEYS = ("c2w", "K", "H", "W", "shading", "ssaa", "fidelity")
 def _check_shading(shading, ssaa):
     if not isinstance(shading, str) or shading not in SHADINGS:
         raise Mi3dError(f"shading must be one of {SHADINGS} (got {shading!r})")
-    if isinstance(ssaa, (bool, np.bool_)) or not isinstance(ssaa, (int, np.integer)) or ssaa not in SSAA:
+    if not _is_number(ssaa, integer=True) or ssaa not in SSAA:
         raise Mi3dError(f"ssaa must be one of {SSAA} (got {ssaa!r})")
     return shading, int(ssaa)
 
@@ -943,8 +934,7 @@ def _shade_backward(vertices, triangles, records, H, W, vis, dimage, uvs, shape)
     with them - from dimage float32 [V, H, W, 3].  The workspace comes from torch's allocator; nothing is read back."""
     dev, V = vertices.device, int(records.shape[0])
     grad = torch.empty(shape, dtype=torch.float32, device=dev)
-    ws_bytes = int(_lib.lib().mi3d_mesh_shade_backward_workspace(grad.numel()))
-    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    ws, ws_bytes = _workspace(dev, "mi3d_mesh_shade_backward_workspace", grad.numel())
     textured = uvs is not None
     _lib.launch("mi3d_mesh_shade_backward", vertices, _lib.ptr(vertices), int(vertices.shape[0]), _lib.ptr(triangles),
                 int(triangles.shape[0]), _lib.ptr(records), V, H, W, _lib.ptr(vis), _lib.ptr(dimage), _lib.ptr(uvs),
@@ -989,6 +979,36 @@ def box_average(x, ssaa):
     return s * (1.0 / (ssaa * ssaa))
 
 
+def _scaled_K(K, ssaa):
+    """K for ssaa x ssaa sub-pixels: its first two rows times ssaa (exact: a power of two); any other shape is returned
+    as it is, for view_records to refuse."""
+    K = _host64(K)
+    return K * np.array([[ssaa], [ssaa], [1.0]]) if K.shape == (3, 3) else K
+
+
+def _check_colour_source(nv, nt, dev, colors, uvs, texture):
+    """One colour source of a mesh of nv vertices and nt triangles on `dev`: colors float32 [nv, 3], or uvs float32
+    [3 nt, 2] with a texture uint8 or float32 [T, T, 3].  Returns (colors, uvs, texture) as the kernels take them."""
+    if colors is not None:
+        colors = _lib.dev_f32(colors, "colors", 3)
+        if tuple(colors.shape) != (nv, 3) or colors.device != dev:
+            raise Mi3dError(f"colors must be [{nv}, 3] on the mesh's device (got {tuple(colors.shape)} on {colors.device})")
+        return colors, None, None
+    if uvs is None or texture is None:
+        raise Mi3dError("uvs and texture go together")
+    uvs = _lib.dev_f32(uvs, "uvs", 2)
+    if not isinstance(texture, torch.Tensor):
+        raise TypeError("texture must be a torch.Tensor")
+    texture = _lib.dev_typed(texture, "texture", torch.float32 if texture.dtype == torch.float32 else torch.uint8)
+    if tuple(uvs.shape) != (3 * nt, 2) or uvs.device != dev:
+        raise Mi3dError(f"uvs must be [{3 * nt}, 2] on the mesh's device (got {tuple(uvs.shape)} on {uvs.device})")
+    if texture.dim() != 3 or texture.shape[0] != texture.shape[1] or texture.shape[2] != 3 or texture.device != dev or \
+            not MIN_TEXTURE <= texture.shape[0] <= MAX_TEXTURE:
+        raise Mi3dError(f"texture must be [T, T, 3] with T in [{MIN_TEXTURE}, {MAX_TEXTURE}] on the mesh's device (got "
+                        f"{tuple(texture.shape)} on {texture.device})")
+    return None, uvs, texture
+
+
 def render(vertices, triangles, c2w, K, H, W, colors=None, uvs=None, texture=None, normals=None, shading="albedo",
            light_d=None, ambient_ratio=0.1, bg_color=1.0, ssaa=1, return_buffers=False):
     """Images of an indexed mesh from V pinhole cameras (include/mi3d.h Part 17): vertices float32 [nv, 3], triangles
@@ -1014,10 +1034,7 @@ def render(vertices, triangles, c2w, K, H, W, colors=None, uvs=None, texture=Non
     outside [0, nv) raises Mi3dError.  Every argument is checked before anything is launched."""
     shading, ssaa = _check_shading(shading, ssaa)
     H, W = int(H), int(W)
-    Ks = _host64(K)
-    if Ks.shape == (3, 3):
-        Ks = Ks * np.array([[ssaa], [ssaa], [1.0]])             # the first two rows; exact: a power of two
-    records = view_records(c2w, Ks)
+    records = view_records(c2w, _scaled_K(K, ssaa))
     V = int(records.shape[0])
     _check_view_size(V, H, W)
     ambient, bg, light = _check_render_options(ambient_ratio, bg_color, light_d, V)
@@ -1030,23 +1047,7 @@ def render(vertices, triangles, c2w, K, H, W, colors=None, uvs=None, texture=Non
                             f"and a float32 texture are differentiable (detach {name})")
     if (colors is None) == (uvs is None and texture is None):
         raise Mi3dError("render takes exactly one colour source: colors, or uvs with texture")
-    if colors is not None:
-        colors = _lib.dev_f32(colors, "colors", 3)
-        if tuple(colors.shape) != (nv, 3) or colors.device != dev:
-            raise Mi3dError(f"colors must be [{nv}, 3] on the mesh's device (got {tuple(colors.shape)} on {colors.device})")
-    else:
-        if uvs is None or texture is None:
-            raise Mi3dError("uvs and texture go together")
-        uvs = _lib.dev_f32(uvs, "uvs", 2)
-        if not isinstance(texture, torch.Tensor):
-            raise TypeError("texture must be a torch.Tensor")
-        texture = _lib.dev_typed(texture, "texture", torch.float32 if texture.dtype == torch.float32 else torch.uint8)
-        if tuple(uvs.shape) != (3 * nt, 2) or uvs.device != dev:
-            raise Mi3dError(f"uvs must be [{3 * nt}, 2] on the mesh's device (got {tuple(uvs.shape)} on {uvs.device})")
-        if texture.dim() != 3 or texture.shape[0] != texture.shape[1] or texture.shape[2] != 3 or texture.device != dev or \
-                not MIN_TEXTURE <= texture.shape[0] <= MAX_TEXTURE:
-            raise Mi3dError(f"texture must be [T, T, 3] with T in [{MIN_TEXTURE}, {MAX_TEXTURE}] on the mesh's device (got "
-                            f"{tuple(texture.shape)} on {texture.device})")
+    colors, uvs, texture = _check_colour_source(nv, nt, dev, colors, uvs, texture)
     if normals is not None:
         normals = _lib.dev_f32(normals, "normals", 3)
         if tuple(normals.shape) != (nv, 3) or normals.device != dev:
@@ -1131,12 +1132,9 @@ MAX_FIT_ITERATIONS = 100000
 
 
 def _check_fit(iterations, lr):
-    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or \
-            not 1 <= iterations <= MAX_FIT_ITERATIONS:
-        raise Mi3dError(f"iterations must be an integer in [1, {MAX_FIT_ITERATIONS}] (got {iterations!r})")
-    if isinstance(lr, (bool, np.bool_)) or not isinstance(lr, (int, float, np.integer, np.floating)) or not 0 < lr <= 1:
+    if not _is_number(lr) or not 0 < lr <= 1:                   # false for NaN
         raise Mi3dError(f"lr must be a number in (0, 1] (got {lr!r})")
-    return int(iterations), float(lr)
+    return _integer(iterations, "iterations", 1, MAX_FIT_ITERATIONS), float(lr)
 
 
 def _fit(vertices, triangles, uvs, start, images, c2w, K, masks, weights, iterations, lr, ssaa, bg_color, return_history):
@@ -1146,8 +1144,7 @@ def _fit(vertices, triangles, uvs, start, images, c2w, K, masks, weights, iterat
     _, weights, _, _, (V, H, W) = check_views(images, c2w, K, masks, weights)
     if not weights.sum() > 0:
         raise Mi3dError("weights must not all be zero")
-    Ks = _host64(K) * np.array([[ssaa], [ssaa], [1.0]])
-    records = view_records(c2w, Ks)
+    records = view_records(c2w, _scaled_K(K, ssaa))
     _, bg, _ = _check_render_options(0.0, bg_color, None, V)
     _check_view_size(V, ssaa * H, ssaa * W)
     vertices, triangles = _check_mesh(vertices, triangles)
@@ -1155,18 +1152,9 @@ def _fit(vertices, triangles, uvs, start, images, c2w, K, masks, weights, iterat
     if not isinstance(start, torch.Tensor):
         raise TypeError("the start must be a torch.Tensor")
     if uvs is None:
-        start = _lib.dev_f32(start, "colors", 3)
-        if tuple(start.shape) != (nv, 3) or start.device != dev:
-            raise Mi3dError(f"colors must be [{nv}, 3] on the mesh's device (got {tuple(start.shape)} on {start.device})")
+        start = _check_colour_source(nv, nt, dev, start, None, None)[0]
     else:
-        uvs = _lib.dev_f32(uvs, "uvs", 2)
-        if tuple(uvs.shape) != (3 * nt, 2) or uvs.device != dev:
-            raise Mi3dError(f"uvs must be [{3 * nt}, 2] on the mesh's device (got {tuple(uvs.shape)} on {uvs.device})")
-        start = _lib.dev_typed(start, "texture", torch.float32 if start.dtype == torch.float32 else torch.uint8)
-        if start.dim() != 3 or start.shape[0] != start.shape[1] or start.shape[2] != 3 or start.device != dev or \
-                not MIN_TEXTURE <= start.shape[0] <= MAX_TEXTURE:
-            raise Mi3dError(f"texture must be [T, T, 3] with T in [{MIN_TEXTURE}, {MAX_TEXTURE}] on the mesh's device (got "
-                            f"{tuple(start.shape)} on {start.device})")
+        _, uvs, start = _check_colour_source(nv, nt, dev, None, uvs, start)
         if start.dtype == torch.uint8:
             start = start.float() / 255.0                       # what mi3d_mesh_shade makes of a byte
     rec = torch.from_numpy(records).to(dev)
@@ -1273,14 +1261,13 @@ def _check_preview(preview):
     p = dict(shading="albedo", ssaa=1, fidelity=False)
     p.update(preview)
     for k in ("H", "W"):
-        if isinstance(p[k], (bool, np.bool_)) or not isinstance(p[k], (int, np.integer)):
+        if not _is_number(p[k], integer=True):
             raise Mi3dError(f"preview: {k} must be an integer (got {p[k]!r})")
     V = view_records(p["c2w"], p["K"]).shape[0]
     _check_view_size(V, int(p["H"]), int(p["W"]))
     p["shading"], p["ssaa"] = _check_shading(p["shading"], p["ssaa"])
     _check_view_size(V, p["ssaa"] * int(p["H"]), p["ssaa"] * int(p["W"]))
-    if not isinstance(p["fidelity"], (bool, np.bool_)):
-        raise Mi3dError(f"preview: fidelity must be a bool (got {p['fidelity']!r})")
+    p["fidelity"] = _flag(p["fidelity"], "preview: fidelity")
     if p["fidelity"] and p["shading"] != "albedo":
         raise Mi3dError("preview: fidelity compares albedo renders: give shading='albedo' with it")
     return p

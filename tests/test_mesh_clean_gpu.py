@@ -546,6 +546,45 @@ def test_bad_indices_are_counted_and_never_dereferenced(cuda):
     assert np.array_equal(out_t[:-2].cpu().numpy(), rt[:-2]) and torch.all(out_t[-2:] == -7)
 
 
+def test_emit_into_short_buffers_counts_what_does_not_fit(cuda):
+    """A strip of 600 vertices / 598 triangles behind a one-triangle floater that min_faces=2 drops: both rows of block sums
+    have three entries, and the one kept row of each kind that does not fit stands in the LAST workgroup, so only `block
+    base + rank` finds it.  Caps one below the kept counts: a sentinel row behind each cap stays, the two losses are
+    counted, vertex_map is complete, and every row below the caps is that of a full emit."""
+    import torch
+    from mi3d import _lib
+    n = 600
+    strip = np.stack([np.arange(n - 2), np.arange(1, n - 1), np.arange(2, n)], 1) + 3
+    t = np.concatenate([[[0, 1, 2]], strip]).astype(np.int32)
+    v = coords(n + 3, 23)
+    nv, nt, kv, kt = n + 3, n - 1, n, n - 2
+    assert -(-nv // CLEAN_BLOCK) == 3 and -(-nt // CLEAN_BLOCK) == 3
+    rv, rt, rmap, _ = M.clean(v, t, 2, 0.0, False)
+    assert (len(rv), len(rt)) == (kv, kt) and rmap[nv - 1] == kv - 1 and (rmap[:3] == -1).all()
+    gv, gt = upload(cuda, v, t)
+    full_v, full_t, full_map, counted, emitted = clean_through_the_abi(gv, gt, 2, 0.0, False)
+    assert counted[:2] == [kv, kt] and emitted[6] == 0
+    assert full_v.cpu().numpy().tobytes() == rv.tobytes() and np.array_equal(full_t.cpu().numpy(), rt)
+
+    from mi3d import mesh
+    p = _lib.ptr
+    label, faces, bmin, bmax, counts = mesh._label_components(gv, gt)
+    need = int(_lib.lib().mi3d_mesh_components_workspace(nv, nt))
+    ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=cuda)
+    _lib.launch("mi3d_mesh_clean_count", gv, p(gt), nv, nt, p(label), p(faces), p(bmin), p(bmax), 2, 0.0, 0, p(ws), need,
+                p(counts))
+    out_v = torch.full((kv, 3), -7.0, device=cuda)             # row kv - 1: the sentinel behind the cap
+    out_t = torch.full((kt, 3), -7, dtype=torch.int32, device=cuda)
+    vmap = torch.full((nv,), -7, dtype=torch.int32, device=cuda)
+    _lib.launch("mi3d_mesh_clean_emit", gv, p(gv), nv, p(gt), nt, p(label), p(ws), need, p(counts), p(out_v), kv - 1,
+                p(out_t), kt - 1, p(vmap))
+    host = counts.tolist()
+    assert host[:2] == [kv, kt] and host[6] == 2
+    assert torch.all(out_v[kv - 1] == -7.0) and torch.all(out_t[kt - 1] == -7)
+    assert torch.equal(out_v[:kv - 1], full_v[:kv - 1]) and torch.equal(out_t[:kt - 1], full_t[:kt - 1])
+    assert torch.equal(vmap, full_map) and np.array_equal(vmap.cpu().numpy(), rmap)
+
+
 def test_c_abi_argument_checks_launch_nothing(cuda):
     """hipErrorInvalidValue (1) for NULL pointers, a short or misaligned workspace, sizes out of range and a bad
     min_diagonal; success (0) without a launch for an empty mesh.  Nothing refused touches its buffers."""
