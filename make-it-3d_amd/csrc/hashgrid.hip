@@ -88,12 +88,17 @@ __device__ __forceinline__ void point_of(const PointSet &ps, const float (&b)[2]
 // Feature / gradient planes hold one pair per (level, row): fp32 (8 bytes) or - under torch.autocast(float16), where
 // the MLP's first layer rounds its input to binary16 and its input gradient comes out of a binary16 GEMM anyway -
 // binary16 (4 bytes): the same values the fp32 planes would hold after the rounding autocast applies to them.
+__device__ __forceinline__ float2 half_pair(uint32_t u) {   // a binary16 pair as it lies in memory -> two floats
+    return make_float2((float)__builtin_bit_cast(_Float16, (unsigned short)(u & 0xFFFFu)),
+                       (float)__builtin_bit_cast(_Float16, (unsigned short)(u >> 16)));
+}
+// a gradient pair from the raw bits it was loaded as: binary16 planes keep the whole pair in r0
+template <bool HP>
+__device__ __forceinline__ float2 raw_pair(uint32_t r0, uint32_t r1) {
+    return HP ? half_pair(r0) : make_float2(__uint_as_float(r0), __uint_as_float(r1));
+}
 __device__ __forceinline__ float2 plane_pair(const float *planes, int half, size_t i) {
-    if (half) {
-        const uint32_t u = reinterpret_cast<const uint32_t *>(planes)[i];
-        return make_float2((float)__builtin_bit_cast(_Float16, (unsigned short)(u & 0xFFFFu)),
-                           (float)__builtin_bit_cast(_Float16, (unsigned short)(u >> 16)));
-    }
+    if (half) return half_pair(reinterpret_cast<const uint32_t *>(planes)[i]);
     return reinterpret_cast<const float2 *>(planes)[i];
 }
 typedef float f32x2_native __attribute__((ext_vector_type(2)));
@@ -480,11 +485,6 @@ __device__ __forceinline__ void gather_corners(const GridLevel &L, const float2 
 
 struct __attribute__((packed, aligned(8))) EntryPair { float ax, ay, bx, by; };  // entries e, e + 1 of a level
 
-// (24-bit multiplies for the spatial hash and the gather table's slot hash: tried in round 6, slightly slower - DESIGN.md 3.2, A.11)
-__device__ __forceinline__ uint32_t merge_slot(uint32_t e) {   // 9-bit slot of the per-wave gather table (kMergeSlots = 512)
-    return (e * 2654435761u) >> (32 - 9);
-}
-
 // four corner entries of a cell - the z-bit `zb` half of its eight, corner j = x-bit | y-bit << 1 - by the short routes
 // (grid_entry's values)
 __device__ __forceinline__ void corner_entries4(const GridLevel &L, const LevelFast &F, uint32_t cx, uint32_t cy,
@@ -584,10 +584,8 @@ __device__ __forceinline__ void encode_points(const PointSet &ps, const float (&
         float2 v[8];
         if (KIND == kGeneral || !gather_corners_fast<KIND, PAIR>(L, F, lvl, cx, cy, cz, v))
             gather_corners<PAIR>(L, lvl, cx, cy, cz, v);
-        const float gx = 1.0f - fx, gy = 1.0f - fy, gz = 1.0f - fz;
-        // weights in tcnn's multiplication order ((1 * wx) * wy) * wz, corners accumulated in its order
-        const float w00 = gx * gy, w10 = fx * gy, w01 = gx * fy, w11 = fx * fy;
-        const float w[8] = {w00 * gz, w10 * gz, w01 * gz, w11 * gz, w00 * fz, w10 * fz, w01 * fz, w11 * fz};
+        float w[8];   // tcnn's multiplication order, corners accumulated in its order
+        corner_weights(fx, fy, fz, w);
         float r0 = 0.f, r1 = 0.f;
 #pragma unroll
         for (int k = 0; k < 8; ++k) { r0 += w[k] * v[k].x; r1 += w[k] * v[k].y; }
@@ -1021,9 +1019,8 @@ __global__ __launch_bounds__(kWave *kWaves) void k_scatter_runs(PointSet ps, uin
             grid_cell(q[0], L.scale, cx, fx);
             grid_cell(q[1], L.scale, cy, fy);
             grid_cell(q[2], L.scale, cz, fz);
-            const float gx = 1.0f - fx, gy = 1.0f - fy, gz = 1.0f - fz;
-            const float w00 = gx * gy, w10 = fx * gy, w01 = gx * fy, w11 = fx * fy;  // the forward's product order
-            const float wk[8] = {w00 * gz, w10 * gz, w01 * gz, w11 * gz, w00 * fz, w10 * fz, w01 * fz, w11 * fz};
+            float wk[8];
+            corner_weights(fx, fy, fz, wk);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 slab[lane * kRunStride + 2 * k] = has ? wk[k] * d0 : 0.f;
@@ -1170,17 +1167,31 @@ int launch_second_order(const PointSet &ps, uint32_t n, const float *dout, const
 __device__ __forceinline__ void unpack_row12(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t &e_local, uint32_t &t, float &w,
                                              float &fx, float &dx, float &dy) {
     unpack_row12_fields(w0, w2, e_local, t, w, fx);
-    dx = (float)__builtin_bit_cast(_Float16, (unsigned short)(w1 & 0xFFFFu));
-    dy = (float)__builtin_bit_cast(_Float16, (unsigned short)(w1 >> 16));
+    const float2 d = half_pair(w1);
+    dx = d.x; dy = d.y;
+}
+
+// neither value is inf or NaN (a NaN fails the comparison)
+constexpr float kFltMax = 3.4028234663852886e38f;
+__device__ __forceinline__ bool finite2(float a, float b) { return fabsf(a) <= kFltMax && fabsf(b) <= kFltMax; }
+
+// The float-atomic route: one pair straight to its table entry.  It serves a region that is full and every non-finite
+// value: those never enter the fixed-point path, and float atomics put the inf / NaN on exactly the entries the
+// reference's atomicAdd would have put it on (GradScaler then sees it).
+__device__ __forceinline__ void table_add(float *grad_table, const GridLevel &L, uint32_t e, float a, float b) {
+    float *dst = grad_table + ((size_t)L.offset + e) * 2;
+    unsafeAtomicAdd(dst, a);
+    unsafeAtomicAdd(dst + 1, b);
 }
 
 __device__ __forceinline__ void emit_record(const BinPlan &plan, const GridLevel &L, uint32_t l, uint32_t gw, uint32_t e,
                                             float g0, float g1, uint32_t *fill, BinRecord *__restrict__ arena,
                                             float *__restrict__ grad_table, float &lmax) {
     const uint32_t b = e >> kBinShift;
-    // a non-finite contribution never enters the fixed-point path: it goes to the table with float atomics, which puts
-    // the inf / NaN on exactly the entries the reference's atomicAdd would have put it on (GradScaler then sees it)
-    const bool finite = fabsf(g0) <= 3.4028234663852886e38f && fabsf(g1) <= 3.4028234663852886e38f;
+    // a non-finite contribution takes the float-atomic route.  (finite2's test spelled out: as a call it reaches this
+    // function as one and-ed flag, not two branches, and each of the 56 inlined copies then loses a v_mov - the emit's
+    // instruction stream is held fixed)
+    const bool finite = fabsf(g0) <= kFltMax && fabsf(g1) <= kFltMax;
     uint32_t slot = 0xFFFFFFFFu;
     if (finite) {
         slot = atomicAdd(&fill[plan.level_bin0[l] + b], 1u);  // wave-private LDS counter
@@ -1190,19 +1201,10 @@ __device__ __forceinline__ void emit_record(const BinPlan &plan, const GridLevel
         BinRecord r{e, g0, g1};
         reinterpret_cast<BinRecord *>(reinterpret_cast<char *>(arena) + plan.level_base[l])[((size_t)gw * level_bins(L) + b) * plan.level_cap[l] + slot] = r;
     } else {  // region full (or non-finite): straight to the table
-        float *dst = grad_table + ((size_t)L.offset + e) * 2;
-        unsafeAtomicAdd(dst, g0);
-        unsafeAtomicAdd(dst + 1, g1);
+        table_add(grad_table, L, e, g0, g1);
     }
 }
-
-// round-to-nearest-even of x (|x| < 2^51) as a 64-bit two's complement integer: adding 1.5 * 2^52 in binary64 leaves it in
-// the low mantissa bits.  Same result as __float2ll_rn, 5 VALU operations instead of the ~13 of the software conversion
-// (there is no native float -> int64), four times per record.
-__device__ __forceinline__ unsigned long long fixed_point(float x) {
-    const double d = (double)x + 6755399441055744.0;
-    return (unsigned long long)(__double_as_longlong(d) - 0x4338000000000000ll);
-}
+// (fixed_point, the 1.5 * 2^52 rounding both passes use for their 64-bit sums, is in mi3d_common.h)
 
 // Coarse levels (cells of 3 marching steps and more): the 64 samples of a tile x 13 stencil points x 8 corners fall on a
 // few hundred distinct entries at most, so the wave first sums them in a small LDS hash table - entry -> two 64-bit
@@ -1219,6 +1221,94 @@ constexpr uint32_t kMergeProbes = 16, kMergeEmpty = 0xFFFFFFFFu;   // (kMergeSlo
 constexpr uint32_t kChunkPts = 2, kStageRecs = kWave * 4 * kChunkPts;
 static_assert(kStageRecs * 16 == 2 * kMergeSlots * 8, "the staging area is the gather table's sums");
 static_assert(3 * 64 <= kMergeSlots, "histogram, cursors and region deltas live in the gather table's keys");
+
+// What the pieces of the emit are handed for their (tile, level), all of it wave-uniform: the plan, the level and its short
+// entry routes, this wave's index within its role, the wave's fill counters (of all bins), the record arena and the
+// gradient table.
+struct EmitLevel {
+    const BinPlan &plan;
+    const GridLevel &L;
+    const LevelFast &LF;
+    uint32_t l, gw;
+    uint32_t *fill;
+    BinRecord *arena;
+    float *grad_table;
+};
+
+// The coarse role's gather table (one per wave, in LDS): entry -> two 64-bit fixed-point sums, scaled by a power of two
+// from the tile's largest gradient (gather_scale, mi3d_common.h).  Between two (tile, level)s it is empty.
+struct GatherTable {
+    unsigned long long *sums;   // [kMergeSlots][2]
+    uint32_t *keys;             // [kMergeSlots], kMergeEmpty where free
+    float scale;
+    double unscale;
+
+    __device__ __forceinline__ void clear(int lane) const {
+        for (uint32_t i = lane; i < kMergeSlots; i += kWave) { keys[i] = kMergeEmpty; sums[2 * i] = 0ull; sums[2 * i + 1] = 0ull; }
+    }
+    // Four entries e[j] with the values g[K0 + j].  All first probes are issued before any of their results is looked at:
+    // an LDS compare-and-swap returns after ~120 cycles, and eight dependent probe loops in a row (round 2) made the
+    // coarse role a chain of LDS latencies - 36 of the 61 ms of a dense 13-point emit (rocprofv3 per level,
+    // profiles/kernel_trace_r03_scatter_levels.csv).  A probe that finds its slot taken by another entry (rare at 512
+    // slots for a few hundred entries) walks on alone; zeros are skipped; a contribution that finds no slot within
+    // kMergeProbes goes out as a record of its own (lmax: see emit_record).
+    template <uint32_t K0, uint32_t N>
+    __device__ __forceinline__ void add4(const EmitLevel &lv, const uint32_t (&e)[4], const float (&g0)[N],
+                                         const float (&g1)[N], float &lmax) const {
+        static_assert(kMergeSlots == 512, "the slot hash keeps 9 bits");
+        uint32_t slot[4], old[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) slot[j] = merge_slot(e[j]);
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t k = K0 + j;
+            old[j] = (g0[k] != 0.f || g1[k] != 0.f) ? atomicCAS(&keys[slot[j]], kMergeEmpty, e[j]) : e[j];
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t k = K0 + j;
+            if (!(g0[k] != 0.f || g1[k] != 0.f)) continue;
+            bool placed = old[j] == kMergeEmpty || old[j] == e[j];
+            for (uint32_t tries = 1; !placed && tries < kMergeProbes; ++tries) {
+                slot[j] = (slot[j] + 1u) & (kMergeSlots - 1u);
+                const uint32_t o = atomicCAS(&keys[slot[j]], kMergeEmpty, e[j]);
+                placed = o == kMergeEmpty || o == e[j];
+            }
+            if (placed) {
+                atomicAdd(&sums[2 * slot[j]], fixed_point(g0[k] * scale));
+                atomicAdd(&sums[2 * slot[j] + 1], fixed_point(g1[k] * scale));
+            } else {
+                emit_record(lv.plan, lv.L, lv.l, lv.gw, e[j], g0[k], g1[k], lv.fill, lv.arena, lv.grad_table, lmax);
+            }
+        }
+    }
+    // the 8 corners of cell (ex, ey, ez): two batches of four probes in flight (registers)
+    __device__ __forceinline__ void add8(const EmitLevel &lv, uint32_t ex, uint32_t ey, uint32_t ez, const float (&g0)[8],
+                                         const float (&g1)[8], float &lmax) const {
+#pragma unroll
+        for (uint32_t half = 0; half < 2; ++half) {
+            uint32_t e[4];
+            corner_entries4(lv.L, lv.LF, ex, ey, ez, half, e);
+            if (half == 0) add4<0>(lv, e, g0, g1, lmax);
+            else add4<4>(lv, e, g0, g1, lmax);
+        }
+    }
+    // the end of a coarse (tile, level): one record per distinct entry the tile touched; the table is left empty
+    __device__ __forceinline__ void drain(const EmitLevel &lv, int lane, float &lmax) const {
+        __builtin_amdgcn_wave_barrier();
+        for (uint32_t i = lane; i < kMergeSlots; i += kWave) {
+            const uint32_t e = keys[i];
+            if (e != kMergeEmpty) {
+                const long long a0 = (long long)sums[2 * i], a1 = (long long)sums[2 * i + 1];
+                keys[i] = kMergeEmpty; sums[2 * i] = 0ull; sums[2 * i + 1] = 0ull;
+                if (a0 != 0 || a1 != 0)
+                    emit_record(lv.plan, lv.L, lv.l, lv.gw, e, (float)((double)a0 * unscale), (float)((double)a1 * unscale),
+                                lv.fill, lv.arena, lv.grad_table, lmax);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+};
 
 template <bool HP>
 __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint32_t s_begin, uint32_t s_end,
@@ -1244,8 +1334,9 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
     unsigned long long *sums = emit_lds + (size_t)wave_in_wg * (emit_wave_words(plan.n_bins) / 2u);  // [kMergeSlots][2]
     uint32_t *keys = reinterpret_cast<uint32_t *>(sums + 2 * kMergeSlots);                            // [kMergeSlots]
     uint32_t *fill = keys + kMergeSlots;  // [n_bins] records appended so far by this wave
+    GatherTable table{sums, keys, 0.f, 0.0};
     for (uint32_t b = lane; b < plan.n_bins; b += kWave) fill[b] = 0;
-    for (uint32_t i = lane; i < kMergeSlots; i += kWave) { keys[i] = kMergeEmpty; sums[2 * i] = 0ull; sums[2 * i + 1] = 0ull; }
+    table.clear(lane);
     if (lane < MI3D_MAX_LEVELS) lmax_all[wave_in_wg][lane] = 0.f;
     if (gw >= n_waves) return;
 
@@ -1289,6 +1380,7 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
             uint32_t *fill_l = fill + plan.level_bin0[l];
             RowRecord *region0 = reinterpret_cast<RowRecord *>(reinterpret_cast<char *>(arena) + plan.level_base[l]) +
                                  (size_t)gw * level_bins(L) * cap;
+            const EmitLevel lv{plan, L, LF, l, gw, fill, arena, grad_table};
             // ALL gradient pairs of this (tile, level) are fetched before its first record is stored.  gfx950 has one
             // counter for vector loads and stores (vmcnt), and the compiler cannot count the conditional stores between a
             // load and its use - so a load consumed inside the point loop costs "s_waitcnt vmcnt(0)": a full drain of the
@@ -1322,9 +1414,8 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
             if (extra0 != nullptr) {
                 const size_t erow = (size_t)l * n_rows + (valid ? s : s_end - 1u);
                 if (HP) {
-                    const uint32_t u = reinterpret_cast<const uint32_t *>(extra0)[erow];
-                    ex0x = (float)__builtin_bit_cast(_Float16, (unsigned short)(u & 0xFFFFu));
-                    ex0y = (float)__builtin_bit_cast(_Float16, (unsigned short)(u >> 16));
+                    const float2 v = half_pair(reinterpret_cast<const uint32_t *>(extra0)[erow]);
+                    ex0x = v.x; ex0y = v.y;
                 } else {
                     const float2 v = reinterpret_cast<const float2 *>(extra0)[erow];
                     ex0x = v.x; ex0y = v.y;
@@ -1332,22 +1423,19 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
             }
             // coarse level: the power-of-two scale of the wave's gather table, from the tile's largest gradient (every
             // contribution is a weight <= 1 times a gradient, 6656 of them per tile: |sum| < 2^13 2^40)
-            float merge_scale = 0.f;
-            double merge_unscale = 0.0;
+            table.scale = 0.f;
+            table.unscale = 0.0;
             bool merge_any = false, dead = false;
             if (merge) {
                 float tmax = 0.f;
                 bool bad = false;
 #pragma unroll
                 for (uint32_t k = 0; k < (uint32_t)kMaxPts; ++k) {
-                    float dx = HP ? (float)__builtin_bit_cast(_Float16, (unsigned short)(raw0[k] & 0xFFFFu))
-                                           : __uint_as_float(raw0[k]);
-                    float dy = HP ? (float)__builtin_bit_cast(_Float16, (unsigned short)(raw0[k] >> 16))
-                                           : __uint_as_float(raw1[HP ? 0 : k]);
-                    if (k == 0u) { dx += ex0x; dy += ex0y; }
+                    float2 d = raw_pair<HP>(raw0[k], raw1[HP ? 0 : k]);
+                    if (k == 0u) { d.x += ex0x; d.y += ex0y; }
                     if (valid && k < ps.P) {
-                        bad |= !(fabsf(dx) <= 3.4028234663852886e38f && fabsf(dy) <= 3.4028234663852886e38f);
-                        tmax = fmaxf(tmax, fmaxf(fabsf(dx), fabsf(dy)));
+                        bad |= !finite2(d.x, d.y);
+                        tmax = fmaxf(tmax, fmaxf(fabsf(d.x), fabsf(d.y)));
                     }
                 }
 #pragma unroll
@@ -1355,80 +1443,15 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                 if (__ballot(bad) != 0ull) {  // inf / NaN in the tile: its contributions go to the table one by one (float
                     dead = true;              // atomics, as the reference adds them) instead of through the fixed-point sums
                 } else if (tmax > 0.f) {
-                    int ex;
-                    (void)frexpf(tmax, &ex);  // tmax < 2^ex
-                    int k2 = 40 - ex;
-                    k2 = k2 > 126 ? 126 : (k2 < -126 ? -126 : k2);
-                    merge_scale = ldexpf(1.0f, k2);
-                    merge_unscale = ldexp(1.0, -k2);
+                    const GatherScale gs = gather_scale(tmax);
+                    table.scale = gs.scale;
+                    table.unscale = gs.unscale;
                     merge_any = true;
                 }
             }
             uint32_t bx = 0, by = 0, bz = 0;  // the cell of the current group's base position
             float acc0[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, acc1[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             bool acc_any = false;
-            // The 8 corners of a cell into the wave's gather table (kMergeSlots).  All eight first probes are issued
-            // before any of their results is looked at: an LDS compare-and-swap returns after ~120 cycles, and eight
-            // dependent probe loops in a row (round 2) made the coarse role a chain of LDS latencies - 36 of the 61 ms of
-            // a dense 13-point emit (rocprofv3 per level, profiles/kernel_trace_r03_scatter_levels.csv).  A probe that
-            // finds its slot taken by another entry (rare at 512 slots for a few hundred entries) walks on alone.
-            auto gather8 = [&](uint32_t ex, uint32_t ey, uint32_t ez, const float (&g0)[8], const float (&g1)[8]) __attribute__((always_inline)) {
-                static_assert(kMergeSlots == 512, "the slot hash keeps 9 bits");
-#pragma unroll
-                for (uint32_t half = 0; half < 2; ++half) {  // two batches of four probes in flight (registers)
-                    uint32_t e[4], slot[4], old[4];
-                    corner_entries4(L, LF, ex, ey, ez, half, e);
-#pragma unroll
-                    for (uint32_t j = 0; j < 4; ++j) slot[j] = merge_slot(e[j]);
-#pragma unroll
-                    for (uint32_t j = 0; j < 4; ++j) {
-                        const uint32_t k = 4 * half + j;
-                        old[j] = (g0[k] != 0.f || g1[k] != 0.f) ? atomicCAS(&keys[slot[j]], kMergeEmpty, e[j]) : e[j];
-                    }
-#pragma unroll
-                    for (uint32_t j = 0; j < 4; ++j) {
-                        const uint32_t k = 4 * half + j;
-                        if (!(g0[k] != 0.f || g1[k] != 0.f)) continue;
-                        bool placed = old[j] == kMergeEmpty || old[j] == e[j];
-                        for (uint32_t tries = 1; !placed && tries < kMergeProbes; ++tries) {
-                            slot[j] = (slot[j] + 1u) & (kMergeSlots - 1u);
-                            const uint32_t o = atomicCAS(&keys[slot[j]], kMergeEmpty, e[j]);
-                            placed = o == kMergeEmpty || o == e[j];
-                        }
-                        if (placed) {
-                            atomicAdd(&sums[2 * slot[j]], fixed_point(g0[k] * merge_scale));
-                            atomicAdd(&sums[2 * slot[j] + 1], fixed_point(g1[k] * merge_scale));
-                        } else {
-                            emit_record(plan, L, l, gw, e[j], g0[k], g1[k], fill, arena, grad_table, lmax);
-                        }
-                    }
-                }
-            };
-            // four given entries into the gather table (the second half of what gather8 does per batch)
-            auto gather4 = [&](const uint32_t (&e)[4], const float (&g0)[4], const float (&g1)[4]) __attribute__((always_inline)) {
-                uint32_t slot[4], old[4];
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j) slot[j] = merge_slot(e[j]);
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j)
-                    old[j] = (g0[j] != 0.f || g1[j] != 0.f) ? atomicCAS(&keys[slot[j]], kMergeEmpty, e[j]) : e[j];
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j) {
-                    if (!(g0[j] != 0.f || g1[j] != 0.f)) continue;
-                    bool placed = old[j] == kMergeEmpty || old[j] == e[j];
-                    for (uint32_t tries = 1; !placed && tries < kMergeProbes; ++tries) {
-                        slot[j] = (slot[j] + 1u) & (kMergeSlots - 1u);
-                        const uint32_t o = atomicCAS(&keys[slot[j]], kMergeEmpty, e[j]);
-                        placed = o == kMergeEmpty || o == e[j];
-                    }
-                    if (placed) {
-                        atomicAdd(&sums[2 * slot[j]], fixed_point(g0[j] * merge_scale));
-                        atomicAdd(&sums[2 * slot[j] + 1], fixed_point(g1[j] * merge_scale));
-                    } else {
-                        emit_record(plan, L, l, gw, e[j], g0[j], g1[j], fill, arena, grad_table, lmax);
-                    }
-                }
-            };
             // A +eps / -eps neighbour pair along AXIS whose point left the base cell sits in the cell NEXT to it: the four
             // corners on the face between the two cells ARE corners of the base cell - those contributions join the group's
             // register sums - and only the four corners of the far face go through the gather table: 12 LDS atomics per
@@ -1448,18 +1471,14 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                 float f0[4], f1[4];
                 const uint32_t far_c = (AXIS == 0 ? bx : (AXIS == 1 ? by : bz)) + (fa ? 2u : 0xFFFFFFFFu);   // base + 2 / base - 1
 #pragma unroll
-                for (uint32_t j = 0; j < 4; ++j) {
-                    const uint32_t lo = j & 1u, hi = j >> 1;   // the two other axes' bits, in x < y < z order
-                    const uint32_t k1 = AXIS == 0 ? (1u | lo << 1 | hi << 2) : (AXIS == 1 ? (lo | 2u | hi << 2) : (lo | hi << 1 | 4u));
-                    const uint32_t k0 = k1 & ~m;
+                for (uint32_t j = 0; j < 4; ++j) {   // (the far face's corner maps: mi3d_common.h)
+                    const uint32_t k1 = face_k1(AXIS, j), k0 = face_k0(AXIS, j);
                     f0[j] = fa ? a0[k1] : (fb ? b0[k0] : 0.f);
                     f1[j] = fa ? a1[k1] : (fb ? b1[k0] : 0.f);
-                    const uint32_t x = AXIS == 0 ? far_c : bx + lo;
-                    const uint32_t y = AXIS == 1 ? far_c : by + (AXIS == 0 ? lo : hi);
-                    const uint32_t z = AXIS == 2 ? far_c : bz + hi;
-                    e[j] = corner_entry1(L, LF, x, y, z);
+                    e[j] = corner_entry1(L, LF, face_far_coord(AXIS, j, 0, bx, far_c), face_far_coord(AXIS, j, 1, by, far_c),
+                                         face_far_coord(AXIS, j, 2, bz, far_c));
                 }
-                gather4(e, f0, f1);
+                table.add4<0>(lv, e, f0, f1, lmax);
             };
             auto flush_group = [&]() __attribute__((always_inline)) {
                 if (acc_any) {
@@ -1497,7 +1516,7 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                     seg_step(std::integral_constant<int, 0x114>{}, 4u);   // row_shr:4
 #pragma unroll
                     for (uint32_t k = 0; k < 8; ++k) { acc0[k] = tail ? acc0[k] : 0.f; acc1[k] = tail ? acc1[k] : 0.f; }
-                    gather8(bx, by, bz, acc0, acc1);
+                    table.add8(lv, bx, by, bz, acc0, acc1, lmax);
 #pragma unroll
                     for (uint32_t k = 0; k < 8; ++k) { acc0[k] = 0.f; acc1[k] = 0.f; }
                 }
@@ -1521,22 +1540,18 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                 const uint32_t Pf = ps.P + (extra_pt ? 1u : 0u);
                 uint32_t ex_raw = 0u;
                 if (extra_pt) ex_raw = reinterpret_cast<const uint32_t *>(extra0)[(size_t)l * n_rows + (valid ? s : s_end - 1u)];
-                auto to_table = [&](uint32_t e, float va, float vb) __attribute__((always_inline)) {  // straight to the table (float atomics)
-                    float *dst = grad_table + ((size_t)L.offset + e) * 2;
-                    unsafeAtomicAdd(dst, va); unsafeAtomicAdd(dst + 1, vb);
-                };
                 auto put_single = [&](uint32_t e, float va, float vb) __attribute__((always_inline)) {  // a record of its own, appended directly
                     const uint32_t bin = e >> kBinShift;
                     const uint32_t slot = atomicAdd(&fill_l[bin], 1u);
                     if (slot < cap) region0[__umul24(bin, cap) + slot] = RowRecord{e, va, vb, 0.f};
-                    else to_table(e, va, vb);
+                    else table_add(grad_table, L, e, va, vb);
                 };
                 // (binary16 planes: the single carries its whole weight wgt = (1 - fx) w or fx w, and fx_q = 0)
                 auto put_single12 = [&](uint32_t e, float wgt, uint32_t raw, float dx, float dy) __attribute__((always_inline)) {
                     const uint32_t bin = e >> kBinShift;
                     const uint32_t slot = atomicAdd(&fill_l[bin], 1u);
                     if (slot < cap) region12[__umul24(bin, cap) + slot] = pack_row12(e & (kBinEntries - 1u), 0u, wgt, 0.f, raw);
-                    else to_table(e, wgt * dx, wgt * dy);
+                    else table_add(grad_table, L, e, wgt * dx, wgt * dy);
                 };
                 // the four (y, z) corner pairs of a cell: e0 = entry of the x corner, e1 = of the x + 1 corner
                 auto pair_entries = [&](uint32_t cx, uint32_t cy, uint32_t cz, uint32_t j, uint32_t &e0, uint32_t &e1) __attribute__((always_inline)) {
@@ -1574,13 +1589,10 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                         const uint32_t p = p0 + c;  // uniform
                         if (extra_pt && p == ps.P) craw0[c] = ex_raw;   // the extra "point": point 0's position, the first pass's pair
                         const uint32_t r0 = craw0[c], r1 = craw1[c];
-                        float2 d = HP
-                            ? make_float2((float)__builtin_bit_cast(_Float16, (unsigned short)(r0 & 0xFFFFu)),
-                                          (float)__builtin_bit_cast(_Float16, (unsigned short)(r0 >> 16)))
-                            : make_float2(__uint_as_float(r0), __uint_as_float(r1));
+                        float2 d = raw_pair<HP>(r0, r1);
                         if (!HP && p == 0u) { d.x += ex0x; d.y += ex0y; }   // (uniform; fp32 planes: summed in place)
                         const bool has = valid && p < Pf && (d.x != 0.f || d.y != 0.f);
-                        const bool finite = fabsf(d.x) <= 3.4028234663852886e38f && fabsf(d.y) <= 3.4028234663852886e38f;
+                        const bool finite = finite2(d.x, d.y);
                         float q[3];
                         point_of(ps, base, p < ps.P ? p : 0u, q);
                         uint32_t cy, cz;
@@ -1621,7 +1633,7 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                                     const float a = w * d.x, b = w * d.y;
                                     if (finite && HP) { put_single12(e0, gx * w, r0, d.x, d.y); put_single12(e1, cfx[c] * w, r0, d.x, d.y); }
                                     else if (finite) { put_single(e0, gx * a, gx * b); put_single(e1, cfx[c] * a, cfx[c] * b); }
-                                    else { to_table(e0, gx * a, gx * b); to_table(e1, cfx[c] * a, cfx[c] * b); }
+                                    else { table_add(grad_table, L, e0, gx * a, gx * b); table_add(grad_table, L, e1, cfx[c] * a, cfx[c] * b); }
                                 }
                             }
                         }
@@ -1697,8 +1709,8 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                                 unpack_row12(rec.x, rec.y, rec.z, el, tt, w, fx, dx, dy);
                                 const uint32_t e0 = (bin << kBinShift) | el;
                                 const uint32_t e1 = L.hashed ? (e0 ^ (((1u << tt) - 1u) & mask)) : e0 + 1u;
-                                to_table(e0, (1.0f - fx) * (w * dx), (1.0f - fx) * (w * dy));
-                                if (fx != 0.f) to_table(e1, fx * (w * dx), fx * (w * dy));
+                                table_add(grad_table, L, e0, (1.0f - fx) * (w * dx), (1.0f - fx) * (w * dy));
+                                if (fx != 0.f) table_add(grad_table, L, e1, fx * (w * dx), fx * (w * dy));
                             }
                             continue;
                         }
@@ -1710,8 +1722,8 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                             const float a = __uint_as_float(rec.y), b = __uint_as_float(rec.z), fx = __uint_as_float(rec.w);
                             const uint32_t tt = rec.x >> kRowEntryBits;
                             const uint32_t e1 = L.hashed ? (e0 ^ (((1u << tt) - 1u) & mask)) : e0 + 1u;
-                            to_table(e0, (1.0f - fx) * a, (1.0f - fx) * b);
-                            if (fx != 0.f) to_table(e1, fx * a, fx * b);
+                            table_add(grad_table, L, e0, (1.0f - fx) * a, (1.0f - fx) * b);
+                            if (fx != 0.f) table_add(grad_table, L, e1, fx * a, fx * b);
                         }
                     }
                     __builtin_amdgcn_wave_barrier();
@@ -1728,20 +1740,15 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                     uint32_t r0 = raw0[0], r1 = raw1[0];
                     const uint32_t pc = p < (uint32_t)kMaxPts ? p : 0u;   // (p is uniform: one relative register move, not a 12-step select chain)
                     r0 = raw0[pc]; r1 = raw1[HP ? 0 : pc];
-                    float2 d = HP
-                        ? make_float2((float)__builtin_bit_cast(_Float16, (unsigned short)(r0 & 0xFFFFu)),
-                                      (float)__builtin_bit_cast(_Float16, (unsigned short)(r0 >> 16)))
-                        : make_float2(__uint_as_float(r0), __uint_as_float(r1));
+                    float2 d = raw_pair<HP>(r0, r1);
                     if (p == 0u) { d.x += ex0x; d.y += ex0y; }   // (uniform)
                     float q[3];
                     point_of(ps, base, p, q);
-                    float fx, fy, fz;
+                    float fx, fy, fz, wk[8];
                     grid_cell(q[0], L.scale, cx, fx);
                     grid_cell(q[1], L.scale, cy, fy);
                     grid_cell(q[2], L.scale, cz, fz);
-                    const float gx = 1.0f - fx, gy = 1.0f - fy, gz = 1.0f - fz;
-                    const float w00 = gx * gy, w10 = fx * gy, w01 = gx * fy, w11 = fx * fy;  // forward's product order
-                    const float wk[8] = {w00 * gz, w10 * gz, w01 * gz, w11 * gz, w00 * fz, w10 * fz, w01 * fz, w11 * fz};
+                    corner_weights(fx, fy, fz, wk);
 #pragma unroll
                     for (uint32_t k = 0; k < 8; ++k) { v0[k] = wk[k] * d.x; v1[k] = wk[k] * d.y; }
                     return valid && (d.x != 0.f || d.y != 0.f);
@@ -1817,16 +1824,16 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                     }
                     if (__ballot(ex_a || ex_b) != 0ull) {
 #pragma unroll
-                        for (uint32_t k = 0; k < 8; ++k) {  // in place (registers): zeros are skipped by gather8
+                        for (uint32_t k = 0; k < 8; ++k) {  // in place (registers): zeros are skipped by the table
                             a0[k] = ex_a ? a0[k] : (ex_b ? b0[k] : 0.f);
                             a1[k] = ex_a ? a1[k] : (ex_b ? b1[k] : 0.f);
                         }
-                        gather8(ex_a ? ax : cx2, ex_a ? ay : cy2, ex_a ? az : cz2, a0, a1);
+                        table.add8(lv, ex_a ? ax : cx2, ex_a ? ay : cy2, ex_a ? az : cz2, a0, a1, lmax);
                         const bool both = ex_a && ex_b;
                         if (__ballot(both) != 0ull) {
 #pragma unroll
                             for (uint32_t k = 0; k < 8; ++k) { b0[k] = both ? b0[k] : 0.f; b1[k] = both ? b1[k] : 0.f; }
-                            gather8(cx2, cy2, cz2, b0, b1);
+                            table.add8(lv, cx2, cy2, cz2, b0, b1, lmax);
                         }
                     }
                     p += paired ? 2u : 1u;
@@ -1836,10 +1843,7 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                 uint32_t r0 = raw0[0], r1 = raw1[0];
 #pragma unroll
                 for (uint32_t k = 1; k < (uint32_t)kMaxPts; ++k) { r0 = (p == k) ? raw0[k] : r0; r1 = (p == k) ? raw1[HP ? 0 : k] : r1; }
-                float2 d = HP
-                    ? make_float2((float)__builtin_bit_cast(_Float16, (unsigned short)(r0 & 0xFFFFu)),
-                                  (float)__builtin_bit_cast(_Float16, (unsigned short)(r0 >> 16)))
-                    : make_float2(__uint_as_float(r0), __uint_as_float(r1));
+                float2 d = raw_pair<HP>(r0, r1);
                 if (p == 0u) { d.x += ex0x; d.y += ex0y; }   // (uniform)
                 const bool has = valid && (d.x != 0.f || d.y != 0.f);
                 const unsigned long long act = __ballot(has);
@@ -1852,8 +1856,8 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
                 grid_cell(q[1], L.scale, cy, fy);
                 grid_cell(q[2], L.scale, cz, fz);
                 const float gx = 1.0f - fx, gy = 1.0f - fy, gz = 1.0f - fz;
-                const float w00 = gx * gy, w10 = fx * gy, w01 = gx * fy, w11 = fx * fy;  // forward's product order
-                const float wk[8] = {w00 * gz, w10 * gz, w01 * gz, w11 * gz, w00 * fz, w10 * fz, w01 * fz, w11 * fz};
+                float wk[8];
+                corner_weights(fx, fy, fz, wk);
                 if (!merge) {  // fine level without the pair structure: every point emits its 8 corners
                     // (appending the two 12-byte records of an x-pair together - one counter update, 24 contiguous
                     // bytes - was measured: 106 -> 114 ms per 141 M evaluations; the store path is paid per lane-store)
@@ -1871,28 +1875,13 @@ __global__ __launch_bounds__(kWave *kWaves, 3) void k_bin_emit(PointSet ps, uint
 #pragma unroll 1
                         for (uint32_t k = 0; k < 8; ++k) {  // (rare path: kept rolled, it must not cost the kernel registers)
                             const float wkk = ((k & 1u) ? fx : gx) * ((k & 2u) ? fy : gy) * ((k & 4u) ? fz : gz);
-                            float *dst = grad_table + ((size_t)L.offset + grid_entry(L, cx + (k & 1u), cy + ((k >> 1) & 1u), cz + (k >> 2))) * 2;
-                            unsafeAtomicAdd(dst, wkk * d.x);
-                            unsafeAtomicAdd(dst + 1, wkk * d.y);
+                            table_add(grad_table, L, grid_entry(L, cx + (k & 1u), cy + ((k >> 1) & 1u), cz + (k >> 2)), wkk * d.x, wkk * d.y);
                         }
                     }
                 }
             }
             if (merge) flush_group();
-            if (merge && merge_any) {  // one record per distinct entry the tile touched on this level; the table is left empty
-                __builtin_amdgcn_wave_barrier();
-                for (uint32_t i = lane; i < kMergeSlots; i += kWave) {
-                    const uint32_t e = keys[i];
-                    if (e != kMergeEmpty) {
-                        const long long a0 = (long long)sums[2 * i], a1 = (long long)sums[2 * i + 1];
-                        keys[i] = kMergeEmpty; sums[2 * i] = 0ull; sums[2 * i + 1] = 0ull;
-                        if (a0 != 0 || a1 != 0)
-                            emit_record(plan, L, l, gw, e, (float)((double)a0 * merge_unscale), (float)((double)a1 * merge_unscale),
-                                        fill, arena, grad_table, lmax);
-                    }
-                }
-                __builtin_amdgcn_wave_barrier();
-            }
+            if (merge && merge_any) table.drain(lv, lane, lmax);
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, off, 64));
             if (lane == 0) lmax_all[wave_in_wg][l] = fmaxf(lmax_all[wave_in_wg][l], lmax);

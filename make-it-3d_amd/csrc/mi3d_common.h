@@ -190,6 +190,60 @@ MI3D_HD void grid_cell(float x, float scale, uint32_t &cell, float &w) {
     w = p - fl;
 }
 
+// the 8 trilinear corner weights of a point with cell fractions (fx, fy, fz) - corner k: bit0 -> +x, bit1 -> +y, bit2 -> +z -
+// in the forward's (tcnn's) multiplication order ((1 * wx) * wy) * wz: forward, scatter and emit all form them here
+MI3D_HD void corner_weights(float fx, float fy, float fz, float (&w)[8]) {
+    const float gx = 1.0f - fx, gy = 1.0f - fy, gz = 1.0f - fz;
+    const float w00 = gx * gy, w10 = fx * gy, w01 = gx * fy, w11 = fx * fy;
+    w[0] = w00 * gz; w[1] = w10 * gz; w[2] = w01 * gz; w[3] = w11 * gz;
+    w[4] = w00 * fz; w[5] = w10 * fz; w[6] = w01 * fz; w[7] = w11 * fz;
+}
+
+// ---- the scatter's fixed-point sums (hashgrid.hip k_bin_emit / k_bin_reduce) ----------------------------------------------
+// round-to-nearest-even of x (|x| < 2^51) as a 64-bit two's complement integer: adding 1.5 * 2^52 in binary64 leaves it in
+// the low mantissa bits.  Same result as __float2ll_rn, 5 VALU operations instead of the ~13 of the software conversion
+// (there is no native float -> int64), four times per record.
+MI3D_HD unsigned long long fixed_point(float x) {
+    const double d = (double)x + 6755399441055744.0;
+    return (unsigned long long)(__builtin_bit_cast(long long, d) - 0x4338000000000000ll);
+}
+
+// The power-of-two scale of a wave's gather table, from the tile's largest gradient tmax (finite, > 0): tmax < 2^ex, so
+// tmax scale < 2^40 - every contribution is a weight <= 1 times a gradient, 6656 of them per tile: |sum| < 2^13 2^40.
+// (The +-126 clamp keeps scale and its inverse normal floats; it binds below 2^-86 only, where sums just lose low bits.)
+struct GatherScale {
+    float scale;
+    double unscale;
+};
+MI3D_HD GatherScale gather_scale(float tmax) {
+    int ex;
+    (void)frexpf(tmax, &ex);  // tmax < 2^ex
+    int k2 = 40 - ex;
+    k2 = k2 > 126 ? 126 : (k2 < -126 ? -126 : k2);
+    return GatherScale{ldexpf(1.0f, k2), ldexp(1.0, -k2)};
+}
+
+// 9-bit slot of the per-wave gather table (kMergeSlots = 512, mi3d_grid_plan.h).  (24-bit multiplies for the spatial hash
+// and this slot hash: tried in round 6, slightly slower - DESIGN.md 3.2, A.11)
+MI3D_HD uint32_t merge_slot(uint32_t e) { return (e * 2654435761u) >> (32 - 9); }
+
+// The coarse role's shared-face pass (hashgrid.hip face_pass): a stencil point that moved one cell along `axis` sits in the
+// cell next to the base cell; corner k of ITS cell (bit d of k: +1 along axis d) lies on the far face when its axis bit is
+// set (the + neighbour) or clear (the - neighbour).  The far face's four corners j = lo | hi << 1, lo / hi the two other
+// axes' bits in x < y < z order:
+MI3D_HD uint32_t face_k1(uint32_t axis, uint32_t j) {   // corner of the + neighbour's cell (axis bit set)
+    const uint32_t lo = j & 1u, hi = j >> 1;
+    return axis == 0 ? (1u | (lo << 1) | (hi << 2)) : (axis == 1 ? (lo | 2u | (hi << 2)) : (lo | (hi << 1) | 4u));
+}
+MI3D_HD uint32_t face_k0(uint32_t axis, uint32_t j) { return face_k1(axis, j) & ~(1u << axis); }   // of the - neighbour's
+// lattice coordinate of far corner j along axis d: far_c (base + 2 for the + neighbour, base - 1 for the - neighbour) along
+// `axis` itself, base + the corner's bit elsewhere
+MI3D_HD uint32_t face_far_coord(uint32_t axis, uint32_t j, uint32_t d, uint32_t base_d, uint32_t far_c) {
+    const uint32_t lo = j & 1u, hi = j >> 1;
+    if (d == axis) return far_c;
+    return base_d + (d == 0 ? lo : (d == 2 ? hi : (axis == 0 ? lo : hi)));
+}
+
 // ---- the scatter's 12-byte x-pair record (binary16 gradient planes; hashgrid.hip k_bin_emit / k_bin_reduce) ---------------
 // The two x-neighbours of a (y, z) corner pair differ in their entry's low bits only, because x enters the hash with prime 1:
 // e(x + 1) = e(x) ^ (2^t - 1) (masked to the level), t = 1 + trailing ones of cx (a +1 carry flips exactly those bits); a

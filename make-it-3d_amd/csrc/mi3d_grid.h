@@ -24,11 +24,7 @@ __device__ __forceinline__ void grid_corners(const GridLevel &L, float x, float 
     grid_cell(x, L.scale, cx, fx);
     grid_cell(y, L.scale, cy, fy);
     grid_cell(z, L.scale, cz, fz);
-    const float gx = 1.0f - fx, gy = 1.0f - fy, gz = 1.0f - fz;
-    // weights in tcnn's multiplication order: ((1 * wx) * wy) * wz
-    const float w00 = gx * gy, w10 = fx * gy, w01 = gx * fy, w11 = fx * fy;
-    c.w[0] = w00 * gz; c.w[1] = w10 * gz; c.w[2] = w01 * gz; c.w[3] = w11 * gz;
-    c.w[4] = w00 * fz; c.w[5] = w10 * fz; c.w[6] = w01 * fz; c.w[7] = w11 * fz;
+    corner_weights(fx, fy, fz, c.w);
 #pragma unroll
     for (uint32_t k = 0; k < 8; ++k)
         c.idx[k] = grid_entry(L, cx + (k & 1u), cy + ((k >> 1) & 1u), cz + ((k >> 2) & 1u));

@@ -81,6 +81,34 @@ void hm_pair_rule(const uint32_t* cell, uint32_t n, uint32_t size, uint32_t* e0,
         e1_from_rule[i] = e0[i] ^ (((t >= 32 ? 0xFFFFFFFFu : (1u << t) - 1u)) & (size - 1u));
     }
 }
+// the scatter emit's pure arithmetic (csrc/mi3d_common.h): the 1.5 * 2^52 rounding, the gather table's power-of-two scale and
+// slot hash, the trilinear corner weights, and the face pass's corner maps
+void hm_fixed_point(const float* x, uint32_t n, int64_t* out) {
+    for (uint32_t i = 0; i < n; i++) out[i] = (int64_t)fixed_point(x[i]);
+}
+void hm_gather_scale(const float* tmax, uint32_t n, float* scale, double* unscale) {
+    for (uint32_t i = 0; i < n; i++) { const GatherScale g = gather_scale(tmax[i]); scale[i] = g.scale; unscale[i] = g.unscale; }
+}
+void hm_merge_slot(const uint32_t* e, uint32_t n, uint32_t* slot) {
+    for (uint32_t i = 0; i < n; i++) slot[i] = merge_slot(e[i]);
+}
+void hm_corner_weights(const float* f, uint32_t n, float* w) {
+    for (uint32_t i = 0; i < n; i++) {
+        float wk[8]; corner_weights(f[i*3], f[i*3+1], f[i*3+2], wk);
+        for (int k = 0; k < 8; k++) w[i*8+k] = wk[k];
+    }
+}
+// for every axis and far corner j: k1, k0, and the corner's lattice coordinates for the + and the - neighbour of cell `base`
+void hm_face_maps(const uint32_t* base, uint32_t* k1, uint32_t* k0, uint32_t* far_plus, uint32_t* far_minus) {
+    for (uint32_t axis = 0; axis < 3; axis++)
+        for (uint32_t j = 0; j < 4; j++) {
+            k1[axis*4+j] = face_k1(axis, j); k0[axis*4+j] = face_k0(axis, j);
+            for (uint32_t d = 0; d < 3; d++) {
+                far_plus[(axis*4+j)*3+d] = face_far_coord(axis, j, d, base[d], base[axis] + 2u);
+                far_minus[(axis*4+j)*3+d] = face_far_coord(axis, j, d, base[d], base[axis] - 1u);
+            }
+        }
+}
 // the MLP backward's tile transposition through LDS: the three byte offsets of a lane (csrc/mi3d_common.h)
 void hm_tr_offsets(uint32_t* wr_d, uint32_t* wr_x, uint32_t* rd, int32_t* row_bytes) {
     for (int lane = 0; lane < 64; lane++) {

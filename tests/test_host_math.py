@@ -132,6 +132,101 @@ def test_row12_record_packing_and_the_x_pair_rule(hm):
         assert 0.99 < same_bin.mean() <= 1.0
 
 
+def test_fixed_point_rounds_like_rint(hm):
+    """fixed_point (csrc/mi3d_common.h: the 1.5 * 2^52 trick both scatter passes use for their 64-bit sums) is
+    round-to-nearest-even of a float as a two's complement integer, for |x| < 2^51."""
+    rng = np.random.default_rng(7)
+    big = np.float32(2.0 ** 51 - 2.0 ** 27)          # the largest float below 2^51: what 2^51 - 1 is closest to from below
+    assert float(big) < 2.0 ** 51 - 1 < float(np.nextafter(big, np.float32(np.inf)))
+    tiny = np.float32(2.0 ** -149)
+    special = np.array([0.5, 1.5, 2.5, 3.5, -0.5, -1.5, -2.5, 4194304.5, -4194303.5, 8388607.5, 0.49999997, -0.49999997,
+                        0.0, -0.0, tiny, -tiny, 2.0 ** -127, -2.0 ** -127, 1.17549435e-38, big, -big, 1.0, -1.0,
+                        -7.0, 123456.75], np.float32)
+    x = np.concatenate([special, (rng.standard_normal(60_000) * 100).astype(np.float32),
+                        (rng.uniform(-1, 1, 40_000) * 2.0 ** rng.integers(-30, 51, 40_000)).astype(np.float32)])
+    assert len(x) >= 100_000 and np.abs(x).max() <= big
+    out = np.empty(len(x), np.int64)
+    hm.hm_fixed_point(_p(x), C.c_uint32(len(x)), _p(out))
+    assert np.array_equal(out, np.rint(x.astype(np.float64)).astype(np.int64))
+
+
+def test_gather_scale_is_a_power_of_two_that_fits(hm):
+    """The gather table's scale for a tile whose largest gradient is tmax, in every binade from the smallest subnormal
+    to FLT_MAX (low end, middle and top of each): a power of two with tmax * scale < 2^40 - and >= 2^39 wherever the
+    +-126 clamp of the exponent is not hit; unscale is its exact inverse."""
+    lo = 2.0 ** np.arange(-149, 128, dtype=np.float64)
+    hi = np.minimum(2 * lo * (1 - 2.0 ** -24), 3.4028234663852886e38)   # the binade's last float (normal binades)
+    tmax = np.unique(np.concatenate([lo, 1.5 * lo, hi]).astype(np.float32))
+    tmax = tmax[(tmax > 0) & np.isfinite(tmax)]
+    assert tmax.min() == np.float32(2.0 ** -149) and tmax.max() == np.finfo(np.float32).max
+    scale, unscale = np.empty(len(tmax), np.float32), np.empty(len(tmax), np.float64)
+    hm.hm_gather_scale(_p(tmax), C.c_uint32(len(tmax)), _p(scale), _p(unscale))
+    m, k = np.frexp(scale.astype(np.float64))
+    assert (m == 0.5).all()                                   # a power of two: 2^(k - 1)
+    k2 = k - 1
+    assert (np.abs(k2) <= 126).all() and np.array_equal(unscale, np.ldexp(1.0, -k2))
+    prod = tmax.astype(np.float64) * scale.astype(np.float64)  # exact
+    assert (prod < 2.0 ** 40).all()
+    want = 40 - np.frexp(tmax.astype(np.float64))[1]          # the exponent before the clamp (tmax < 2^ex)
+    free = np.abs(want) <= 126                                # the clamp is not hit (40 - ex == 126 included)
+    assert np.array_equal(k2[free], want[free])
+    assert free.sum() > 200 and (want[free] == 126).any() and (prod[free] >= 2.0 ** 39).all()
+    # at the clamp: the product still fits (tiny tmax) - a tmax large enough for -126 (> 2^166) does not exist
+    assert (want[~free] > 126).all() and (k2[~free] == 126).all()
+
+
+def test_merge_slot_stays_in_the_table(hm):
+    rng = np.random.default_rng(9)
+    e = np.concatenate([np.arange(1 << 16, dtype=np.uint32), rng.integers(0, 2 ** 32, 100_000, dtype=np.uint64).astype(np.uint32),
+                        np.array([0, 2 ** 19 - 1, 2 ** 32 - 1], np.uint32)])
+    slot = np.empty(len(e), np.uint32)
+    hm.hm_merge_slot(_p(e), C.c_uint32(len(e)), _p(slot))
+    assert slot.max() < 512
+    assert np.array_equal(slot, ((e.astype(np.uint64) * 2654435761) & 0xFFFFFFFF) >> 23)
+
+
+def test_corner_weights_are_the_forward_products(hm):
+    """corner_weights (one routine for forward, scatter and emit) gives ((wx * wy) * wz) per corner, bit for bit."""
+    rng = np.random.default_rng(4)
+    f = rng.uniform(0, 1, (5000, 3)).astype(np.float32)
+    f[0] = 0.0; f[1] = [1.0, 0.0, 0.5]
+    w = np.empty((5000, 8), np.float32)
+    hm.hm_corner_weights(_p(f), C.c_uint32(5000), _p(w))
+    g = np.float32(1.0) - f
+    for k in range(8):
+        wx, wy, wz = ((f if (k >> d) & 1 else g)[:, d] for d in range(3))
+        assert np.array_equal(w[:, k].view(np.uint32), ((wx * wy) * wz).view(np.uint32)), k
+
+
+def test_face_maps_against_the_neighbouring_cells_corners(hm):
+    """The coarse role's shared-face pass (face_k1 / face_k0 / face_far_coord): for each axis and direction, enumerate the
+    8 corners of the neighbouring cell by brute force; the four that are NOT corners of the base cell are the far face,
+    and far corner j (the other two axes' bits in x < y < z order) must be corner k1 (+) / k0 (-) of the neighbour's cell
+    at the coordinates the maps give; the other four are corner k ^ axis-bit of the base cell (the near face)."""
+    base = np.array([10, 20, 30], np.uint32)
+    k1, k0 = np.empty(12, np.uint32), np.empty(12, np.uint32)
+    far_plus, far_minus = np.empty((12, 3), np.uint32), np.empty((12, 3), np.uint32)
+    hm.hm_face_maps(_p(base), _p(k1), _p(k0), _p(far_plus), _p(far_minus))
+    base_corners = {tuple(int(base[d]) + ((k >> d) & 1) for d in range(3)) for k in range(8)}
+    for axis in range(3):
+        others = [d for d in range(3) if d != axis]
+        for sign, ks, far in ((+1, k1, far_plus), (-1, k0, far_minus)):
+            cell = [int(v) for v in base]
+            cell[axis] += sign
+            far_face = {}
+            for k in range(8):
+                c = tuple(cell[d] + ((k >> d) & 1) for d in range(3))
+                if c in base_corners:          # the near face: the base cell's corner with the axis bit flipped
+                    assert c == tuple(int(base[d]) + (((k ^ (1 << axis)) >> d) & 1) for d in range(3))
+                else:
+                    j = ((k >> others[0]) & 1) | (((k >> others[1]) & 1) << 1)
+                    far_face[j] = (k, c)
+            assert sorted(far_face) == [0, 1, 2, 3]
+            for j in range(4):
+                assert int(ks[axis * 4 + j]) == far_face[j][0], (axis, sign, j)
+                assert tuple(int(v) for v in far[axis * 4 + j]) == far_face[j][1], (axis, sign, j)
+
+
 def test_grid_planners_built_for_the_host_plan_what_the_library_plans(hm):
     """csrc/mi3d_grid_plan.h is host code: built with plain g++ (no HIP header, -Wall -Wextra -Werror), its encode and
     scatter planners return the very integers libmi3d.so's plan queries - and so its launches - return, over the whole
