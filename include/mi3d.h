@@ -37,7 +37,7 @@ extern "C" {
  * (marching cubes), Part 9 (texture baking), Part 10 (GroupNorm), Part 12 (the Canny detector), Part 1's
  * mi3d_composite_rays_train_backward_depth and mi3d_march_train_plan and the hash grid's input gradients (mi3d_hashgrid_backward_input of Part 2,
  * mi3d_grid_points_backward_input of Part 3) and their second-order passes (mi3d_hashgrid_backward_input_backward,
- * mi3d_grid_points_backward_input_backward) and Parts 11 and 13 to 17 were added under 5: new symbols only, nothing
+ * mi3d_grid_points_backward_input_backward) and Parts 11 and 13 to 20 were added under 5: new symbols only, nothing
  * existing changed. */
 int mi3d_abi_version(void);
 const char *mi3d_last_error_string(int err);
@@ -1232,6 +1232,100 @@ int mi3d_mesh_collapse_count(unsigned long long nv, unsigned long long nt, void 
 int mi3d_mesh_collapse_emit(unsigned long long nv, unsigned long long nt, void *ws, size_t ws_bytes, float *out_vertices,
                             unsigned long long nv_cap, int32_t *out_triangles, unsigned long long nt_cap,
                             int32_t *vertex_map, unsigned long long *counts, void *stream);
+
+/* ------------------------------------------------------------------ Part 20: the area-adaptive atlas (mesh export) */
+
+/* Part 9's atlas with patch sizes that follow the triangle's edge lengths, for meshes whose triangles differ in size by
+ * orders of magnitude (after Part 14 or Part 19).  Still one patch per triangle with unshared vt, still no inpainting
+ * (the gutter is evaluated at the extrapolated point); vt, xyz and owner keep Part 9's formats, so mi3d_texture_pack,
+ * mi3d_texture_project and mi3d_mesh_shade* consume them unchanged.  This project's own contract - PARITY UNPINNED.
+ * Added under ABI version 5: new symbols only.  (Declared ahead of the point-cloud part, like Part 12.)
+ *
+ * ARITHMETIC: binary32, every operation rounded separately (the unit is built with -ffp-contract=off), no sqrt, no
+ * transcendental function: a NumPy float32 restatement gives the same bits (tests/atlas_adaptive_model.py).  All
+ * counters are integers, no float atomics: two runs give the same bytes.
+ *
+ *   1. MEASURE, thread = triangle.  Squared edge lengths l = (dx dx + dy dy) + dz dz; edge k is the one opposite corner
+ *      k.  rot = the corner opposite the longest edge: rot = 0; if l1 > l0 then 1; if l2 > the larger then 2 (ties go to
+ *      the smallest index; a NaN never wins).  Patch corners A' = corner rot, B' = corner (rot + 1) % 3, C' = corner
+ *      (rot + 2) % 3: a cyclic rotation, the winding stays.  A squared length's BIN is its binary32 biased exponent
+ *      - 127, clamped to [-60, 3], + 60, so in [0, 63]; a biased exponent of 0 or 255 (zero, denormal, infinite, NaN)
+ *      gives bin 0.  One bin step is a factor sqrt 2 in length.  Outputs: shape uint32[nt], the SHAPE WORD rot |
+ *      binAB << 8 | binAC << 16 | bad << 31 with AB = A'B' and AC = A'C'; hist uint32[64][64], hist[binAC][binAB] ADDED
+ *      to (zeroed by the caller), built in LDS per workgroup and merged with integer atomics.  A triangle with a vertex
+ *      index outside [0, nv) is never dereferenced: rot 0, bins (0, 0), bit 31 set; it is sorted and placed like any
+ *      class-(0, 0) triangle but owns nothing, and is COUNTED once in *bad (device uint64, 8-byte aligned, zeroed by the
+ *      caller) - Part 9's convention.
+ *   2. PLAN, host only, a pure function of hist and T in [64, 16384].  LEGS = 2 3 4 6 8 11 16 23 32 45 64 91 128 181 256
+ *      362 (round(2^(k / 2 + 1)), k = 0 .. 15); kmax = the largest k with LEGS[k] + 3 <= T.  Under a SHIFT s in [0, 63] a
+ *      leg's class is clamp(bin - s, 0, kmax); a triangle of class (ka, kb) = (class of binAB, class of binAC) has
+ *      a = LEGS[ka] texel intervals along A'B' and b = LEGS[kb] along A'C', KEY kb * 16 + ka, and a CELL of (a + 3) x
+ *      (b + 3) texels that two triangles of the class share as halves 0 and 1: ceil(count / 2) cells per class.
+ *      SHELVES: height classes kb in descending order, each starting a new shelf at x = 0; inside one, width classes ka
+ *      in descending order; a class goes on in the current shelf at the current x while a cell still fits
+ *      (T - x >= a + 3), else in the next shelf at x = 0; empty classes take nothing.  Rows used = the sum over the
+ *      height classes of shelves * (b + 3).  The plan takes the SMALLEST s whose rows used are <= T, scanning upward
+ *      from 0; if none fits (or hist is empty or sums to more than 2^31 - 1) mi3d_atlas_adaptive_plan returns 0, else 1.
+ *      plan_host int32[MI3D_ATLAS_PLAN_WORDS]:
+ *        [0 .. 16)       s, T, kmax, rows used, height groups G, classes NC, nt, owned texels, legs with bin - s < 0
+ *                        (clamped at the smallest class), legs with bin - s > kmax (clamped at the largest), 0 ...
+ *        [16 .. 144)     G groups of 8 words, in placement order: y0 (first image row), b + 3, shelves, first class
+ *                        record, class records, kb, 0, 0
+ *        [144 .. 3216)   NC class records of 12 words, in placement order: key, a, b, x0 and shelf (within the group) of
+ *                        cell 0, n0 = cells in that first shelf's rest ((T - x0) / (a + 3)), per = cells in a whole
+ *                        shelf (T / (a + 3)), count, start, y0 of the group, cells, 0
+ *        [3216 .. 3472)  key -> class record index, -1 for an empty class
+ *      Cell q of a class: q < n0 at (x0 + q (a + 3), y0 + shelf (b + 3)); else with r = q - n0 at ((r % per) (a + 3),
+ *      y0 + (shelf + 1 + r / per) (b + 3)).  The caller uploads the plan (too large for kernel arguments).
+ *   3. SORT: a stable counting sort of the triangles by key (one 8-bit pass; csrc/mi3d_scan.h's scan).  `start` of a class
+ *      is the number of triangles with a smaller key.  slot uint32[nt]: slot[i] = start + the number of triangles
+ *      j < i of the same key; triangle_of uint32[nt] its inverse.  Triangle i lies in cell (slot[i] - start) / 2 of its
+ *      class as half (slot[i] - start) & 1; the missing partner of an odd count owns nothing.
+ *   4. OWNERSHIP AND UVS: local texel (x, y) of a cell, 0 <= x <= a + 2, 0 <= y <= b + 2.  Half 0 owns it iff x <= a,
+ *      y <= b and b max(x - 1, 0) + a max(y - 1, 0) < a b (integers); half 1 owns the image of that set under
+ *      (x, y) -> (a + 2 - x, b + 2 - y); every other texel of the cell, like margins and unused cells, is owned by no
+ *      one: owner -1, colour 0.  Half 0's set is exactly what a bilinear lookup touches with non-zero weight somewhere
+ *      in the UV triangle, and the halves never meet (tests/test_atlas_adaptive_cpu.py checks all pairs with legs up to
+ *      91).  Half 0 puts A', B', C' at the CENTRES of local texels (0, 0), (a, 0), (0, b), half 1 at their reflections;
+ *      vt = ((X + 0.5) / T, 1 - (Y + 0.5) / T) as in Part 9.  vt float[3 nt][2], row 3 i + k for ORIGINAL corner k:
+ *      faces and everything downstream are unchanged.
+ *   5. TEXEL -> SURFACE POINT: Part 9's formula on the rotated corners: (u, v) = the local coordinates, reflected for
+ *      half 1; s = u / a, t = v / b; p = (A' + s (B' - A')) + t (C' - A'), clamped to [-1, 1] with fmax then fmin (a NaN
+ *      becomes -1).  Part 9's SUPERSAMPLING offsets and storage order.  Per texel: the height group by row, then the
+ *      class by position in the group's strip of shelves (the last class that starts at or before shelf * T + X), at
+ *      most 16 steps each.
+ *
+ *   mi3d_atlas_adaptive_workspace  bytes of device scratch for the sort of nt triangles (0 for nt outside
+ *                                  [1, 2^31 - 1]); host only
+ *   mi3d_atlas_adaptive_measure    step 1
+ *   mi3d_atlas_adaptive_plan       step 2; host only, both pointers host memory
+ *   mi3d_atlas_adaptive_owner      host only: -1, 0 or 1, the half that owns local texel (x, y) of a class-(ka, kb)
+ *                                  cell; -2 for a class above 15 or a texel outside the cell
+ *   mi3d_atlas_adaptive_sort       step 3: shape and the uploaded plan -> slot, triangle_of
+ *   mi3d_atlas_adaptive_uv         step 4: vt
+ *   mi3d_atlas_adaptive_positions  step 5 for the band of image rows [row0, row0 + rows): xyz and owner (may be NULL) as
+ *                                  mi3d_atlas_positions writes them
+ * measure, sort, uv and positions of one atlas go to the same stream in this order, with the plan made from the
+ * histogram measure wrote.  A plan that does not belong to the mesh gives a wrong atlas but no access outside the
+ * arrays: every index taken from it is compared with its bound.  No entry point allocates or synchronises; a bake
+ * reads the host twice (hist before the plan, bad at the end).  Refused (hipErrorInvalidValue), launching nothing: nt
+ * or nv outside [1, 2^31 - 1], T or ssaa or a band outside Part 9's ranges, a workspace that is NULL, too small or not
+ * 8-byte aligned, a bad that is not 8-byte aligned, and every NULL pointer other than `owner`. */
+#define MI3D_ATLAS_PLAN_WORDS 3472
+size_t mi3d_atlas_adaptive_workspace(unsigned long long nt);
+int mi3d_atlas_adaptive_measure(const float *vertices, unsigned long long nv, const int32_t *triangles,
+                                unsigned long long nt, uint32_t *shape, uint32_t *hist, unsigned long long *bad,
+                                void *stream);
+uint32_t mi3d_atlas_adaptive_plan(const uint32_t *hist_host, uint32_t T, int32_t *plan_host);
+int mi3d_atlas_adaptive_owner(uint32_t ka, uint32_t kb, uint32_t x, uint32_t y);
+int mi3d_atlas_adaptive_sort(const uint32_t *shape, unsigned long long nt, const int32_t *plan, void *ws, size_t ws_bytes,
+                             uint32_t *slot, uint32_t *triangle_of, void *stream);
+int mi3d_atlas_adaptive_uv(const uint32_t *shape, const uint32_t *slot, unsigned long long nt, const int32_t *plan,
+                           uint32_t T, float *vt, void *stream);
+int mi3d_atlas_adaptive_positions(const float *vertices, unsigned long long nv, const int32_t *triangles,
+                                  unsigned long long nt, const uint32_t *shape, const uint32_t *triangle_of,
+                                  const int32_t *plan, uint32_t T, uint32_t ssaa, uint32_t row0, uint32_t rows, float *xyz,
+                                  int32_t *owner, void *stream);
 
 /* ------------------------------------------------------------------ Part 11: the refine stage's point cloud */
 

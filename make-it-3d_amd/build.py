@@ -29,13 +29,14 @@ UNITS = [
     ("meshsmooth.hip", ["-ffp-contract=off"]),
     ("meshcollapse.hip", ["-ffp-contract=off"]),
     ("texture.hip", ["-ffp-contract=off"]),
+    ("atlasadaptive.hip", ["-ffp-contract=off"]),
     ("textureviews.hip", ["-ffp-contract=off"]),
     ("meshrender.hip", ["-ffp-contract=off"]),
     ("groupnorm.hip", []),
     ("pointcloud.hip", ["-ffp-contract=off"]),
     ("canny.hip", []),
 ]
-HEADERS = ["mi3d_common.h", "mi3d_grid.h", "mi3d_grid_plan.h", "mi3d_dev.h", "lds_transpose.h", "mi3d_mc_tables.h", "mi3d_meshraster.h", "mi3d_scan.h", "mi3d_incidence.h", "mi3d_workspace.h", os.path.join("..", "..", "include", "mi3d.h")]
+HEADERS = ["mi3d_common.h", "mi3d_grid.h", "mi3d_grid_plan.h", "mi3d_dev.h", "lds_transpose.h", "mi3d_mc_tables.h", "mi3d_meshraster.h", "mi3d_scan.h", "mi3d_incidence.h", "mi3d_workspace.h", "mi3d_atlas_adaptive.h", os.path.join("..", "..", "include", "mi3d.h")]
 
 
 def _newer(src, dst):

@@ -138,6 +138,11 @@ _SIGNATURES = {
     "mi3d_mesh_collapse_rounds": [C.c_uint64, C.c_uint64, C.c_uint64, f32, u32, vp, C.c_size_t, vp, vp],
     "mi3d_mesh_collapse_count": [C.c_uint64, C.c_uint64, vp, C.c_size_t, vp, vp],
     "mi3d_mesh_collapse_emit": [C.c_uint64, C.c_uint64, vp, C.c_size_t, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp],
+    # Part 20 -----------------------------------------------------------------------------------------
+    "mi3d_atlas_adaptive_measure": [vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp],
+    "mi3d_atlas_adaptive_sort": [vp, C.c_uint64, vp, vp, C.c_size_t, vp, vp, vp],
+    "mi3d_atlas_adaptive_uv": [vp, vp, C.c_uint64, vp, u32, vp, vp],
+    "mi3d_atlas_adaptive_positions": [vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, u32, u32, u32, u32, vp, vp, vp],
 }
 
 # host-only queries whose return value is not a hipError_t: (argtypes, restype), bound in lib() like the block below
@@ -154,6 +159,9 @@ _LATE_SIGNATURES = {
     "mi3d_mesh_smooth_workspace": ([C.c_uint64, C.c_uint64], C.c_size_t),
     "mi3d_mesh_shade_backward_workspace": ([C.c_uint64], C.c_size_t),
     "mi3d_mesh_collapse_workspace": ([C.c_uint64, C.c_uint64], C.c_size_t),
+    "mi3d_atlas_adaptive_workspace": ([C.c_uint64], C.c_size_t),
+    "mi3d_atlas_adaptive_plan": ([vp, u32, vp], u32),
+    "mi3d_atlas_adaptive_owner": ([u32, u32, u32, u32], C.c_int),
 }
 
 

@@ -17,6 +17,8 @@
                    vertices - the incidence built once, then passes without atomics over exact fixed-point sums
   bake_texture     the kernels of csrc/texture.hip (include/mi3d.h Part 9): a texel patch per triangle, the field's albedo
                    at every texel's surface point, packed to 8-bit RGB on the device
+  atlas_plan       what atlas="adaptive" does with a mesh (csrc/atlasadaptive.hip, include/mi3d.h Part 20): patches whose
+                   legs follow the triangle's edge lengths - shift, rows used, fill, class histogram, clamped legs
   render_depth     the depth maps of a mesh from V pinhole cameras (csrc/textureviews.hip, include/mi3d.h Part 15)
   bake_views       the same atlas coloured from views by projection: per sample the visibility-tested, angle-weighted
                    mean of the views that see it, the field's albedo where none does (Part 15)
@@ -614,14 +616,120 @@ def _fitting_cell(nt, T):
     return c
 
 
-def bake_texture(model, vertices, triangles, texture_size, ssaa=1):
+ATLASES = ("uniform", "adaptive")
+PLAN_WORDS = 3472                                    # MI3D_ATLAS_PLAN_WORDS
+ATLAS_LEGS = (2, 3, 4, 6, 8, 11, 16, 23, 32, 45, 64, 91, 128, 181, 256, 362)
+
+
+def _check_atlas(atlas, texture_size=0):
+    if not isinstance(atlas, str) or atlas not in ATLASES:
+        raise Mi3dError(f"atlas must be one of {ATLASES} (got {atlas!r})")
+    if atlas == "adaptive" and texture_size is None:
+        raise Mi3dError('atlas="adaptive" lays out a texture: give texture_size too')
+    return atlas
+
+
+def atlas_adaptive_plan(hist, texture_size):
+    """The host plan of include/mi3d.h Part 20 for a 64 x 64 bin histogram (indexed [binAC, binAB]) and a texture size:
+    the int32 [PLAN_WORDS] array in the header's layout, or None if no shift fits.  Host arithmetic: no GPU."""
+    hist = np.ascontiguousarray(np.asarray(hist).reshape(-1))
+    if hist.shape != (4096,) or hist.dtype.kind not in "iu" or (hist < 0).any() or (hist > 2 ** 32 - 1).any():
+        raise Mi3dError("hist must hold 64 x 64 counts below 2^32")
+    T = int(texture_size)
+    if not 0 <= T < 2 ** 32:
+        return None
+    hist = hist.astype(np.uint32)
+    words = np.empty(PLAN_WORDS, np.int32)
+    ok = _lib.lib().mi3d_atlas_adaptive_plan(hist.ctypes.data, T, words.ctypes.data)
+    return words if ok else None
+
+
+def _plan_dict(words):
+    recs = words[144:144 + 12 * int(words[5])].reshape(-1, 12)
+    classes = np.zeros((16, 16), np.int64)               # [kb, ka]
+    classes[recs[:, 0] // 16, recs[:, 0] % 16] = recs[:, 7]
+    T = int(words[1])
+    return {"shift": int(words[0]), "texture_size": T, "kmax": int(words[2]), "rows": int(words[3]),
+            "fill": int(words[7]) / float(T * T), "classes": classes, "clamped_small": int(words[8]),
+            "clamped_large": int(words[9])}
+
+
+def _fitting_plan(hist, nt, T):
+    words = atlas_adaptive_plan(hist, T)
+    if words is None:
+        fit = next((t for t in (1 << k for k in range(6, 15)) if atlas_adaptive_plan(hist, t) is not None), None)
+        hint = f"the smallest power of two that fits is {fit}" if fit else f"no size up to {MAX_TEXTURE} fits"
+        raise Mi3dError(f"{nt} triangles do not fit a {T} x {T} adaptive texture atlas: {hint}")
+    return words
+
+
+class _AdaptiveAtlas:
+    """Steps 1 and 2 of include/mi3d.h Part 20 for a mesh: the shape words, the histogram read back (the first host read),
+    the plan on the host and on the device, the bad-triangle counter (read at the end of a bake)."""
+
+    def __init__(self, vertices, triangles, T):
+        nv, nt, dev = int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
+        self.T, self.nt = T, nt
+        self.shape = torch.empty(nt, dtype=torch.int32, device=dev)
+        hist = torch.zeros(4096, dtype=torch.int32, device=dev)
+        self.bad = torch.zeros(1, dtype=torch.int64, device=dev)
+        _lib.launch("mi3d_atlas_adaptive_measure", vertices, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt,
+                    _lib.ptr(self.shape), _lib.ptr(hist), _lib.ptr(self.bad))
+        self.hist = hist.cpu().numpy().view(np.uint32)
+        self.words = _fitting_plan(self.hist, nt, T)
+        self.plan = torch.from_numpy(self.words).to(dev)
+
+    def layout(self):
+        """Steps 3 and 4: (slot, triangle_of, vt)."""
+        dev, nt = self.shape.device, self.nt
+        ws, ws_bytes = _workspace(dev, "mi3d_atlas_adaptive_workspace", nt)
+        slot = torch.empty(nt, dtype=torch.int32, device=dev)
+        triangle_of = torch.empty(nt, dtype=torch.int32, device=dev)
+        vt = torch.empty(3 * nt, 2, dtype=torch.float32, device=dev)
+        _lib.launch("mi3d_atlas_adaptive_sort", vt, _lib.ptr(self.shape), nt, _lib.ptr(self.plan), _lib.ptr(ws), ws_bytes,
+                    _lib.ptr(slot), _lib.ptr(triangle_of))
+        _lib.launch("mi3d_atlas_adaptive_uv", vt, _lib.ptr(self.shape), _lib.ptr(slot), nt, _lib.ptr(self.plan), self.T,
+                    _lib.ptr(vt))
+        return slot, triangle_of, vt
+
+
+def _atlas_state(vertices, triangles, T, atlas):
+    """What _bake_bands lays the texture out by: the cell size of the uniform atlas, or the measured and planned
+    adaptive one.  A mesh that does not fit raises here, before any colour is evaluated."""
+    if atlas == "adaptive":
+        return _AdaptiveAtlas(vertices, triangles, T)
+    return _fitting_cell(int(triangles.shape[0]), T)
+
+
+def atlas_plan(vertices, triangles, texture_size):
+    """What atlas="adaptive" would do with this mesh at this texture size (include/mi3d.h Part 20), without baking: a
+    dict with `shift` (the chosen s: every leg gets LEGS[bin - s] texel intervals), `rows` (image rows used of
+    texture_size), `fill` (owned texels / texture_size^2), `classes` (int64 [16, 16], triangles per class, indexed
+    [class of A'C', class of A'B']), `clamped_small` / `clamped_large` (legs whose bin - s lies below 0 / above `kmax`:
+    they get more / fewer texels per unit length than the rest) and `kmax`, `texture_size`.  The shift moves in steps
+    of sqrt 2 in length, so `rows` can end well short of texture_size.  A mesh that does not fit raises Mi3dError naming
+    the smallest power of two that does.  One kernel (the measure) and one host read."""
+    T, _ = _check_texture(texture_size, 1)
+    vertices, triangles = _check_bake_mesh(vertices, triangles, "atlas_plan")
+    return _plan_dict(_AdaptiveAtlas(vertices, triangles, T).words)
+
+
+def bake_texture(model, vertices, triangles, texture_size, ssaa=1, atlas="uniform"):
     """The albedo of `model` baked into the per-triangle atlas of include/mi3d.h Part 9.  vertices float32 [nv, 3] and
     triangles int32 [nt, 3] on the GPU (what marching_cubes returns).  Returns (image uint8 [T, T, 3], vt float32
     [3 nt, 2], owner int32 [T, T]) on the same device; image row 0 is the top row, vt of triangle i are rows 3 i .. 3 i + 2.
-    The texels are evaluated in bands of image rows of at most CHUNK points; bands below the last owned texel are not."""
+    The texels are evaluated in bands of image rows of at most CHUNK points; bands below the last owned texel are not.
+
+    atlas="adaptive" lays the patches out by include/mi3d.h Part 20 instead: a triangle's patch has legs that follow its
+    two shorter edges, so that texels per unit length differ by less than a factor 1.6 over all legs that are not
+    clamped (atlas_plan reports those) - the atlas for a mesh after collapse or decimation, whose triangles differ in
+    size by orders of magnitude.  On a mesh of very many tiny triangles every leg ends at the smallest class and the
+    uniform atlas is the better choice.  Same return value, same formats."""
     T, ssaa = _check_texture(texture_size, ssaa)
+    atlas = _check_atlas(atlas)
     vertices, triangles = _check_bake_mesh(vertices, triangles, "bake_texture")
-    return _bake_bands(vertices, triangles, T, ssaa, lambda xyz, owner, row0, rows: _field_albedo(model, xyz))
+    return _bake_bands(vertices, triangles, T, ssaa, lambda xyz, owner, row0, rows: _field_albedo(model, xyz),
+                       _atlas_state(vertices, triangles, T, atlas))
 
 
 def _check_bake_mesh(vertices, triangles, who):
@@ -638,27 +746,40 @@ def _field_albedo(model, xyz):
     return albedo
 
 
-def _bake_bands(vertices, triangles, T, ssaa, colour):
+def _bake_bands(vertices, triangles, T, ssaa, colour, state=None):
     """The band loop the two bakes share: mi3d_atlas_uv, then per band of image rows mi3d_atlas_positions,
     `colour(xyz, owner_band, row0, rows)` -> float32 [rows T ssaa^2, 3], and mi3d_texture_pack; the one host read (the
-    bad-triangle counter) at the end.  Returns (image, vt, owner)."""
+    bad-triangle counter) at the end.  Returns (image, vt, owner).  `state`: what _atlas_state returned (None: the
+    uniform atlas); with an adaptive one the sort, mi3d_atlas_adaptive_uv and mi3d_atlas_adaptive_positions take the
+    places of Part 9's two kernels."""
     nv, nt = int(vertices.shape[0]), int(triangles.shape[0])
-    c = _fitting_cell(nt, T)
+    adaptive = isinstance(state, _AdaptiveAtlas)
+    c = None if adaptive else _fitting_cell(nt, T) if state is None else state
     dev, ss2 = vertices.device, ssaa * ssaa
-    vt = torch.empty(3 * nt, 2, dtype=torch.float32, device=dev)
     image = torch.zeros(T, T, 3, dtype=torch.uint8, device=dev)
     owner = torch.full((T, T), -1, dtype=torch.int32, device=dev)
-    bad = torch.zeros(1, dtype=torch.int64, device=dev)
-    _lib.launch("mi3d_atlas_uv", vt, nt, T, _lib.ptr(vt))
-    cols = T // (c + 1)
-    used = -(-((nt + 1) // 2) // cols) * c              # image rows down to the last cell row that holds a triangle
+    if adaptive:
+        bad = state.bad
+        _, triangle_of, vt = state.layout()
+        used = int(state.words[3])
+    else:
+        vt = torch.empty(3 * nt, 2, dtype=torch.float32, device=dev)
+        bad = torch.zeros(1, dtype=torch.int64, device=dev)
+        _lib.launch("mi3d_atlas_uv", vt, nt, T, _lib.ptr(vt))
+        cols = T // (c + 1)
+        used = -(-((nt + 1) // 2) // cols) * c          # image rows down to the last cell row that holds a triangle
     band = max(4, CHUNK // (T * ss2) // 4 * 4)          # a multiple of 4 rows: every band starts on a 32-bit word
     with torch.no_grad():
         for row0 in range(0, used, band):
             rows = min(band, used - row0)
             xyz = torch.empty(rows * T * ss2, 3, dtype=torch.float32, device=dev)
-            _lib.launch("mi3d_atlas_positions", xyz, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, T, ssaa, row0, rows,
-                        _lib.ptr(xyz), _lib.ptr(owner[row0]), _lib.ptr(bad))
+            if adaptive:
+                _lib.launch("mi3d_atlas_adaptive_positions", xyz, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt,
+                            _lib.ptr(state.shape), _lib.ptr(triangle_of), _lib.ptr(state.plan), T, ssaa, row0, rows,
+                            _lib.ptr(xyz), _lib.ptr(owner[row0]))
+            else:
+                _lib.launch("mi3d_atlas_positions", xyz, _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, T, ssaa, row0,
+                            rows, _lib.ptr(xyz), _lib.ptr(owner[row0]), _lib.ptr(bad))
             albedo = colour(xyz, owner[row0:row0 + rows], row0, rows)
             _lib.launch("mi3d_texture_pack", albedo, _lib.ptr(albedo), _lib.ptr(owner[row0]), T, ssaa, rows,
                         _lib.ptr(image[row0]))
@@ -799,7 +920,7 @@ def render_depth(vertices, triangles, c2w, K, H, W, return_counts=False):
 
 
 def bake_views(model_or_base, vertices, triangles, texture_size, images, c2w, K, ssaa=1, masks=None, weights=None,
-               power=4, min_cos=0.2, depth_tol=0.02):
+               power=4, min_cos=0.2, depth_tol=0.02, atlas="uniform"):
     """The atlas of bake_texture coloured from VIEWS by projection (include/mi3d.h Part 15): every atlas sample takes the
     weighted mean of the views that see it - inside the image, not behind a nearer surface of the mesh (the depth maps
     of render_depth, made once), inside the view's mask, and facing the camera with cos >= `min_cos` - each weighted
@@ -811,15 +932,17 @@ def bake_views(model_or_base, vertices, triangles, texture_size, images, c2w, K,
     float32 tensor [T, T, ssaa^2, 3] of per-sample base colours.  vertices and triangles as bake_texture takes them.
     Returns (image uint8 [T, T, 3], vt float32 [3 nt, 2], owner int32 [T, T], hits uint8 [T, T, ssaa^2]: the number of
     views that contributed to each sample).  Every argument is checked before anything is uploaded or launched.
+    atlas="adaptive": the layout of include/mi3d.h Part 20 (see bake_texture) in place of Part 9's.
 
     The defaults power=4, min_cos=0.2 and depth_tol=0.02 (in world units, for an object in [-1, 1]^3) are choices
     nobody has measured against alternatives."""
     T, ssaa = _check_texture(texture_size, ssaa)
+    atlas = _check_atlas(atlas)
     records, weights, min_cos2, depth_tol, (V, H, W) = check_views(images, c2w, K, masks, weights, power, min_cos,
                                                                    depth_tol)
     vertices, triangles = _check_bake_mesh(vertices, triangles, "bake_views")
     dev, ss2 = vertices.device, ssaa * ssaa
-    _fitting_cell(int(triangles.shape[0]), T)
+    state = _atlas_state(vertices, triangles, T, atlas)
     base = None
     if not hasattr(model_or_base, "density"):
         if _shape(model_or_base) == (3,):
@@ -852,7 +975,7 @@ def bake_views(model_or_base, vertices, triangles, texture_size, images, c2w, K,
                     _lib.ptr(hits[row0]))
         return out
 
-    image, vt, owner = _bake_bands(vertices, triangles, T, ssaa, colour)
+    image, vt, owner = _bake_bands(vertices, triangles, T, ssaa, colour, state)
     return image, vt, owner, hits
 
 
@@ -1404,9 +1527,10 @@ def vertex_normals(model, vertices):
 
 def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False, min_faces=None,
            min_diagonal=None, largest=False, decimate=None, target_faces=None, views=None, smooth=None, preview=None,
-           collapse=None):
+           collapse=None, atlas="uniform"):
     """What NeRFRenderer.export_mesh does (see there).  `S` only sizes the reference's chunks and is ignored."""
     del S
+    atlas = _check_atlas(atlas, texture_size)                   # before any work
     collapsing = _check_collapse_option(collapse)              # before any work
     smoothing = _check_smooth_option(smooth)                    # before any work
     if preview is not None:                                     # before any work
@@ -1450,17 +1574,17 @@ def export(model, path, resolution=None, S=128, texture_size=None, ssaa=1, norma
         if smoothing is not None:                               # before the atlas check, the colours, the bakes, the normals
             vertices = _smooth_export(vertices, triangles, smoothing, h)
         if texture_size is not None:
-            _fitting_cell(triangles.shape[0], texture_size)     # refuse before the field is evaluated anywhere
+            _atlas_state(vertices, triangles, texture_size, atlas)   # refuse before the field is evaluated anywhere
         albedo = vertex_albedo(model, vertices)
         if views is not None:                                   # after the floater filter and the decimation
-            image, vt = bake_views(model, vertices, triangles, texture_size, ssaa=ssaa, **views)[:2]
+            image, vt = bake_views(model, vertices, triangles, texture_size, ssaa=ssaa, atlas=atlas, **views)[:2]
             if fit is not None:                                 # the bake corrected by what the renderer reads from it
                 start = image.float() / 255.0
                 fitted = fit_texture(vertices, triangles, vt, start, views["images"], views["c2w"], views["K"],
                                      views.get("masks"), views.get("weights"), **fit)
                 image = torch.where(fitted == start, image, quantise(fitted))     # an untouched texel keeps its byte
         elif texture_size is not None:
-            image, vt, _ = bake_texture(model, vertices, triangles, texture_size, ssaa)
+            image, vt, _ = bake_texture(model, vertices, triangles, texture_size, ssaa, atlas)
         vn = vertex_normals(model, vertices).cpu().numpy() if normals else None
         if preview is not None:                                 # the mesh as it is written: after the bake
             textured = texture_size is not None

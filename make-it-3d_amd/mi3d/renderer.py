@@ -119,7 +119,7 @@ class NeRFRenderer(nn.Module):
     @torch.no_grad()
     def export_mesh(self, path, resolution=None, S=128, texture_size=None, ssaa=1, normals=False, min_faces=None,
                     min_diagonal=None, largest=False, decimate=None, target_faces=None, views=None, smooth=None,
-                    preview=None, collapse=None):
+                    preview=None, collapse=None, atlas="uniform"):
         """renderer.py:157-191 + the file writing of :300-328, reached through main.py's `--save_mesh`: sigma on the
         `resolution`^3 lattice of [-1, 1]^3 (default grid_size), marching cubes at min(mean_density, density_thresh)
         (density_thresh without cuda_ray) on the GPU (mi3d.mesh), `<path>/mesh.obj` + `mesh.mtl`.  By default
@@ -183,11 +183,20 @@ class NeRFRenderer(nn.Module):
         before `smooth=`, the atlas check, the colours, the bakes and the normals, which are all re-evaluated from the
         field at the new vertices.  `max_error` (None: no limit) bounds the quadric error of a collapse, `max_rounds`
         (default 256) the rounds.  The option is checked before any work.  With `collapse=None` nothing of this runs and
-        the files are byte for byte what they were without the argument."""
+        the files are byte for byte what they were without the argument.  `atlas="adaptive"` (with `texture_size`;
+        without it: Mi3dError before any work) lays the texture out by include/mi3d.h Part 20 instead of
+        Part 9: every triangle's patch has legs that follow its two shorter edges, so that a mesh after `collapse=` or
+        `decimate=` gets about the same number of texels per unit length everywhere (within a factor 1.6 over the legs
+        that are not clamped; mesh.atlas_plan reports shift, fill and clamped legs).  The files keep their formats; a
+        mesh that does not fit raises Mi3dError naming the smallest power of two that does, before the field is
+        evaluated.  For very many tiny triangles the uniform atlas is the better choice.  An unknown value raises
+        Mi3dError; with the default `atlas="uniform"` launches, bytes and files are what they were without the
+        argument."""
         from . import mesh
         return mesh.export(self, path, resolution, S, texture_size=texture_size, ssaa=ssaa, normals=normals,
                            min_faces=min_faces, min_diagonal=min_diagonal, largest=largest, decimate=decimate,
-                           target_faces=target_faces, views=views, smooth=smooth, preview=preview, collapse=collapse)
+                           target_faces=target_faces, views=views, smooth=smooth, preview=preview, collapse=collapse,
+                           atlas=atlas)
 
     @torch.no_grad()
     def export_point_cloud(self, outputdir, poses, ref_rgb, fov, H, W, **kwargs):
